@@ -51,6 +51,11 @@ FPMUL_G2_VALID = (63 * 18 + 5 * 36) + 8 + 8 + 16
 LANES_PER_CLK = 256 * 4 * 16
 NOMINAL_GHZ = 2.4
 PEAK_MACS = LANES_PER_CLK * NOMINAL_GHZ * 1e9
+# --dump-outputs: Gt rows sampled from the shard (16384 x 144 float64 = 18.9 MB) and the seed that picks them; ok is written whole
+# up to DUMP_OK_MAX pairs (32 MB of float64), else at the sampled rows - under 64 MB in all
+DUMP_GT_ROWS = 1 << 14
+DUMP_OK_MAX = 1 << 22
+DUMP_SEED = 0xD0
 
 
 def usable_cores():
@@ -119,6 +124,23 @@ def launch_ranks(n_ranks, argv):
     return rc
 
 
+def dump_outputs(path, out_gt, ok, flag):
+    """what the timed step hands its caller (Gt rows, ok bytes, AND flag), as float64 .npy files that two builds can be compared by:
+    a u64 limb does not fit a float64's mantissa, its two u32 halves do"""
+    import numpy as np
+    import torch
+    n = out_gt.shape[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(n, size=min(n, DUMP_GT_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(out_gt.device)
+    gt = out_gt.index_select(0, idx).cpu().numpy().view(np.uint64)
+    halves = np.stack([gt & np.uint64(0xFFFFFFFF), gt >> np.uint64(32)], axis=-1).reshape(len(rows), 144)
+    ok_h = ok.cpu().numpy() if n <= DUMP_OK_MAX else ok.index_select(0, idx).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("gt", halves), ("gt_rows", rows), ("ok", ok_h), ("all_ok", flag.cpu().numpy())):
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,8 +159,14 @@ def main():
     ap.add_argument("--collective", choices=("torch", "abi"), default=os.environ.get("ZKP_BENCH_COLLECTIVE", "torch"),
                     help="torch: all-reduce(MIN) through torch.distributed (nccl = RCCL); abi: the step is zkp_pairing_gt_check_batch_allreduce_dev "
                          "on the library's own RCCL communicator (what a Rust / C host runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to DIR/<name>.npy (float64; rank 0's shard): gt = a fixed "
+                         "seeded sample of %d Gt rows, each u64 limb as two exact u32 halves (low first), gt_rows = their indices, "
+                         "ok = the per-pair identity bytes, all_ok = the AND flag" % DUMP_GT_ROWS)
     ap.add_argument("--rank-echo", action="store_true", help=argparse.SUPPRESS)   # launcher self-test: ranks report and exit before any GPU use
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.bare:
         args.no_cpu_baseline = True
 
@@ -263,6 +291,9 @@ def main():
     w64 = torch.arange(1, 73, dtype=torch.int64, device=dev) * 0x1E3779B97F4A7C15 | 1
     gt_fp = [int(out_gt.sum().item()), int((out_gt * w64).sum().item())]
     del w64
+    # before any leg below writes the same buffers again (config 4 and points_check reuse ok and flag)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_gt, ok, flag)
 
     # ---- diagnosis of an N > 1 line (outside the timed region, every rank): what each rank's kernels take on their own, what
     # the collective takes on its own, each rank's wall time of the timed steps - gathered to rank 0.  A bad scaling curve then
