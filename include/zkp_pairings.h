@@ -21,6 +21,9 @@
  *                                   conjugate, frobenius_map (the TRUE map),  src/fp12.rs:99-210 (:143-170 is wrong)
  *                                   invert, mul_by_nonresidue, mul_by_1 / 01  src/fp2.rs:95-102,161-168,278-296, src/fp6.rs:102-141,291-309
  *   zkp_points_check_batch          raw points -> Fp::from_bytes, is_valid, pairing check in one call  src/fp.rs:165-207, src/g1.rs:49-62, src/g2.rs:57-69
+ *   zkp_fp_sqrt_batch / fp2         Fp::sqrt, Fp2::sqrt                      src/fp.rs:280-300, src/fp2.rs:231-273
+ *   zkp_g*_(de)compress_batch,      compressed points (48 / 96 B): decompression = x^3 + b, a square root, the sort flag's sign;
+ *   zkp_points_check_compressed_*   the points check on compressed inputs (see "compressed points" below)
  *   zkp_pairing_*_multi             the same pairing()/check over several GPUs from ONE host thread
  *   zkp_comm_*, zkp_*_allreduce     one rank per GPU: the check + the path's one RCCL collective
  *
@@ -163,7 +166,7 @@ int zkp_g2_mul_batch(zkp_ctx* ctx, const uint64_t* base, size_t base_stride, con
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).
  * G1: x(48) | y(48) = 96 bytes; G2: x.c1 | x.c0 | y.c1 | y.c0 = 192 bytes (c1 first, the usual BLS12-381
- * serialisation order).  The top three bits of byte 0 are flags: 0x80 compressed (rejected), 0x40 infinity
+ * serialisation order).  The top three bits of byte 0 are flags: 0x80 compressed (rejected here; zkp_g*_decompress_batch below), 0x40 infinity
  * (all other bytes must be zero), 0x20 must be clear.
  * status[i]: 0 ok, 1 coordinate >= p, 2 bad flags / malformed infinity.  Decoded points go out in wire
  * format (+ infinity byte) and can be fed to zkp_g*_is_valid_batch / zkp_pairing_*. */
@@ -244,6 +247,36 @@ int zkp_points_check_batch(zkp_ctx* ctx, const uint8_t* g1_bytes, const uint8_t*
                            uint8_t* st2, uint8_t* ok, int* all_ok);
 int zkp_points_check_batch_dev(zkp_ctx* ctx, const void* d_g1_bytes, const void* d_g2_bytes, size_t n_checks, size_t k, void* d_st1,
                                void* d_st2, void* d_ok, void* d_all_ok, void* stream);
+
+/* ---- compressed points (48 B per G1 point, 96 B per G2 point): square roots, codec, points check -------------------------------
+ * The usual BLS12-381 compressed serialisation: x only, big-endian, G2 as x.c1 | x.c0 (c1 first, as the uncompressed codec).  The top
+ * three bits of byte 0 are flags: 0x80 compressed (must be set, else status 2), 0x40 infinity (every other bit of the string, the sort
+ * flag included, must be zero, else status 2), 0x20 sort flag = y is the lexicographically larger of y and -y (G1: y > (p-1)/2; G2:
+ * compare c1, and c0 when c1 == 0).
+ * Decompression: status[i] (zkp_point_status) 0 ok, 1 x (either coordinate on G2) >= p, 2 bad flags / malformed infinity,
+ * 3 x^3 + b has no square root (ZKP_POINT_NOT_ON_CURVE).  Otherwise the root the sort flag selects: the unique point (x, y) on the
+ * curve; y = 0 (possible on G2 only) decodes to (x, 0) whatever the flag says.  The subgroup is NOT checked (is_valid does that, as
+ * after zkp_g*_decode_batch).  Output: the wire formats above + infinity byte; the identity decodes to (0, 1); rejected points to 0.
+ * Compression reads x and the sign of y only: it does not assume the point is valid.  inf may be NULL.
+ * The square roots stand in for Fp::sqrt (src/fp.rs:280-300: a^((p+1)/4), checked by squaring) and Fp2::sqrt (src/fp2.rs:231-273,
+ * step for step, the alpha == -1 branch included): out[i] is the reference's root bit for bit, or zero where the reference returns
+ * Err / None; is_square[i] = 1 iff it returns Ok / Some.  Host pointers only, like zkp_fp_op_batch; validation mode applies.
+ * zkp_points_check_compressed_batch[_dev] is zkp_points_check_batch[_dev] with decompression as its decode step: same status bytes,
+ * same validate-first compaction, same device-resident count (the _dev flavour is asynchronous and capturable). */
+int zkp_fp_sqrt_batch(zkp_ctx* ctx, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square);    /* src/fp.rs:280-300 */
+int zkp_fp2_sqrt_batch(zkp_ctx* ctx, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square);   /* src/fp2.rs:231-273 */
+int zkp_g1_decompress_batch(zkp_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* out_g1, uint8_t* out_inf, uint8_t* status);
+int zkp_g2_decompress_batch(zkp_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* out_g2, uint8_t* out_inf, uint8_t* status);
+int zkp_g1_compress_batch(zkp_ctx* ctx, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int zkp_g2_compress_batch(zkp_ctx* ctx, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* out_bytes);
+int zkp_g1_decompress_batch_dev(zkp_ctx* ctx, const void* d_bytes, size_t n, void* d_out_g1, void* d_out_inf, void* d_status, void* stream);
+int zkp_g2_decompress_batch_dev(zkp_ctx* ctx, const void* d_bytes, size_t n, void* d_out_g2, void* d_out_inf, void* d_status, void* stream);
+int zkp_g1_compress_batch_dev(zkp_ctx* ctx, const void* d_g1, const void* d_inf /* may be NULL */, size_t n, void* d_out_bytes, void* stream);
+int zkp_g2_compress_batch_dev(zkp_ctx* ctx, const void* d_g2, const void* d_inf /* may be NULL */, size_t n, void* d_out_bytes, void* stream);
+int zkp_points_check_compressed_batch(zkp_ctx* ctx, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1,
+                                      uint8_t* st2, uint8_t* ok, int* all_ok);
+int zkp_points_check_compressed_batch_dev(zkp_ctx* ctx, const void* d_g1_bytes, const void* d_g2_bytes, size_t n_checks, size_t k, void* d_st1,
+                                          void* d_st2, void* d_ok, void* d_all_ok, void* stream);
 
 /* validation mode (zkp_set_validate) on the device-pointer entry points: the range check of the inputs runs on the caller's
  * stream and ORs into a word inside the context - no host synchronisation in the *_dev call itself.  This call waits for

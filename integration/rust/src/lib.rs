@@ -125,6 +125,26 @@ extern "C" {
     pub fn zkp_points_check_batch_dev(ctx: *mut ZkpCtx, d_g1_bytes: *const c_void, d_g2_bytes: *const c_void, n_checks: usize, k: usize,
                                       d_st1: *mut c_void, d_st2: *mut c_void, d_ok: *mut c_void, d_all_ok: *mut c_void,
                                       stream: *mut c_void) -> c_int;
+    // compressed points (48 B per G1 point, 96 B per G2 point) and the square roots of Fp / Fp2 (src/fp.rs:280-300, src/fp2.rs:231-273)
+    pub fn zkp_fp_sqrt_batch(ctx: *mut ZkpCtx, a: *const u64, n: usize, out: *mut u64, is_square: *mut u8) -> c_int;
+    pub fn zkp_fp2_sqrt_batch(ctx: *mut ZkpCtx, a: *const u64, n: usize, out: *mut u64, is_square: *mut u8) -> c_int;
+    pub fn zkp_g1_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g1: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_g2_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g2: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_g1_compress_batch(ctx: *mut ZkpCtx, g1: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;
+    pub fn zkp_g2_compress_batch(ctx: *mut ZkpCtx, g2: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;
+    pub fn zkp_g1_decompress_batch_dev(ctx: *mut ZkpCtx, d_bytes: *const c_void, n: usize, d_out_g1: *mut c_void, d_out_inf: *mut c_void,
+                                       d_status: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_g2_decompress_batch_dev(ctx: *mut ZkpCtx, d_bytes: *const c_void, n: usize, d_out_g2: *mut c_void, d_out_inf: *mut c_void,
+                                       d_status: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_g1_compress_batch_dev(ctx: *mut ZkpCtx, d_g1: *const c_void, d_inf: *const c_void, n: usize, d_out_bytes: *mut c_void,
+                                     stream: *mut c_void) -> c_int;
+    pub fn zkp_g2_compress_batch_dev(ctx: *mut ZkpCtx, d_g2: *const c_void, d_inf: *const c_void, n: usize, d_out_bytes: *mut c_void,
+                                     stream: *mut c_void) -> c_int;
+    pub fn zkp_points_check_compressed_batch(ctx: *mut ZkpCtx, g1_bytes: *const u8, g2_bytes: *const u8, n_checks: usize, k: usize, st1: *mut u8,
+                                             st2: *mut u8, ok: *mut u8, all_ok: *mut c_int) -> c_int;
+    pub fn zkp_points_check_compressed_batch_dev(ctx: *mut ZkpCtx, d_g1_bytes: *const c_void, d_g2_bytes: *const c_void, n_checks: usize,
+                                                 k: usize, d_st1: *mut c_void, d_st2: *mut c_void, d_ok: *mut c_void, d_all_ok: *mut c_void,
+                                                 stream: *mut c_void) -> c_int;
     /// one rank per GPU: the path's ONE collective (RCCL all-reduce(MIN) of the AND flag) behind the ABI
     pub fn zkp_comm_unique_id(out_id: *mut c_void) -> c_int;
     pub fn zkp_comm_init_rank(ctx: *mut ZkpCtx, nranks: c_int, rank: c_int, unique_id: *const c_void) -> c_int;

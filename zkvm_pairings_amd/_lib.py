@@ -61,6 +61,18 @@ SIGNATURES = {
     "zkp_g2_encode_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "zkp_points_check_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_int)]),
     "zkp_points_check_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_fp_sqrt_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_fp2_sqrt_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g2_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g1_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "zkp_g2_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "zkp_g1_decompress_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_g2_decompress_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_g1_compress_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g2_compress_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_points_check_compressed_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, ctypes.POINTER(c_int)]),
+    "zkp_points_check_compressed_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "zkp_comm_unique_id": (c_int, [c_vp]),
     "zkp_comm_init_rank": (c_int, [c_vp, c_int, c_int, c_vp]),
     "zkp_comm_destroy": (c_int, [c_vp]),

@@ -206,6 +206,105 @@ def raw_points(eng, n, which, seed):
     return raw, cls
 
 
+# ------------------------------------------------------------------------------------------------- compressed points
+HALF = (P - 1) // 2
+_HALF_LIMBS = _limbs(HALF)
+
+
+def _gt_half(y):
+    """(n, 6) canonical limbs -> bool (n,): y > (p-1)/2, i.e. y is the lexicographically larger of y and -y"""
+    gt, eq = np.zeros(y.shape[0], dtype=bool), np.ones(y.shape[0], dtype=bool)
+    for w in range(5, -1, -1):
+        gt |= eq & (y[:, w] > _HALF_LIMBS[w])
+        eq &= y[:, w] == _HALF_LIMBS[w]
+    return gt
+
+
+def compress_np(pts, which, inf=None):
+    """(n, 12 | 24) canonical limbs -> (n, 48 | 96) compressed big-endian bytes on the host (numpy only): x (G2: x.c1 | x.c0) with
+    0x80, plus 0x20 when y is the larger root (G2: decided by y.c1, by y.c0 when y.c1 == 0); 0xc0 and zeros for an infinity"""
+    pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, 12 * which)
+    n = pts.shape[0]
+    out = to_bytes(pts, which)[:, :48 * which].copy()
+    if which == 1:
+        big = _gt_half(pts[:, 6:12])
+    else:
+        y1_zero = ~pts[:, 18:24].any(axis=1)
+        big = np.where(y1_zero, _gt_half(pts[:, 12:18]), _gt_half(pts[:, 18:24]))
+    out[:, 0] |= np.where(big, 0xA0, 0x80).astype(np.uint8)
+    if inf is not None:
+        i = np.asarray(inf, dtype=bool).reshape(n)
+        out[i] = 0
+        out[i, 0] = 0xC0
+    return out
+
+
+def _x_not_on_curve(which, count):
+    """`count` x coordinates (Fp, or Fp2 as (c0, c1)) for which x^3 + b has no square root: no point has them"""
+    found, x = [], 1
+    while len(found) < count:
+        x += 1
+        if which == 1:
+            if pow((x * x * x + 4) % P, HALF, P) == P - 1:
+                found.append(x)
+        else:
+            X = (x, x + 7)
+            x2 = ((X[0] * X[0] - X[1] * X[1]) % P, 2 * X[0] * X[1] % P)
+            a0, a1 = (x2[0] * X[0] - x2[1] * X[1] + 4) % P, (x2[0] * X[1] + x2[1] * X[0] + 4) % P
+            if pow((a0 * a0 + a1 * a1) % P, HALF, P) == P - 1:      # Fp2 square <=> its norm is a square in Fp
+                found.append(X)
+    return found
+
+
+# compressed classes: (decompression status, infinity byte, status byte of the points check)
+COMPRESSED_CLASSES = ("valid", "valid_negated", "x_ge_p", "x_not_on_curve", "wrong_subgroup", "infinity", "bad_infinity", "uncompressed_flag")
+COMPRESSED_EXPECT = {"valid": (0, 0, 0), "valid_negated": (0, 0, 0), "x_ge_p": (1, 0, 1), "x_not_on_curve": (3, 0, 3), "wrong_subgroup": (0, 0, 4),
+                     "infinity": (0, 1, 0), "bad_infinity": (2, 0, 2), "uncompressed_flag": (2, 0, 2)}
+
+
+def raw_points_compressed(eng, n, which, seed):
+    """n compressed byte strings with seeded fractions of every class of COMPRESSED_CLASSES -> (bytes (n, 48 | 96), class index (n,),
+    points (n, 12 | 24): the curve point behind each string where there is one - the subgroup point, its negation, the point outside
+    the subgroup - and zeros elsewhere).  raw_points stays the uncompressed generator."""
+    sel = (synthetic.splitmix64(seed ^ 0xC0C0A, n) % np.uint64(1024)).astype(np.int64)
+    cls = np.zeros(n, dtype=np.int64)
+    for lo, hi, c in ((0, 256, 1), (256, 264, 2), (264, 272, 3), (272, 280, 4), (280, 284, 5), (284, 288, 6), (288, 292, 7)):
+        cls[(sel >= lo) & (sel < hi)] = c
+    gen = synthetic.G1_GENERATOR if which == 1 else synthetic.G2_GENERATOR
+    mul = eng.g1_mul if which == 1 else eng.g2_mul
+    pts, _ = mul(gen, synthetic.scalars(seed, n))
+    ycol = 6 * which
+    neg = np.flatnonzero(cls == 1)
+    if neg.size:        # -P = (x, -y) through the engine's field negation, coordinate by coordinate
+        for c in range(which):
+            pts[neg, ycol + 6 * c:ycol + 6 * c + 6] = eng.fp_op("neg", np.ascontiguousarray(pts[neg, ycol + 6 * c:ycol + 6 * c + 6]))
+    wrong = np.flatnonzero(cls == 4)
+    if wrong.size:
+        w, winf = mul(curve_point_outside_subgroup(which), synthetic.scalars(seed ^ 0x5B, wrong.size))
+        assert not winf.any()
+        pts[wrong] = w
+    none = np.isin(cls, (2, 3, 5))
+    pts[none] = 0
+    raw = compress_np(pts, which)
+    nc = np.flatnonzero(cls == 2)
+    for j, i in enumerate(nc):         # first encoded coordinate := p + small: >= p, < 2^381 (no flag bit)
+        raw[i, :48] = np.frombuffer((P + 1 + (j & 0xFFFF)).to_bytes(48, "big"), dtype=np.uint8)
+        raw[i, 0] |= 0x80
+    off = np.flatnonzero(cls == 3)
+    if off.size:
+        pool = _x_not_on_curve(which, 32)
+        for j, i in enumerate(off):
+            x = pool[j % len(pool)]
+            fe = [x] if which == 1 else [x[1], x[0]]
+            raw[i] = np.frombuffer(b"".join(v.to_bytes(48, "big") for v in fe), dtype=np.uint8)
+            raw[i, 0] |= 0x80 | (0x20 if j & 1 else 0)
+    raw[cls == 5] = 0
+    raw[cls == 5, 0] = 0xC0
+    raw[cls == 6, 0] |= 0x40           # infinity flag on a finite point's bytes
+    raw[cls == 7, 0] &= 0x7F           # compression flag cleared
+    return raw, cls, pts
+
+
 def run_config5(eng, n, seed=0x5EED5):
     r = {}
     decoded, raws = {}, {}

@@ -17,6 +17,7 @@
 #include "../../include/zkp_pairings.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
+#include "zkp_compress.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -1053,8 +1054,11 @@ enum { PC_G1 = 0, PC_G2, PC_INF1, PC_INF2, PC_DEC, PC_VAL, PC_ST1, PC_ST2, PC_OK
 // host: asynchronous on `s` like every other *_dev entry point, and capturable into a hipGraph once its workspaces exist.  (Round 5 read
 // the count back - 4 bytes, one hipStreamSynchronize - to size the grids on the host.)  The thread family has no such kernels: it
 // runs the fused pairing on every check and fails the invalid ones afterwards (k_checks_merge), as round 4 did.
+// `compressed` picks the input format of the decode step: uncompressed (96 / 192 B per point, k_decode) or compressed (48 / 96 B per
+// point, zkp_compress.hip - decompression status 3 is "not on the curve", which k_points_merge passes through as ZKP_POINT_NOT_ON_CURVE).
+// Everything after the decode step is the same for both.
 static int points_check_dev(zkp_ctx* c, const void* b1, const void* b2, size_t n_checks, size_t k, void* st1, void* st2, void* ok, int* all_ok,
-                            hipStream_t s) {
+                            hipStream_t s, bool compressed) {
     const size_t np = n_checks * k;
     const bool compact = n_checks && k && zkp::coop_selected(&c->coop, c->kernel) && zkp::coop_supports_k(k);
     int rc;
@@ -1075,9 +1079,15 @@ static int points_check_dev(zkp_ctx* c, const void* b1, const void* b2, size_t n
     uint8_t* s2 = st2 ? (uint8_t*)st2 : (uint8_t*)c->pc[PC_ST2];
     uint8_t* okb = ok ? (uint8_t*)ok : (uint8_t*)c->pc[PC_OK];
     if (np) {
-        if ((rc = codec_dev(c, true, 2, b1, nullptr, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s)) ||
-            (rc = codec_dev(c, true, 4, b2, nullptr, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s)) ||
-            (rc = valid_dev(c, 1, c->pc[PC_G1], c->pc[PC_INF1], np, val1, s)) || (rc = valid_dev(c, 2, c->pc[PC_G2], c->pc[PC_INF2], np, val2, s)))
+        if (compressed) {
+            if ((rc = coop_rc(c, "g1_decompress", zkp_cmp::decompress(1, b1, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s))) ||
+                (rc = coop_rc(c, "g2_decompress", zkp_cmp::decompress(2, b2, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s))))
+                return rc;
+        } else if ((rc = codec_dev(c, true, 2, b1, nullptr, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s)) ||
+                   (rc = codec_dev(c, true, 4, b2, nullptr, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s))) {
+            return rc;
+        }
+        if ((rc = valid_dev(c, 1, c->pc[PC_G1], c->pc[PC_INF1], np, val1, s)) || (rc = valid_dev(c, 2, c->pc[PC_G2], c->pc[PC_INF2], np, val2, s)))
             return rc;
         hipLaunchKernelGGL(k_points_merge, dim3(grid_for(np, 256)), dim3(256), 0, s, dec1, val1, (uint8_t*)c->pc[PC_INF1], np, s1);
         hipLaunchKernelGGL(k_points_merge, dim3(grid_for(np, 256)), dim3(256), 0, s, dec2, val2, (uint8_t*)c->pc[PC_INF2], np, s2);
@@ -1115,7 +1125,35 @@ int zkp_points_check_batch_dev(zkp_ctx* c, const void* g1_bytes, const void* g2_
                                void* all_ok, void* stream) {
     if (!c || too_many(n_checks, k) || (n_checks && k && (!g1_bytes || !g2_bytes))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return points_check_dev(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, (int*)all_ok, S(stream));
+    return points_check_dev(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, (int*)all_ok, S(stream), false);
+}
+int zkp_points_check_compressed_batch_dev(zkp_ctx* c, const void* g1_bytes, const void* g2_bytes, size_t n_checks, size_t k, void* st1, void* st2,
+                                          void* ok, void* all_ok, void* stream) {
+    if (!c || too_many(n_checks, k) || (n_checks && k && (!g1_bytes || !g2_bytes))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return points_check_dev(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, (int*)all_ok, S(stream), true);
+}
+
+// ---- compressed point codec on resident buffers (zkp_compress.hip): 48 B per G1 point, 96 B per G2 point
+int zkp_g1_decompress_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g1, void* out_inf, void* status, void* stream) {
+    if (!c || too_many(n) || (n && (!bytes || !out_g1 || !out_inf || !status))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return coop_rc(c, "g1_decompress", zkp_cmp::decompress(1, bytes, n, out_g1, out_inf, status, S(stream)));
+}
+int zkp_g2_decompress_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g2, void* out_inf, void* status, void* stream) {
+    if (!c || too_many(n) || (n && (!bytes || !out_g2 || !out_inf || !status))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return coop_rc(c, "g2_decompress", zkp_cmp::decompress(2, bytes, n, out_g2, out_inf, status, S(stream)));
+}
+int zkp_g1_compress_batch_dev(zkp_ctx* c, const void* g1, const void* inf, size_t n, void* out_bytes, void* stream) {
+    if (!c || too_many(n) || (n && (!g1 || !out_bytes))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return coop_rc(c, "g1_compress", zkp_cmp::compress(1, g1, inf, n, out_bytes, S(stream)));
+}
+int zkp_g2_compress_batch_dev(zkp_ctx* c, const void* g2, const void* inf, size_t n, void* out_bytes, void* stream) {
+    if (!c || too_many(n) || (n && (!g2 || !out_bytes))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return coop_rc(c, "g2_compress", zkp_cmp::compress(2, g2, inf, n, out_bytes, S(stream)));
 }
 int zkp_g1_mul_batch_dev(zkp_ctx* c, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, void* stream) {
     if (!c || too_many(n) || (n && (!base || !sc || !out)) || (stride != 0 && stride != 12)) return ZKP_ERR_ARG;
@@ -1364,8 +1402,8 @@ int zkp_g2_encode_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size
     return codec_host(c, false, 4, g2, inf, n, out, nullptr, nullptr);
 }
 
-int zkp_points_check_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1, uint8_t* st2,
-                           uint8_t* ok, int* all_ok) {
+static int points_check_host(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1, uint8_t* st2,
+                             uint8_t* ok, int* all_ok, bool compressed) {
     if (!c || too_many(n_checks, k) || (n_checks && k && (!g1_bytes || !g2_bytes))) return ZKP_ERR_ARG;
     if (all_ok) *all_ok = 1;
     if (!n_checks) return ZKP_OK;
@@ -1373,16 +1411,17 @@ int zkp_points_check_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g
     if (rc) return rc;
     HostCall drain(c);
     const size_t np = n_checks * k;
-    if ((rc = ensure_pc(c, PC_BYTES, np * 288 + 8)) || (rc = ensure_pc(c, PC_ST1, np + 8)) || (rc = ensure_pc(c, PC_ST2, np + 8)) ||
+    const size_t sz1 = compressed ? 48 : 96, sz2 = 2 * sz1;
+    if ((rc = ensure_pc(c, PC_BYTES, np * (sz1 + sz2) + 8)) || (rc = ensure_pc(c, PC_ST1, np + 8)) || (rc = ensure_pc(c, PC_ST2, np + 8)) ||
         (rc = ensure_pc(c, PC_OK, n_checks + 8)))
         return rc;
     uint8_t* d1 = (uint8_t*)c->pc[PC_BYTES];
-    uint8_t* d2 = d1 + np * 96;
+    uint8_t* d2 = d1 + np * sz1;
     if (np) {
-        HIPCHK(c, hipMemcpyAsync(d1, g1_bytes, np * 96, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d2, g2_bytes, np * 192, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d1, g1_bytes, np * sz1, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d2, g2_bytes, np * sz2, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = points_check_dev(c, d1, d2, n_checks, k, nullptr, nullptr, nullptr, c->d_flag + 1, c->stream))) return rc;
+    if ((rc = points_check_dev(c, d1, d2, n_checks, k, nullptr, nullptr, nullptr, c->d_flag + 1, c->stream, compressed))) return rc;
     if (st1 && np) HIPCHK(c, hipMemcpyAsync(st1, c->pc[PC_ST1], np, hipMemcpyDeviceToHost, c->stream));
     if (st2 && np) HIPCHK(c, hipMemcpyAsync(st2, c->pc[PC_ST2], np, hipMemcpyDeviceToHost, c->stream));
     if (ok) HIPCHK(c, hipMemcpyAsync(ok, c->pc[PC_OK], n_checks, hipMemcpyDeviceToHost, c->stream));
@@ -1392,6 +1431,76 @@ int zkp_points_check_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g
     if (all_ok) *all_ok = flag;
     return ZKP_OK;
 }
+int zkp_points_check_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1, uint8_t* st2,
+                           uint8_t* ok, int* all_ok) {
+    return points_check_host(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, all_ok, false);
+}
+int zkp_points_check_compressed_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1,
+                                      uint8_t* st2, uint8_t* ok, int* all_ok) {
+    return points_check_host(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, all_ok, true);
+}
+
+// compressed point codec, host pointers: which = 1 (48 B <-> 12 u64) or 2 (96 B <-> 24 u64)
+static int cmp_codec_host(zkp_ctx* c, bool decompress, int which, const void* in, const uint8_t* inf_in, size_t n, void* out, uint8_t* out_inf,
+                          uint8_t* status) {
+    if (!c || too_many(n) || (n && (!in || !out)) || (decompress && n && (!out_inf || !status))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    int rc = bind(c);
+    if (rc) return rc;
+    HostCall drain(c);
+    const size_t nb = n * 48 * which, nw = n * 96 * which;   // compressed bytes, wire-point bytes
+    const size_t in_sz = decompress ? nb : nw, out_sz = decompress ? nw : nb;
+    if ((rc = ensure(c, 0, in_sz)) || (rc = ensure(c, 4, out_sz)) || (rc = ensure(c, 2, n)) || (rc = ensure(c, 6, n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->buf[0], in, in_sz, hipMemcpyHostToDevice, c->stream));
+    if (decompress) {
+        if ((rc = coop_rc(c, "decompress", zkp_cmp::decompress(which, c->buf[0], n, c->buf[4], c->buf[2], c->buf[6], c->stream)))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[2], n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(status, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        const void* di = nullptr;
+        if (inf_in) {
+            HIPCHK(c, hipMemcpyAsync(c->buf[2], inf_in, n, hipMemcpyHostToDevice, c->stream));
+            di = c->buf[2];
+        }
+        if ((rc = coop_rc(c, "compress", zkp_cmp::compress(which, c->buf[0], di, n, c->buf[4], c->stream)))) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], out_sz, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+}
+int zkp_g1_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g1, uint8_t* out_inf, uint8_t* status) {
+    return cmp_codec_host(c, true, 1, bytes, nullptr, n, out_g1, out_inf, status);
+}
+int zkp_g2_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g2, uint8_t* out_inf, uint8_t* status) {
+    return cmp_codec_host(c, true, 2, bytes, nullptr, n, out_g2, out_inf, status);
+}
+int zkp_g1_compress_batch(zkp_ctx* c, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+    return cmp_codec_host(c, false, 1, g1, inf, n, out_bytes, nullptr, nullptr);
+}
+int zkp_g2_compress_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+    return cmp_codec_host(c, false, 2, g2, inf, n, out_bytes, nullptr, nullptr);
+}
+
+// square-root hooks (host pointers, like zkp_fp_op_batch): which = 1 Fp::sqrt, 2 Fp2::sqrt
+static int sqrt_host(zkp_ctx* c, int which, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) {
+    if (!c || n > 0x7fffffffu || (n && (!a || !out || !is_square))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    int rc = bind(c);
+    if (rc) return rc;
+    HostCall drain(c);
+    const size_t bytes = n * 48 * which;
+    if ((rc = ensure(c, 0, bytes)) || (rc = ensure(c, 4, bytes)) || (rc = ensure(c, 6, n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->buf[0], a, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n * which))) return rc;
+    if ((rc = coop_rc(c, "sqrt", zkp_cmp::sqrt_ref(which, (const uint64_t*)c->buf[0], n, (uint64_t*)c->buf[4], (uint8_t*)c->buf[6], c->stream))))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(is_square, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+}
+int zkp_fp_sqrt_batch(zkp_ctx* c, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) { return sqrt_host(c, 1, a, n, out, is_square); }
+int zkp_fp2_sqrt_batch(zkp_ctx* c, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) { return sqrt_host(c, 2, a, n, out, is_square); }
 
 int zkp_fp_op_batch(zkp_ctx* c, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
     const int base = op & ~ZKP_FP_CORE28;

@@ -292,27 +292,39 @@ class PairingEngine:
         """raw uncompressed points -> decode -> is_valid -> pairing check (zkp_points_check_batch[_dev]).
         numpy uint8 arrays (n x 96, n x 192): returns (st1, st2, ok, all_ok bool).  torch uint8 tensors on the engine's GPU:
         fills the given st1 / st2 / ok (uint8) and all_ok (int32[1]) tensors - each optional - asynchronously, returns None."""
+        return self._points_check(g1_bytes, g2_bytes, k, st1, st2, ok, all_ok, compressed=False)
+
+    def points_check_compressed(self, g1_bytes, g2_bytes, k, st1=None, st2=None, ok=None, all_ok=None):
+        """points_check on compressed points (n x 48, n x 96 bytes; zkp_points_check_compressed_batch[_dev]): decompression is the
+        decode step, status 3 (no square root) is "not on curve"; the same return values / tensor conventions as points_check"""
+        return self._points_check(g1_bytes, g2_bytes, k, st1, st2, ok, all_ok, compressed=True)
+
+    def _points_check(self, g1_bytes, g2_bytes, k, st1, st2, ok, all_ok, compressed):
+        sz1 = 48 if compressed else 96
+        sz2 = 2 * sz1
         if _is_torch(g1_bytes):
             import torch
             u8 = (torch.uint8,)
-            self._t_check(g1_bytes, 96, "g1_bytes", dtypes=u8), self._t_check(g2_bytes, 192, "g2_bytes", dtypes=u8)
-            n = g1_bytes.numel() // 96
-            if g2_bytes.numel() // 192 != n or k <= 0 or n % k:
+            self._t_check(g1_bytes, sz1, "g1_bytes", dtypes=u8), self._t_check(g2_bytes, sz2, "g2_bytes", dtypes=u8)
+            n = g1_bytes.numel() // sz1
+            if g2_bytes.numel() // sz2 != n or k <= 0 or n % k:
                 raise ValueError("byte strings / k do not match")
             self._t_bytes(st1, n, "st1"), self._t_bytes(st2, n, "st2"), self._t_bytes(ok, n // k, "ok")
             if all_ok is not None:
                 self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
-            self._chk(self._lib.zkp_points_check_batch_dev(self._h, self._tp(g1_bytes), self._tp(g2_bytes), n // k, k, self._tp(st1), self._tp(st2),
-                                                           self._tp(ok), self._tp(all_ok), self._stream()))
+            fn = self._lib.zkp_points_check_compressed_batch_dev if compressed else self._lib.zkp_points_check_batch_dev
+            self._chk(fn(self._h, self._tp(g1_bytes), self._tp(g2_bytes), n // k, k, self._tp(st1), self._tp(st2), self._tp(ok), self._tp(all_ok),
+                         self._stream()))
             return None
-        b1 = np.ascontiguousarray(g1_bytes, dtype=np.uint8).reshape(-1, 96)
-        b2 = np.ascontiguousarray(g2_bytes, dtype=np.uint8).reshape(-1, 192)
+        b1 = np.ascontiguousarray(g1_bytes, dtype=np.uint8).reshape(-1, sz1)
+        b2 = np.ascontiguousarray(g2_bytes, dtype=np.uint8).reshape(-1, sz2)
         n = b1.shape[0]
         if b2.shape[0] != n or k <= 0 or n % k:
             raise ValueError("byte strings / k do not match")
         s1, s2, okb = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint8), np.empty(n // k, dtype=np.uint8)
         allok = ctypes.c_int(1)
-        self._chk(self._lib.zkp_points_check_batch(self._h, _ptr(b1), _ptr(b2), n // k, k, _ptr(s1), _ptr(s2), _ptr(okb), ctypes.byref(allok)))
+        fn = self._lib.zkp_points_check_compressed_batch if compressed else self._lib.zkp_points_check_batch
+        self._chk(fn(self._h, _ptr(b1), _ptr(b2), n // k, k, _ptr(s1), _ptr(s2), _ptr(okb), ctypes.byref(allok)))
         return s1, s2, okb, bool(allok.value)
 
     def decode_points_dev(self, data, which):
@@ -337,6 +349,74 @@ class PairingEngine:
         self._t_bytes(inf, n, "inf")
         out = torch.empty((n, cols * 8), dtype=torch.uint8, device=pts.device)
         fn = self._lib.zkp_g1_encode_batch_dev if which == 1 else self._lib.zkp_g2_encode_batch_dev
+        self._chk(fn(self._h, self._tp(pts), self._tp(inf), n, self._tp(out), self._stream()))
+        return out
+
+    # ---- compressed points (48 B per G1 point, 96 B per G2 point) and the square roots behind them
+    def fp_sqrt(self, a):
+        """Fp::sqrt (reference src/fp.rs:280-300) of (n, 6) canonical elements -> (roots (n, 6), is_square (n,) uint8); the root is
+        the reference's a^((p+1)/4), zero where the reference returns Err"""
+        return self._sqrt(a, 1)
+
+    def fp2_sqrt(self, a):
+        """Fp2::sqrt (reference src/fp2.rs:231-273) of (n, 12) elements (c0 | c1) -> (roots (n, 12), is_square (n,) uint8), bit for bit
+        the reference's root, zero where it returns None"""
+        return self._sqrt(a, 2)
+
+    def _sqrt(self, a, which):
+        a = _np(a, 6 * which)
+        out, sq = np.empty_like(a), np.empty(a.shape[0], dtype=np.uint8)
+        fn = self._lib.zkp_fp_sqrt_batch if which == 1 else self._lib.zkp_fp2_sqrt_batch
+        self._chk(fn(self._h, _ptr(a), a.shape[0], _ptr(out), _ptr(sq)))
+        return out, sq
+
+    def decompress_points(self, data, which):
+        """compressed big-endian bytes -> (points, inf, status); which = 1 (G1, 48 B) or 2 (G2, 96 B).  status: 0 ok, 1 x >= p,
+        2 malformed flags, 3 no square root (not on the curve); the subgroup is not checked"""
+        size = 48 * which
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if buf.size % size:
+            raise ValueError("byte string is not a multiple of %d bytes" % size)
+        n = buf.size // size
+        pts = np.empty((n, 12 * which), dtype=np.uint64)
+        inf, st = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint8)
+        fn = self._lib.zkp_g1_decompress_batch if which == 1 else self._lib.zkp_g2_decompress_batch
+        self._chk(fn(self._h, _ptr(buf), n, _ptr(pts), _ptr(inf), _ptr(st)))
+        return pts, inf, st
+
+    def compress_points(self, pts, which, inf=None):
+        """(n, 12 | 24) points -> compressed bytes (48 | 96 per point: x, the compression flag and the sort flag of y)"""
+        cols = 12 * which
+        pts = _np(pts, cols)
+        n = pts.shape[0]
+        i = _flags(inf, n, "inf")
+        out = np.empty(n * 48 * which, dtype=np.uint8)
+        fn = self._lib.zkp_g1_compress_batch if which == 1 else self._lib.zkp_g2_compress_batch
+        self._chk(fn(self._h, _ptr(pts), _ptr(i), n, _ptr(out)))
+        return out.tobytes()
+
+    def decompress_points_dev(self, data, which):
+        """uint8 tensor of compressed points on the engine's GPU -> (points int64 (n, 12 | 24), inf uint8, status uint8) tensors"""
+        import torch
+        size = 48 * which
+        self._t_check(data, size, "bytes", dtypes=(torch.uint8,))
+        n = data.numel() // size
+        pts = torch.empty((n, 12 * which), dtype=torch.int64, device=data.device)
+        inf = torch.empty(n, dtype=torch.uint8, device=data.device)
+        st = torch.empty(n, dtype=torch.uint8, device=data.device)
+        fn = self._lib.zkp_g1_decompress_batch_dev if which == 1 else self._lib.zkp_g2_decompress_batch_dev
+        self._chk(fn(self._h, self._tp(data), n, self._tp(pts), self._tp(inf), self._tp(st), self._stream()))
+        return pts, inf, st
+
+    def compress_points_dev(self, pts, which, inf=None):
+        """(n, 12 | 24) point tensor on the engine's GPU -> (n, 48 | 96) uint8 tensor of compressed points"""
+        import torch
+        cols = 12 * which
+        self._t_check(pts, cols, "points")
+        n = pts.numel() // cols
+        self._t_bytes(inf, n, "inf")
+        out = torch.empty((n, 48 * which), dtype=torch.uint8, device=pts.device)
+        fn = self._lib.zkp_g1_compress_batch_dev if which == 1 else self._lib.zkp_g2_compress_batch_dev
         self._chk(fn(self._h, self._tp(pts), self._tp(inf), n, self._tp(out), self._stream()))
         return out
 

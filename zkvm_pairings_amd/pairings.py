@@ -54,6 +54,20 @@ class G1Affine:
     def is_identity(self):
         return self.is_infinity
 
+    def to_compressed(self, engine=None):
+        """48 bytes: x big-endian with the compression flag, the sort flag of y (y > (p-1)/2), or 0xc0 and zeros for the identity"""
+        return (engine or default_engine()).compress_points(self.to_array(), 1, [1 if self.is_infinity else 0])
+
+    @classmethod
+    def from_compressed(cls, data, engine=None):
+        """48 compressed bytes -> G1Affine on the curve (the subgroup is not checked: is_valid does that); ValueError otherwise"""
+        if len(data) != 48:
+            raise ValueError("a compressed G1 point has 48 bytes")
+        pts, inf, st = (engine or default_engine()).decompress_points(bytes(data), 1)
+        if st[0]:
+            raise ValueError("not a compressed G1 point: %s" % PairingEngine.POINT_STATUS[int(st[0])])
+        return cls.from_array(pts[0], bool(inf[0]))
+
     def is_valid(self, engine=None):
         """Ok(()) / Err(String) of src/g1.rs:49-62 as None / message."""
         st = (engine or default_engine()).g1_is_valid(self.to_array(), [1 if self.is_infinity else 0])[0]
@@ -94,6 +108,20 @@ class G2Affine:
 
     def is_identity(self):
         return self.is_infinity
+
+    def to_compressed(self, engine=None):
+        """96 bytes: x.c1 | x.c0 big-endian with the compression flag and the sort flag of y (c1 decides, c0 when c1 == 0)"""
+        return (engine or default_engine()).compress_points(self.to_array(), 2, [1 if self.is_infinity else 0])
+
+    @classmethod
+    def from_compressed(cls, data, engine=None):
+        """96 compressed bytes -> G2Affine on the curve (the subgroup is not checked: is_valid does that); ValueError otherwise"""
+        if len(data) != 96:
+            raise ValueError("a compressed G2 point has 96 bytes")
+        pts, inf, st = (engine or default_engine()).decompress_points(bytes(data), 2)
+        if st[0]:
+            raise ValueError("not a compressed G2 point: %s" % PairingEngine.POINT_STATUS[int(st[0])])
+        return cls.from_array(pts[0], bool(inf[0]))
 
     def is_valid(self, engine=None):
         st = (engine or default_engine()).g2_is_valid(self.to_array(), [1 if self.is_infinity else 0])[0]
