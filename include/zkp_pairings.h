@@ -15,6 +15,8 @@
  *   zkp_g2_is_valid_batch           G2Affine::is_valid                       src/g2.rs:57-69  (:109-120, :166-170)
  *   zkp_g1_mul_batch / g2           &G1Affine * &Fr / &G2Affine * &Fr         src/g1.rs:130-153 (bit-0 bug F5 NOT
  *                                                                            mirrored), src/g2.rs:185-208
+ *   zkp_g1_add_batch / g2           G1Affine + G1Affine / G2Affine + G2Affine src/g1.rs:155-187, src/g2.rs:210-242 (P + (-P): F7)
+ *   zkp_g1_msm_batch / g2           sum_i [k_i] P_i (no upstream counterpart: Add and Mul composed)
  *   zkp_fp_op_batch                 bls12381_sys_bigint(out, op, a, b)       src/fp.rs:376,443 (op 0 = mul, 1 = add); also
  *                                   Fp::sub / neg / square / invert          src/fp.rs:307-319, 383-411, 453-455
  *   zkp_tower_op_batch              Fp2 / Fp6 / Fp12 mul, square, mul_by_014, src/fp2.rs:171-209, src/fp6.rs:188-288,
@@ -163,6 +165,26 @@ int zkp_g1_mul_batch(zkp_ctx* ctx, const uint64_t* base, size_t base_stride, con
                      uint64_t* out, uint8_t* out_inf);
 int zkp_g2_mul_batch(zkp_ctx* ctx, const uint64_t* base, size_t base_stride, const uint64_t* scalars, size_t n,
                      uint64_t* out, uint8_t* out_inf);
+/* ---- group addition and multi-scalar multiplication (on the 14 x 28-bit core whatever zkp_set_kernel says) --------------------------
+ * out[i] = a[i] + b[i] (G1Affine / G2Affine Add, src/g1.rs:155-187, src/g2.rs:210-242); inf_a / inf_b / out_inf may be NULL (no infinities /
+ * not wanted).  An infinite result is written as (0, 1) with out_inf = 1, as zkp_g*_mul_batch does.  Finite results equal the reference's
+ * bit for bit.  F7 divergence: P + (-P) gives the identity; the reference's affine Add panics there (it inverts x_Q - x_P = 0).
+ * MSM: n_msm independent sums out[j] = sum_{i<m} [k_{j,i}] P_{j,i}.  Scalars are full 256-bit integers, 4 u64 each, row j of m scalars
+ * per sum (same contract as zkp_g1_mul_batch: no reduction mod r, no dropped bit 0).  shared_bases != 0: every sum uses the same m points
+ * (points / inf hold m entries), else m * n_msm.  m * n_msm <= 2^24 and m >= 1 (when n_msm > 0), else ZKP_ERR_ARG.  Bucket method: c-bit
+ * signed windows (c from 2 to 16, chosen from m), a radix sort of the digits, load-balanced bucket sums, one inversion per sum.
+ * Workspace (grow-only, owned by the context, layout zkvm_pairings_amd/csrc/zkp_msm_plan.hpp): per pass 16 B per digit key
+ * (W = 256/c + 1 keys per term), the converted points (128 B per G1 / 256 B per G2 point), W (192 B G1 / 384 B G2) / 16 B of partial sums per
+ * term, and W 2^(c-1) buckets of 192 / 384 B per sum.  For example about 1.0 KB per term for a G1 MSM of 2^20 terms (c = 16),
+ * 1.6 KB for G2. */
+int zkp_g1_add_batch(zkp_ctx* ctx, const uint64_t* a, const uint8_t* inf_a, const uint64_t* b, const uint8_t* inf_b, size_t n, uint64_t* out,
+                     uint8_t* out_inf);
+int zkp_g2_add_batch(zkp_ctx* ctx, const uint64_t* a, const uint8_t* inf_a, const uint64_t* b, const uint8_t* inf_b, size_t n, uint64_t* out,
+                     uint8_t* out_inf);
+int zkp_g1_msm_batch(zkp_ctx* ctx, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases,
+                     uint64_t* out, uint8_t* out_inf);
+int zkp_g2_msm_batch(zkp_ctx* ctx, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases,
+                     uint64_t* out, uint8_t* out_inf);
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).
  * G1: x(48) | y(48) = 96 bytes; G2: x.c1 | x.c0 | y.c1 | y.c0 = 192 bytes (c1 first, the usual BLS12-381
@@ -216,6 +238,21 @@ int zkp_g1_mul_batch_dev(zkp_ctx* ctx, const void* d_base, size_t base_stride, c
                          void* d_out, void* d_out_inf, void* stream);
 int zkp_g2_mul_batch_dev(zkp_ctx* ctx, const void* d_base, size_t base_stride, const void* d_scalars, size_t n,
                          void* d_out, void* d_out_inf, void* stream);
+
+/* addition and MSM on resident buffers (same formats and limits as zkp_g*_add_batch / zkp_g*_msm_batch above).  Capturable into a hipGraph
+ * once the context's MSM workspace has reached the call's size. */
+int zkp_g1_add_batch_dev(zkp_ctx* ctx, const void* d_a, const void* d_inf_a, const void* d_b, const void* d_inf_b, size_t n, void* d_out,
+                         void* d_out_inf, void* stream);
+int zkp_g2_add_batch_dev(zkp_ctx* ctx, const void* d_a, const void* d_inf_a, const void* d_b, const void* d_inf_b, size_t n, void* d_out,
+                         void* d_out_inf, void* stream);
+int zkp_g1_msm_batch_dev(zkp_ctx* ctx, const void* d_points, const void* d_inf, const void* d_scalars, size_t m, size_t n_msm, int shared_bases,
+                         void* d_out, void* d_out_inf, void* stream);
+int zkp_g2_msm_batch_dev(zkp_ctx* ctx, const void* d_points, const void* d_inf, const void* d_scalars, size_t m, size_t n_msm, int shared_bases,
+                         void* d_out, void* d_out_inf, void* stream);
+/* measurement: zkp_g*_msm_batch_dev (which = 1 / 2) that synchronises and reports the milliseconds of its six phases, summed over its passes:
+ * phase_ms[0] point conversion, [1] digits, [2] sort, [3] bucket sums, [4] bucket reduction, [5] window combination + affine output */
+int zkp_msm_profile_dev(zkp_ctx* ctx, int which, const void* d_points, const void* d_inf, const void* d_scalars, size_t m, size_t n_msm,
+                        int shared_bases, void* d_out, void* d_out_inf, void* stream, float* phase_ms);
 
 /* the uncompressed point codec on resident buffers (same formats and status bytes as zkp_g1/g2_decode_batch above) */
 int zkp_g1_decode_batch_dev(zkp_ctx* ctx, const void* d_bytes, size_t n, void* d_out_g1, void* d_out_inf, void* d_status, void* stream);

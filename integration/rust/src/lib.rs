@@ -128,6 +128,26 @@ extern "C" {
     // compressed points (48 B per G1 point, 96 B per G2 point) and the square roots of Fp / Fp2 (src/fp.rs:280-300, src/fp2.rs:231-273)
     pub fn zkp_fp_sqrt_batch(ctx: *mut ZkpCtx, a: *const u64, n: usize, out: *mut u64, is_square: *mut u8) -> c_int;
     pub fn zkp_fp2_sqrt_batch(ctx: *mut ZkpCtx, a: *const u64, n: usize, out: *mut u64, is_square: *mut u8) -> c_int;
+    // group addition and multi-scalar multiplication (28-bit core)
+    pub fn zkp_g1_add_batch(ctx: *mut ZkpCtx, a: *const u64, inf_a: *const u8, b: *const u64, inf_b: *const u8, n: usize, out: *mut u64,
+                            out_inf: *mut u8) -> c_int;
+    pub fn zkp_g2_add_batch(ctx: *mut ZkpCtx, a: *const u64, inf_a: *const u8, b: *const u64, inf_b: *const u8, n: usize, out: *mut u64,
+                            out_inf: *mut u8) -> c_int;
+    pub fn zkp_g1_msm_batch(ctx: *mut ZkpCtx, points: *const u64, inf: *const u8, scalars: *const u64, m: usize, n_msm: usize, shared_bases: c_int,
+                            out: *mut u64, out_inf: *mut u8) -> c_int;
+    pub fn zkp_g2_msm_batch(ctx: *mut ZkpCtx, points: *const u64, inf: *const u8, scalars: *const u64, m: usize, n_msm: usize, shared_bases: c_int,
+                            out: *mut u64, out_inf: *mut u8) -> c_int;
+    pub fn zkp_g1_add_batch_dev(ctx: *mut ZkpCtx, d_a: *const c_void, d_inf_a: *const c_void, d_b: *const c_void, d_inf_b: *const c_void, n: usize,
+                                d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_g2_add_batch_dev(ctx: *mut ZkpCtx, d_a: *const c_void, d_inf_a: *const c_void, d_b: *const c_void, d_inf_b: *const c_void, n: usize,
+                                d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_g1_msm_batch_dev(ctx: *mut ZkpCtx, d_points: *const c_void, d_inf: *const c_void, d_scalars: *const c_void, m: usize, n_msm: usize,
+                                shared_bases: c_int, d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_g2_msm_batch_dev(ctx: *mut ZkpCtx, d_points: *const c_void, d_inf: *const c_void, d_scalars: *const c_void, m: usize, n_msm: usize,
+                                shared_bases: c_int, d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_msm_profile_dev(ctx: *mut ZkpCtx, which: c_int, d_points: *const c_void, d_inf: *const c_void, d_scalars: *const c_void, m: usize,
+                               n_msm: usize, shared_bases: c_int, d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void,
+                               phase_ms: *mut f32) -> c_int;
     pub fn zkp_g1_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g1: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g2_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g2: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g1_compress_batch(ctx: *mut ZkpCtx, g1: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;

@@ -63,6 +63,15 @@ SIGNATURES = {
     "zkp_points_check_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "zkp_fp_sqrt_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
     "zkp_fp2_sqrt_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_add_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g2_add_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_msm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp]),
+    "zkp_g2_msm_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp]),
+    "zkp_g1_add_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g2_add_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g1_msm_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
+    "zkp_g2_msm_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
+    "zkp_msm_profile_dev": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_float)]),
     "zkp_g1_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g2_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g1_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -29,6 +29,7 @@
 // SURVEY.md S6 (src/pairings.rs is empty upstream).
 #include "zkp_coop.hpp"
 #include "zkp_plan.hpp"
+#include "zkp_msm_plan.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -2281,6 +2282,342 @@ __global__ void k_fp28_op(int op, const uint64_t* a, const uint64_t* b, size_t n
     fp28_to_wire(out + 6 * i, r);
 }
 
+// =============================================================================== group addition and bucket MSM on the 28-bit core
+// G1Affine / G2Affine Add (reference src/g1.rs:155-187, src/g2.rs:210-242) in batches, and multi-scalar multiplication by the
+// bucket method (zkp_msm.hip drives it; zkp_msm_plan.hpp sizes it).  Same policies as the scalar multiplication: one lane per G1
+// value, a lane pair per G2 value (lane c holds coefficient c).  Jacobian values in memory are records of 64 bytes per Fp
+// (rec_store), item j of a Jacobian array holds its Fp (coordinate v, coefficient c) at record (3 j + v) NC + c.
+namespace msm = zkp::msm;
+template <int NC> struct Pol;
+template <> struct Pol<1> { using F = F1; };
+template <> struct Pol<2> { using F = F2; };
+
+// p += q, both Jacobian (add-2007-bl with Z3 = 2 Z1 Z2 H), with every exceptional case: either input at infinity, P == Q (doubled),
+// P == -Q (infinity).  q comes through a loader (0: X, 1: Y, 2: Z) so that it costs no registers across the products; at most six
+// values stay live across a by-value call (jac_dbl explains why that matters).
+template <class F, class Q>
+__device__ __forceinline__ void jac_add(const F& f, JacP& p, Q&& ldq) {
+    if (f.is_zero(p.z)) { p.x = ldq(0); p.y = ldq(1); p.z = ldq(2); return; }
+    if (f.is_zero(ldq(2))) return;
+    Fp28 Z2 = ldq(2);
+    Fp28 Z2Z2 = f.sqr(Z2);
+    Fp28 U1 = f.mul(p.x, Z2Z2);
+    Fp28 S1 = f.mul(p.y, f.mul(Z2, Z2Z2));
+    Fp28 ZZ = f.mul(p.z, Z2);
+    Fp28 Z1Z1 = f.sqr(p.z);
+    Fp28 H = c_sub(f.mul(ldq(0), Z1Z1), U1);
+    Fp28 rr = c_sub(f.mul(ldq(1), f.mul(p.z, Z1Z1)), S1);
+    if (f.is_zero(H)) {
+        if (f.is_zero(rr)) { p.x = ldq(0); p.y = ldq(1); p.z = ldq(2); jac_dbl(f, p); return; }
+        f_zero(p.z);   // P + (-P)
+        return;
+    }
+    rr = c_dbl(rr);
+    Fp28 I = f.sqr(c_dbl(H));
+    Fp28 Z3 = f.mul(c_dbl(ZZ), H);
+    Fp28 J = f.mul(H, I);
+    Fp28 V = f.mul(U1, I);
+    Fp28 X3 = c_sub(c_sub(c_sub(f.sqr(rr), J), V), V);
+    Fp28 Y3 = c_sub(f.mul(rr, c_sub(V, X3)), c_dbl(f.mul(S1, J)));
+    p.x = f_vred(X3); p.y = f_vred(Y3); p.z = f_vred(Z3);
+}
+
+__device__ __forceinline__ void jac_set_inf(const F1& f, JacP& p) { p.x = f.one(); p.y = f.one(); f_zero(p.z); }
+__device__ __forceinline__ void jac_set_inf(const F2& f, JacP& p) { p.x = f.one(); p.y = f.one(); f_zero(p.z); }
+
+template <int NC>
+__device__ __forceinline__ Fp28 jrec_ld(const int4* j, uint32_t item, int v, int c) {
+    Fp28 x;
+    rec_load(x, j + ((size_t)item * 3 * NC + (size_t)(v * NC + c)) * 4);
+    return x;
+}
+template <int NC>
+__device__ __forceinline__ void jrec_st(int4* j, uint32_t item, int c, const JacP& p) {
+    int4* d = j + (size_t)item * 3 * NC * 4;
+    rec_store(d + (0 * NC + c) * 4, p.x);
+    rec_store(d + (1 * NC + c) * 4, p.y);
+    rec_store(d + (2 * NC + c) * 4, p.z);
+}
+// a Jacobian value parked in LDS, slots v0 .. v0 + 2 (layout of valid_park)
+__device__ __forceinline__ void jac_park(int4* park, int lane, int v0, const JacP& p) {
+    valid_park(park, lane, v0, p.x);
+    valid_park(park, lane, v0 + 1, p.y);
+    valid_park(park, lane, v0 + 2, p.z);
+}
+__device__ __forceinline__ JacP jac_unpark(const int4* park, int lane, int v0) {
+    JacP p;
+    p.x = valid_unpark(park, lane, v0);
+    p.y = valid_unpark(park, lane, v0 + 1);
+    p.z = valid_unpark(park, lane, v0 + 2);
+    return p;
+}
+
+// Jacobian item of an array -> LDS slots 0..2: what jac_add reads through valid_unpark (a loader from global memory lets the compiler
+// keep the loaded values in registers across the products, and the addition spills)
+template <int NC>
+__device__ __forceinline__ void jrec_park(int4* park, int lane, const int4* j, uint32_t item, int c) {
+    valid_park(park, lane, 0, jrec_ld<NC>(j, item, 0, c));
+    valid_park(park, lane, 1, jrec_ld<NC>(j, item, 1, c));
+    valid_park(park, lane, 2, jrec_ld<NC>(j, item, 2, c));
+}
+
+// Jacobian -> affine Montgomery (one inversion; the identity becomes (0, 1), reference src/g1.rs:25-31, src/g2.rs:25-31)
+__device__ __forceinline__ bool jac_affine(const F1& f, const JacP& p, Fp28& ax, Fp28& ay) {
+    const bool inf = f.is_zero(p.z);
+    Fp28 zi = f_inv(p.z);
+    Fp28 zi2 = f.sqr(zi);
+    ax = f.mul(p.x, zi2);
+    ay = f.mul(p.y, f.mul(zi2, zi));
+    if (inf) { f_zero(ax); ay = f.one(); }
+    return inf;
+}
+__device__ __forceinline__ bool jac_affine(const F2& f, const JacP& p, Fp28& ax, Fp28& ay) {
+    const bool inf = f.is_zero(p.z);
+    // 1 / (z0 + z1 u) = (z0 - z1 u) / (z0^2 + z1^2)   (reference src/fp2.rs:278-296); both lanes invert the norm
+    Fp28 o;
+    swap_pair(o, p.z);
+    Acc acc;
+    acc_zero(acc);
+    acc_mul(acc, p.z.l, p.z.l);
+    acc_mul(acc, o.l, o.l);
+    Fp28 nrm;
+    acc_reduce(nrm.l, acc);
+    Fp28 ninv = f_inv(nrm);
+    Fp28 zi = f_mul_v(f.c ? c_neg(p.z) : p.z, ninv);
+    Fp28 zi2 = f.sqr(zi);
+    ax = f.mul(p.x, zi2);
+    ay = f.mul(p.y, f.mul(zi2, zi));
+    if (inf) { f_zero(ax); ay = f.one(); }
+    return inf;
+}
+
+// out[i] = a[i] + b[i], affine in / affine out.  inf_a / inf_b / out_inf may be null.
+template <int NC>
+__global__ void __launch_bounds__(64, 2) k_add28(const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, uint32_t n,
+                                                 uint64_t* out, uint8_t* out_inf) {
+    const uint32_t tid = blockIdx.x * 64 + threadIdx.x;
+    const int c = NC == 2 ? (int)(tid & 1) : 0;
+    uint32_t i = tid / NC;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    typename Pol<NC>::F f{c};
+    constexpr int PW = 12 * NC;
+    const int lane = threadIdx.x;
+    __shared__ int4 park[2 * 4 * 64];
+    JacP p;
+    fp28_from_wire(p.x, a + PW * (size_t)i + 6 * c);
+    fp28_from_wire(p.y, a + PW * (size_t)i + 6 * NC + 6 * c);
+    p.z = f.one();
+    if (ia && ia[i]) f_zero(p.z);
+    if (!(ib && ib[i])) {
+        Fp28 qx, qy;
+        fp28_from_wire(qx, b + PW * (size_t)i + 6 * c);
+        fp28_from_wire(qy, b + PW * (size_t)i + 6 * NC + 6 * c);
+        valid_park(park, lane, 0, qx);
+        valid_park(park, lane, 1, qy);
+        jac_madd(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    }
+    Fp28 ax, ay;
+    const bool inf = jac_affine(f, p, ax, ay);
+    if (live) {
+        fp28_to_wire(out + PW * (size_t)i + 6 * c, ax);
+        fp28_to_wire(out + PW * (size_t)i + 6 * NC + 6 * c, ay);
+        if (out_inf && c == 0) out_inf[i] = inf ? 1 : 0;
+    }
+}
+
+// ---- MSM 1: n wire Fp elements -> Montgomery records (the points' coordinates, converted once per pass)
+__global__ void __launch_bounds__(256) k_msm_points(const uint64_t* w, uint32_t n_fp, int4* rec) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_fp) return;
+    Fp28 x;
+    fp28_from_wire(x, w + 6 * (size_t)i);
+    rec_store(rec + 4 * (size_t)i, x);
+}
+
+// ---- MSM 2: signed c-bit digits of every term's scalar, one sort key and one value per (term, window).  Digit d of window w is
+// bits [w c, w c + c) plus the carry of window w - 1, moved to d - 2^c (carry 1) when above 2^(c-1): k = sum_w d_w 2^(c w) exactly,
+// |d| <= 2^(c-1), and the top window (fewer than c bits of the scalar) never carries out.  key: bucket (s W + w) 2^(c-1) + |d| - 1, or
+// KEY_NONE for d = 0 and for points at infinity; value: the point's index in the pass's records, bit 31 the digit's sign.
+__global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* sc, const uint8_t* inf, uint32_t terms, uint32_t m, int shared, uint32_t c,
+                                                    uint32_t windows, uint32_t* keys, uint32_t* vals) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= terms) return;
+    const uint32_t seg = t / m, pt = shared ? t - seg * m : t;
+    const bool dead = inf && inf[pt];
+    const uint64_t k[4] = {sc[4 * (size_t)t], sc[4 * (size_t)t + 1], sc[4 * (size_t)t + 2], sc[4 * (size_t)t + 3]};
+    const int32_t half = 1 << (c - 1);
+    int32_t carry = 0;
+#pragma unroll 1
+    for (uint32_t w = 0; w < windows; w++) {
+        const uint32_t pos = w * c, wd = pos >> 6, sh = pos & 63;
+        uint64_t v = wd < 4 ? k[wd] >> sh : 0;
+        if (sh + c > 64 && wd + 1 < 4) v |= k[wd + 1] << (64 - sh);
+        int32_t d = (int32_t)(v & ((1u << c) - 1)) + carry;
+        carry = d > half ? 1 : 0;
+        if (carry) d -= 2 * half;
+        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+        const size_t o = (size_t)w * terms + t;
+        keys[o] = (d == 0 || dead) ? msm::KEY_NONE : ((seg * windows + w) << (c - 1)) + mag - 1;
+        vals[o] = pt | (d < 0 ? 0x80000000u : 0u);
+    }
+}
+
+// ---- MSM 3: segmented sum of sorted entries, RUN entries per lane (G1) / lane pair (G2) whatever the bucket sizes.  A key group that
+// starts and ends inside the run is complete: its sum goes to sums[key] (at level 0 always; later only when the group holds a real
+// partial, KEY_FLAG).  The run's first group when it began in an earlier run, and its last when it goes on in a later one, leave
+// partial sums in the run's two output slots instead (an unused slot: infinity under a neighbouring key, no flag, so the output stays
+// sorted).  The next level sums those; the last level has one run.  L0: the entries are (key, signed point index) and the sum is of
+// mixed additions; otherwise Jacobian partial sums (jac_add).
+template <int NC, bool L0>
+__global__ void __launch_bounds__(64, 2) k_msm_accum(const uint32_t* keys, const uint32_t* vals, const int4* src, uint32_t n, uint32_t n_sums,
+                                                     int4* sums, uint32_t* okeys, int4* oj) {
+    const uint32_t tid = blockIdx.x * 64 + threadIdx.x;
+    const int c = NC == 2 ? (int)(tid & 1) : 0;
+    const uint32_t runs = (n + msm::RUN - 1) / msm::RUN;
+    uint32_t t = tid / NC;
+    const bool live = t < runs;
+    if (!live) t = runs - 1;
+    const uint32_t lo = t * msm::RUN, hi = n - lo < msm::RUN ? n : lo + msm::RUN;
+    constexpr uint32_t KM = ~msm::KEY_FLAG;
+    const uint32_t prev = lo ? keys[lo - 1] & KM : 0xffffffffu, next = hi < n ? keys[hi] & KM : 0xffffffffu;
+    typename Pol<NC>::F f{c};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[3 * 4 * 64];
+    JacP acc;
+    jac_set_inf(f, acc);
+    uint32_t cur = keys[lo] & KM, s0k = 0, s1k = 0;
+    bool any = L0, first = true, s0 = false, s1 = false;
+    auto emit = [&](bool ends) {
+        if (cur >= n_sums) return;
+        const bool starts = !(first && prev == cur);
+        const uint32_t kw = cur | (any ? msm::KEY_FLAG : 0u);
+        if (starts && ends) {
+            if (any && live) jrec_st<NC>(sums, cur, c, acc);
+        } else if (!starts) {
+            s0 = true; s0k = kw;
+            if (live) jrec_st<NC>(oj, 2 * t, c, acc);
+        } else {
+            s1 = true; s1k = kw;
+            if (live) jrec_st<NC>(oj, 2 * t + 1, c, acc);
+        }
+    };
+#pragma unroll 1
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t kw = keys[i], k = kw & KM;
+        if (k != cur) {
+            emit(true);
+            first = false;
+            cur = k;
+            jac_set_inf(f, acc);
+            any = L0;
+        }
+        if (k >= n_sums) break;   // dropped digits sort last: nothing behind them
+        if (L0) {
+            const uint32_t v = vals[i], idx = v & 0x7fffffffu;
+            Fp28 qx, qy;
+            rec_load(qx, src + ((size_t)idx * 2 * NC + c) * 4);
+            rec_load(qy, src + ((size_t)idx * 2 * NC + NC + c) * 4);
+            if (v >> 31) qy = c_neg(qy);
+            valid_park(park, lane, 0, qx);
+            valid_park(park, lane, 1, qy);
+            jac_madd(f, acc, [&](int w) -> Fp28 { return valid_unpark(park, lane, w); });
+        } else {
+            any = any || (kw & msm::KEY_FLAG);
+            jrec_park<NC>(park, lane, src, i, c);
+            jac_add(f, acc, [&](int w) -> Fp28 { return valid_unpark(park, lane, w); });
+        }
+    }
+    emit(next != cur);
+    if (!live) return;
+    JacP z;
+    jac_set_inf(f, z);
+    if (!s0) jrec_st<NC>(oj, 2 * t, c, z);
+    if (!s1) jrec_st<NC>(oj, 2 * t + 1, c, z);
+    if (c == 0) {
+        okeys[2 * t] = s0 ? s0k : (s1 ? s1k & KM : cur);
+        okeys[2 * t + 1] = s1 ? s1k : (s0 ? s0k & KM : cur);
+    }
+}
+
+// ---- MSM 4: bucket reduction, sum_j (j + 1) B_j of one window split over `split` lanes (pairs): lane s takes buckets [s L, s L + L),
+// L = chunk, with two running sums (run = sum_{j' >= j} B_j', acc = sum of the runs = sum (j - s L + 1) B_j) and adds (s L) run.  Both
+// sums are parked in LDS between the additions.  Output: one flagged partial per lane under key window, for the fix-up levels.
+template <int NC>
+__global__ void __launch_bounds__(64, 2) k_msm_reduce(const int4* buckets, uint32_t n_sums, uint32_t split, uint32_t chunk, uint32_t* okeys,
+                                                      int4* oj) {
+    const uint32_t tid = blockIdx.x * 64 + threadIdx.x;
+    const int c = NC == 2 ? (int)(tid & 1) : 0;
+    uint32_t u = tid / NC;
+    const bool live = u < n_sums * split;
+    if (!live) u = n_sums * split - 1;
+    const uint32_t win = u / split, s = u - win * split, base = win * split * chunk + s * chunk;
+    typename Pol<NC>::F f{c};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[6 * 4 * 64];
+    JacP p;
+    jac_set_inf(f, p);
+    jac_park(park, lane, 0, p);   // run
+    jac_park(park, lane, 3, p);   // acc
+#pragma unroll 1
+    for (uint32_t j = chunk; j-- > 0;) {
+        p = jac_unpark(park, lane, 0);
+        jac_add(f, p, [&](int v) -> Fp28 { return jrec_ld<NC>(buckets, base + j, v, c); });
+        jac_park(park, lane, 0, p);
+        p = jac_unpark(park, lane, 3);
+        jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+        jac_park(park, lane, 3, p);
+    }
+    const uint32_t e = s * chunk;
+    if (e) {
+        p = jac_unpark(park, lane, 0);
+        const int top = 31 - __builtin_clz(e);
+#pragma unroll 1
+        for (int b = top - 1; b >= 0; b--) {
+            jac_dbl(f, p);
+            if ((e >> b) & 1) jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+        }
+        jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, 3 + v); });
+    } else {
+        p = jac_unpark(park, lane, 3);
+    }
+    if (!live) return;
+    jrec_st<NC>(oj, u, c, p);
+    if (c == 0) okeys[u] = win | msm::KEY_FLAG;
+}
+
+// ---- MSM 5: per segment, sum_w 2^(c w) S_w by Horner (c doublings per window), then one inversion to affine wire output
+template <int NC>
+__global__ void __launch_bounds__(64, 2) k_msm_final(const int4* wsums, uint32_t segs, uint32_t windows, uint32_t c_bits, uint64_t* out,
+                                                     uint8_t* out_inf) {
+    const uint32_t tid = blockIdx.x * 64 + threadIdx.x;
+    const int c = NC == 2 ? (int)(tid & 1) : 0;
+    uint32_t sg = tid / NC;
+    const bool live = sg < segs;
+    if (!live) sg = segs - 1;
+    typename Pol<NC>::F f{c};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[3 * 4 * 64];
+    JacP p;
+    jac_set_inf(f, p);
+#pragma unroll 1
+    for (uint32_t w = windows; w-- > 0;) {
+        if (w + 1 < windows)
+#pragma unroll 1
+            for (uint32_t b = 0; b < c_bits; b++) jac_dbl(f, p);
+        jrec_park<NC>(park, lane, wsums, sg * windows + w, c);
+        jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    }
+    Fp28 ax, ay;
+    const bool inf = jac_affine(f, p, ax, ay);
+    constexpr int PW = 12 * NC;
+    if (live) {
+        fp28_to_wire(out + PW * (size_t)sg + 6 * c, ax);
+        fp28_to_wire(out + PW * (size_t)sg + 6 * NC + 6 * c, ay);
+        if (out_inf && c == 0) out_inf[sg] = inf ? 1 : 0;
+    }
+}
+
 // the primer of prime(): a grid of one-wavefront workgroups that leave at once
 __global__ void __launch_bounds__(64) k_primer() {}
 
@@ -3051,6 +3388,57 @@ hipError_t coop_g1_mul(const uint64_t* base, size_t stride, const uint64_t* sc, 
 hipError_t coop_g2_mul(const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_g2_mul28, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, s, base, stride, sc, (uint32_t)n, out, out_inf);
+    return hipGetLastError();
+}
+
+hipError_t coop_add(int which, const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, size_t n, uint64_t* out, uint8_t* out_inf,
+                    hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (which == 1)
+        hipLaunchKernelGGL(k_add28<1>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a, ia, b, ib, (uint32_t)n, out, out_inf);
+    else
+        hipLaunchKernelGGL(k_add28<2>, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, s, a, ia, b, ib, (uint32_t)n, out, out_inf);
+    return hipGetLastError();
+}
+hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s) {
+    if (!n_fp) return hipSuccess;
+    hipLaunchKernelGGL(k_msm_points, dim3((n_fp + 255) / 256), dim3(256), 0, s, w, n_fp, (int4*)rec);
+    return hipGetLastError();
+}
+hipError_t msm_digits(const uint64_t* sc, const uint8_t* inf, uint32_t terms, uint32_t m, int shared, uint32_t c, uint32_t windows, uint32_t* keys,
+                      uint32_t* vals, hipStream_t s) {
+    if (!terms) return hipSuccess;
+    hipLaunchKernelGGL(k_msm_digits, dim3((terms + 255) / 256), dim3(256), 0, s, sc, inf, terms, m, shared, c, windows, keys, vals);
+    return hipGetLastError();
+}
+hipError_t msm_accum(int which, bool level0, const uint32_t* keys, const uint32_t* vals, const void* src, uint32_t n, uint32_t n_sums, void* sums,
+                     uint32_t* okeys, void* oj, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const uint32_t lanes = (n + msm::RUN - 1) / msm::RUN * (uint32_t)which;
+    const dim3 g((lanes + 63) / 64), b(64);
+    const int4* r = (const int4*)src;
+    if (which == 1 && level0) hipLaunchKernelGGL((k_msm_accum<1, true>), g, b, 0, s, keys, vals, r, n, n_sums, (int4*)sums, okeys, (int4*)oj);
+    if (which == 1 && !level0) hipLaunchKernelGGL((k_msm_accum<1, false>), g, b, 0, s, keys, vals, r, n, n_sums, (int4*)sums, okeys, (int4*)oj);
+    if (which == 2 && level0) hipLaunchKernelGGL((k_msm_accum<2, true>), g, b, 0, s, keys, vals, r, n, n_sums, (int4*)sums, okeys, (int4*)oj);
+    if (which == 2 && !level0) hipLaunchKernelGGL((k_msm_accum<2, false>), g, b, 0, s, keys, vals, r, n, n_sums, (int4*)sums, okeys, (int4*)oj);
+    return hipGetLastError();
+}
+hipError_t msm_reduce(int which, const void* buckets, uint32_t n_sums, uint32_t split, uint32_t chunk, uint32_t* okeys, void* oj, hipStream_t s) {
+    const uint32_t lanes = n_sums * split * (uint32_t)which;
+    if (!lanes) return hipSuccess;
+    if (which == 1)
+        hipLaunchKernelGGL(k_msm_reduce<1>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const int4*)buckets, n_sums, split, chunk, okeys, (int4*)oj);
+    else
+        hipLaunchKernelGGL(k_msm_reduce<2>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const int4*)buckets, n_sums, split, chunk, okeys, (int4*)oj);
+    return hipGetLastError();
+}
+hipError_t msm_final(int which, const void* wsums, uint32_t segs, uint32_t windows, uint32_t c, uint64_t* out, uint8_t* out_inf, hipStream_t s) {
+    const uint32_t lanes = segs * (uint32_t)which;
+    if (!lanes) return hipSuccess;
+    if (which == 1)
+        hipLaunchKernelGGL(k_msm_final<1>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const int4*)wsums, segs, windows, c, out, out_inf);
+    else
+        hipLaunchKernelGGL(k_msm_final<2>, dim3((lanes + 63) / 64), dim3(64), 0, s, (const int4*)wsums, segs, windows, c, out, out_inf);
     return hipGetLastError();
 }
 

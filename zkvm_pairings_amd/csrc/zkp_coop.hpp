@@ -29,6 +29,17 @@ hipError_t coop_g1_valid(const uint64_t* g1, const uint8_t* inf, size_t n, uint8
 hipError_t coop_g2_valid(CoopState* st, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* status, hipStream_t s);
 hipError_t coop_g1_mul(const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf, hipStream_t s);
 hipError_t coop_g2_mul(const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf, hipStream_t s);
+// out[i] = a[i] + b[i] on the 28-bit core, which = 1 (G1) or 2 (G2); ia / ib / out_inf may be null
+hipError_t coop_add(int which, const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, size_t n, uint64_t* out, uint8_t* out_inf,
+                    hipStream_t s);
+// the bucket MSM's launches (zkp_coop.hip, "group addition and bucket MSM"; driven by zkp_msm.hip, sized by zkp_msm_plan.hpp)
+hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s);
+hipError_t msm_digits(const uint64_t* sc, const uint8_t* inf, uint32_t terms, uint32_t m, int shared, uint32_t c, uint32_t windows, uint32_t* keys,
+                      uint32_t* vals, hipStream_t s);
+hipError_t msm_accum(int which, bool level0, const uint32_t* keys, const uint32_t* vals, const void* src, uint32_t n, uint32_t n_sums, void* sums,
+                     uint32_t* okeys, void* oj, hipStream_t s);
+hipError_t msm_reduce(int which, const void* buckets, uint32_t n_sums, uint32_t split, uint32_t chunk, uint32_t* okeys, void* oj, hipStream_t s);
+hipError_t msm_final(int which, const void* wsums, uint32_t segs, uint32_t windows, uint32_t c, uint64_t* out, uint8_t* out_inf, hipStream_t s);
 // one tower operation per record (zkp_tower_op_batch); ab = n a-records followed by n b-records
 hipError_t coop_tower_op(CoopState* st, int op, const uint64_t* ab, size_t n, uint32_t repeat, uint64_t* out, hipStream_t s);
 hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hipEvent_t e0, hipEvent_t e1, float* ms);

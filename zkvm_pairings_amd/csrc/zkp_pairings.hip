@@ -18,6 +18,8 @@
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
+#include "zkp_msm.hpp"
+#include "zkp_msm_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -446,6 +448,8 @@ struct zkp_ctx {
     size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int* d_flag = nullptr;      // [0] product check result, [1] AND flag of the host entry points, [2] sticky validation word of the *_dev calls
     hipEvent_t ws_busy = nullptr;   // recorded at the end of every *_dev call: the next call (on whatever stream) waits for it
+    void* msm_ws = nullptr;     // grow-only workspace of the MSM calls (zkp_msm_plan.hpp layout)
+    size_t msm_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -835,6 +839,7 @@ void zkp_free(zkp_ctx* c) {
         if (c->pc[i]) (void)hipFree(c->pc[i]);
     if (c->d_flag) (void)hipFree(c->d_flag);
     if (c->prod) (void)hipFree(c->prod);
+    if (c->msm_ws) (void)hipFree(c->msm_ws);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1183,6 +1188,57 @@ int zkp_g2_mul_batch_dev(zkp_ctx* c, const void* base, size_t stride, const void
 }
 // validation mode of the device-pointer entry points: *bad = 1 if any *_dev call since the last query saw a field
 // element >= p in its inputs (the results of such a call are unspecified).  Waits for `stream`, then clears the word.
+// ---- group addition and multi-scalar multiplication (28-bit core whatever zkp_set_kernel says)
+static int add_dev(zkp_ctx* c, int which, const void* a, const void* ia, const void* b, const void* ib, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || too_many(n) || (n && (!a || !b || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    const size_t nfp = n * (which == 1 ? 2 : 4);
+    int rc;
+    if ((rc = validate_on_stream(c, a, nfp, S(stream))) || (rc = validate_on_stream(c, b, nfp, S(stream)))) return rc;
+    return coop_rc(c, which == 1 ? "g1_add" : "g2_add",
+                   zkp::coop_add(which, (const uint64_t*)a, (const uint8_t*)ia, (const uint64_t*)b, (const uint8_t*)ib, n, (uint64_t*)out, (uint8_t*)out_inf,
+                                 S(stream)));
+}
+int zkp_g1_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, void* stream) {
+    return add_dev(c, 1, a, inf_a, b, inf_b, n, out, out_inf, stream);
+}
+int zkp_g2_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, void* stream) {
+    return add_dev(c, 2, a, inf_a, b, inf_b, n, out, out_inf, stream);
+}
+static int msm_dev(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, int shared, void* out, void* out_inf,
+                   void* stream, float* phase_ms) {
+    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!pts || !sc || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_msm) return ZKP_OK;
+    if (int rc = validate_on_stream(c, pts, (shared ? m : m * n_msm) * (which == 1 ? 2 : 4), S(stream))) return rc;
+    const size_t bytes = zkp::msm_workspace_bytes(which, m, n_msm, shared);
+    if (!bytes) { c->err = "msm: workspace size"; return ZKP_ERR_ARG; }
+    if (bytes > c->msm_cap) {
+        if (c->msm_ws) { HIPCHK(c, hipFree(c->msm_ws)); c->msm_ws = nullptr; c->msm_cap = 0; }
+        if (hipMalloc(&c->msm_ws, bytes) != hipSuccess) { c->msm_ws = nullptr; c->err = "msm: workspace allocation"; return ZKP_ERR_OOM; }
+        zkp_dbg_alloc("ctx.msm", c->msm_ws, bytes);
+        c->msm_cap = bytes;
+    }
+    return coop_rc(c, which == 1 ? "g1_msm" : "g2_msm",
+                   zkp::msm_run(which, c->msm_ws, (const uint64_t*)pts, (const uint8_t*)inf, (const uint64_t*)sc, m, n_msm, shared ? 1 : 0, (uint64_t*)out,
+                                (uint8_t*)out_inf, S(stream), phase_ms));
+}
+int zkp_g1_msm_batch_dev(zkp_ctx* c, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases, void* out,
+                         void* out_inf, void* stream) {
+    return msm_dev(c, 1, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, nullptr);
+}
+int zkp_g2_msm_batch_dev(zkp_ctx* c, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases, void* out,
+                         void* out_inf, void* stream) {
+    return msm_dev(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, nullptr);
+}
+int zkp_msm_profile_dev(zkp_ctx* c, int which, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases,
+                        void* out, void* out_inf, void* stream, float* phase_ms) {
+    if (!phase_ms || (which != 1 && which != 2)) return ZKP_ERR_ARG;
+    for (int i = 0; i < zkp::MSM_PHASES; i++) phase_ms[i] = 0;
+    return msm_dev(c, which, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, phase_ms);
+}
+
 int zkp_take_validation_status_dev(zkp_ctx* c, void* stream, int* bad) {
     if (!c || !bad) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
@@ -1359,6 +1415,64 @@ int zkp_g1_mul_batch(zkp_ctx* c, const uint64_t* base, size_t stride, const uint
 }
 int zkp_g2_mul_batch(zkp_ctx* c, const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf) {
     return mul_host(c, 2, base, stride, sc, n, out, out_inf);
+}
+static int add_host(zkp_ctx* c, int which, const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, size_t n, uint64_t* out,
+                    uint8_t* out_inf) {
+    const size_t w = which == 1 ? 12 : 24;
+    if (!c || too_many(n) || (n && (!a || !b || !out))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    int rc = bind(c);
+    if (rc) return rc;
+    HostCall drain(c);
+    if ((rc = ensure(c, 0, n * w * 8)) || (rc = ensure(c, 1, n * w * 8)) || (rc = ensure(c, 4, n * w * 8)) || (rc = ensure(c, 6, n)) ||
+        (ia && (rc = ensure(c, 2, n))) || (ib && (rc = ensure(c, 3, n))))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(c->buf[0], a, n * w * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->buf[1], b, n * w * 8, hipMemcpyHostToDevice, c->stream));
+    if (ia) HIPCHK(c, hipMemcpyAsync(c->buf[2], ia, n, hipMemcpyHostToDevice, c->stream));
+    if (ib) HIPCHK(c, hipMemcpyAsync(c->buf[3], ib, n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n * w / 6)) || (rc = validate_dev(c, (const uint64_t*)c->buf[1], n * w / 6))) return rc;
+    if ((rc = add_dev(c, which, c->buf[0], ia ? c->buf[2] : nullptr, c->buf[1], ib ? c->buf[3] : nullptr, n, c->buf[4], c->buf[6], c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n * w * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_inf) HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+}
+int zkp_g1_add_batch(zkp_ctx* c, const uint64_t* a, const uint8_t* inf_a, const uint64_t* b, const uint8_t* inf_b, size_t n, uint64_t* out, uint8_t* out_inf) {
+    return add_host(c, 1, a, inf_a, b, inf_b, n, out, out_inf);
+}
+int zkp_g2_add_batch(zkp_ctx* c, const uint64_t* a, const uint8_t* inf_a, const uint64_t* b, const uint8_t* inf_b, size_t n, uint64_t* out, uint8_t* out_inf) {
+    return add_host(c, 2, a, inf_a, b, inf_b, n, out, out_inf);
+}
+static int msm_host(zkp_ctx* c, int which, const uint64_t* pts, const uint8_t* inf, const uint64_t* sc, size_t m, size_t n_msm, int shared, uint64_t* out,
+                    uint8_t* out_inf) {
+    const size_t w = which == 1 ? 12 : 24;
+    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!pts || !sc || !out))) return ZKP_ERR_ARG;
+    if (!n_msm) return ZKP_OK;
+    int rc = bind(c);
+    if (rc) return rc;
+    HostCall drain(c);
+    const size_t terms = m * n_msm, np = shared ? m : terms;
+    if ((rc = ensure(c, 0, np * w * 8)) || (rc = ensure(c, 1, terms * 32)) || (rc = ensure(c, 4, n_msm * w * 8)) || (rc = ensure(c, 6, n_msm)) ||
+        (inf && (rc = ensure(c, 2, np))))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(c->buf[0], pts, np * w * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->buf[1], sc, terms * 32, hipMemcpyHostToDevice, c->stream));
+    if (inf) HIPCHK(c, hipMemcpyAsync(c->buf[2], inf, np, hipMemcpyHostToDevice, c->stream));
+    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], np * w / 6))) return rc;
+    if ((rc = msm_dev(c, which, c->buf[0], inf ? c->buf[2] : nullptr, c->buf[1], m, n_msm, shared, c->buf[4], c->buf[6], c->stream, nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n_msm * w * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_inf) HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[6], n_msm, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+}
+int zkp_g1_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases, uint64_t* out,
+                     uint8_t* out_inf) {
+    return msm_host(c, 1, points, inf, scalars, m, n_msm, shared_bases, out, out_inf);
+}
+int zkp_g2_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases, uint64_t* out,
+                     uint8_t* out_inf) {
+    return msm_host(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf);
 }
 static int codec_host(zkp_ctx* c, bool decode, int nfp, const void* in, const uint8_t* inf_in, size_t n, void* out, uint8_t* out_inf, uint8_t* status) {
     if (!c || (n && (!in || !out)) || (decode && n && (!out_inf || !status))) return ZKP_ERR_ARG;

@@ -262,6 +262,90 @@ class PairingEngine:
         self._chk(self._lib.zkp_g2_mul_batch(self._h, _ptr(base), stride, _ptr(sc), n, _ptr(out), _ptr(oi)))
         return out, oi
 
+    def g1_add(self, a, b, inf_a=None, inf_b=None):
+        """a[i] + b[i] (G1Affine Add); -> (points (n,12), inf (n,)).  torch tensors stay on the GPU (the engine's stream)."""
+        return self._add(a, b, inf_a, inf_b, 1)
+
+    def g2_add(self, a, b, inf_a=None, inf_b=None):
+        return self._add(a, b, inf_a, inf_b, 2)
+
+    def g1_msm(self, points, scalars, n_msm=1, inf=None, shared_bases=False):
+        """n_msm sums of m = len(scalars) / n_msm terms: out[j] = sum_i [k_(j,i)] P_(j,i); points hold m (shared_bases) or
+        m * n_msm entries.  -> (points (n_msm,12), inf (n_msm,))"""
+        return self._msm(points, scalars, n_msm, inf, shared_bases, 1)
+
+    def g2_msm(self, points, scalars, n_msm=1, inf=None, shared_bases=False):
+        return self._msm(points, scalars, n_msm, inf, shared_bases, 2)
+
+    def _add(self, a, b, inf_a, inf_b, which):
+        cols = 12 if which == 1 else 24
+        if _is_torch(a):
+            import torch
+            self._t_check(a, cols, "a")
+            self._t_check(b, cols, "b")
+            n = a.numel() // cols
+            if b.numel() != a.numel():
+                raise ValueError("a and b differ in number of points")
+            self._t_bytes(inf_a, n, "inf_a"), self._t_bytes(inf_b, n, "inf_b")
+            out = torch.empty((n, cols), dtype=a.dtype, device=a.device)
+            oi = torch.empty(n, dtype=torch.uint8, device=a.device)
+            fn = self._lib.zkp_g1_add_batch_dev if which == 1 else self._lib.zkp_g2_add_batch_dev
+            self._chk(fn(self._h, self._tp(a), self._tp(inf_a), self._tp(b), self._tp(inf_b), n, self._tp(out), self._tp(oi), self._stream()))
+            return out, oi
+        a, b = _np(a, cols), _np(b, cols)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("a and b differ in number of points")
+        ia, ib = _flags(inf_a, n, "inf_a"), _flags(inf_b, n, "inf_b")
+        out, oi = np.empty((n, cols), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        fn = self._lib.zkp_g1_add_batch if which == 1 else self._lib.zkp_g2_add_batch
+        self._chk(fn(self._h, _ptr(a), _ptr(ia), _ptr(b), _ptr(ib), n, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def _msm_shape(self, n_pts, n_sc, n_msm, shared):
+        if n_msm < 1 or n_sc % n_msm:
+            raise ValueError("%d scalars do not split into %d sums" % (n_sc, n_msm))
+        m = n_sc // n_msm
+        if n_pts != (m if shared else n_sc):
+            raise ValueError("%d points for %d sums of %d terms (shared_bases=%s)" % (n_pts, n_msm, m, bool(shared)))
+        return m
+
+    def _msm(self, points, scalars, n_msm, inf, shared, which):
+        cols = 12 if which == 1 else 24
+        n_msm = int(n_msm)
+        if _is_torch(scalars):
+            import torch
+            self._t_check(scalars, 4, "scalars")
+            self._t_check(points, cols, "points")
+            m = self._msm_shape(points.numel() // cols, scalars.numel() // 4, n_msm, shared)
+            self._t_bytes(inf, points.numel() // cols, "inf")
+            out = torch.empty((n_msm, cols), dtype=scalars.dtype, device=scalars.device)
+            oi = torch.empty(n_msm, dtype=torch.uint8, device=scalars.device)
+            fn = self._lib.zkp_g1_msm_batch_dev if which == 1 else self._lib.zkp_g2_msm_batch_dev
+            self._chk(fn(self._h, self._tp(points), self._tp(inf), self._tp(scalars), m, n_msm, 1 if shared else 0, self._tp(out), self._tp(oi),
+                         self._stream()))
+            return out, oi
+        pts, sc = _np(points, cols), _np(scalars, 4)
+        m = self._msm_shape(pts.shape[0], sc.shape[0], n_msm, shared)
+        i = _flags(inf, pts.shape[0], "inf")
+        out, oi = np.empty((n_msm, cols), dtype=np.uint64), np.empty(n_msm, dtype=np.uint8)
+        fn = self._lib.zkp_g1_msm_batch if which == 1 else self._lib.zkp_g2_msm_batch
+        self._chk(fn(self._h, _ptr(pts), _ptr(i), _ptr(sc), m, n_msm, 1 if shared else 0, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def msm_profile(self, which, points, scalars, n_msm=1, shared_bases=False):
+        """measurement: one MSM on torch tensors with the milliseconds of its six phases (zkp_msm_profile_dev)"""
+        import torch
+        cols = 12 if which == 1 else 24
+        self._t_check(scalars, 4, "scalars"), self._t_check(points, cols, "points")
+        m = self._msm_shape(points.numel() // cols, scalars.numel() // 4, n_msm, shared_bases)
+        out = torch.empty((n_msm, cols), dtype=scalars.dtype, device=scalars.device)
+        oi = torch.empty(n_msm, dtype=torch.uint8, device=scalars.device)
+        ms = (ctypes.c_float * 6)()
+        self._chk(self._lib.zkp_msm_profile_dev(self._h, int(which), self._tp(points), None, self._tp(scalars), m, int(n_msm), 1 if shared_bases else 0,
+                                                self._tp(out), self._tp(oi), self._stream(), ms))
+        return out, oi, list(ms)
+
     def decode_points(self, data, which):
         """uncompressed big-endian bytes -> (points, inf, status); which = 1 (G1, 96 B) or 2 (G2, 192 B)"""
         size = 96 if which == 1 else 192

@@ -24,6 +24,13 @@ def default_engine():
     return _default
 
 
+P_MODULUS = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+
+
+def _fp_neg(v):
+    return (P_MODULUS - v) % P_MODULUS   # Fp::neg: zero stays zero
+
+
 def _limbs(v):
     return [(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(6)]
 
@@ -79,6 +86,21 @@ class G1Affine:
         out, inf = default_engine().g1_mul(self.to_array(), synthetic.int_to_scalar(int(k) % synthetic.R_ORDER))
         return G1Affine.from_array(out[0], bool(inf[0]))
 
+    def __neg__(self):
+        """src/g1.rs:118-128, on the host: y -> -y, the flag kept (the identity's y = 1 becomes p - 1, as upstream)"""
+        return G1Affine(self.x, _fp_neg(self.y), self.is_infinity)
+
+    def __add__(self, o):
+        """src/g1.rs:155-187 on the GPU; P + (-P) is the identity (upstream panics there)"""
+        out, inf = default_engine().g1_add(self.to_array(), o.to_array(), [1 if self.is_infinity else 0], [1 if o.is_infinity else 0])
+        return G1Affine.from_array(out[0], bool(inf[0]))
+
+    def __sub__(self, o):
+        return self + (-o)
+
+    def double(self):
+        return self + self
+
     def __eq__(self, o):  # src/g1.rs:13-17 compares coordinates only
         return self.x == o.x and self.y == o.y
 
@@ -133,6 +155,21 @@ class G2Affine:
         out, inf = default_engine().g2_mul(self.to_array(), synthetic.int_to_scalar(int(k) % synthetic.R_ORDER))
         return G2Affine.from_array(out[0], bool(inf[0]))
 
+    def __neg__(self):
+        """src/g2.rs:173-183, on the host"""
+        return G2Affine(self.x, (_fp_neg(self.y[0]), _fp_neg(self.y[1])), self.is_infinity)
+
+    def __add__(self, o):
+        """src/g2.rs:210-242 on the GPU; P + (-P) is the identity (upstream panics there)"""
+        out, inf = default_engine().g2_add(self.to_array(), o.to_array(), [1 if self.is_infinity else 0], [1 if o.is_infinity else 0])
+        return G2Affine.from_array(out[0], bool(inf[0]))
+
+    def __sub__(self, o):
+        return self + (-o)
+
+    def double(self):
+        return self + self
+
     def __eq__(self, o):
         return self.x == o.x and self.y == o.y
 
@@ -186,3 +223,25 @@ def pairing(p, q, engine=None):
     e = engine or default_engine()
     out = e.pairing(p.to_array(), q.to_array(), [1 if p.is_infinity else 0], [1 if q.is_infinity else 0])
     return Gt(out[0])
+
+
+def msm(points, scalars, engine=None):
+    """sum_i [k_i] P_i on the GPU (bucket method) for a sequence of G1Affine or of G2Affine points and integer scalars (full 256-bit
+    integers, not reduced mod r).  An empty sum is the identity of G1."""
+    points, scalars = list(points), [int(k) for k in scalars]
+    if len(points) != len(scalars):
+        raise ValueError("%d points, %d scalars" % (len(points), len(scalars)))
+    g2 = bool(points) and isinstance(points[0], G2Affine)
+    cls = G2Affine if g2 else G1Affine
+    if not points:
+        return cls.identity()
+    if any(k < 0 or k >> 256 for k in scalars):
+        raise ValueError("msm: scalars are integers in [0, 2^256)")
+    if any(not isinstance(p, cls) for p in points):
+        raise TypeError("msm: mixed G1 and G2 points")
+    e = engine or default_engine()
+    pts = np.stack([p.to_array() for p in points])
+    inf = np.array([p.is_infinity for p in points], dtype=np.uint8)
+    sc = np.stack([synthetic.int_to_scalar(k) for k in scalars])
+    out, oi = (e.g2_msm if g2 else e.g1_msm)(pts, sc, 1, inf)
+    return cls.from_array(out[0], bool(oi[0]))
