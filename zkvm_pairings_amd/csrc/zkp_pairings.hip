@@ -734,45 +734,75 @@ int host_sliced(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_
     return rc;
 }
 
-// copy a (g1,g2,inf1,inf2) pair batch to workspace slots 0..3
-int stage_pairs(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t np, Staged* st) {
-    int rc;
-    if ((rc = ensure(c, 0, np * 96)) || (rc = ensure(c, 1, np * 192))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], g1, np * 96, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[1], g2, np * 192, hipMemcpyHostToDevice, c->stream));
-    st->g1 = (const uint64_t*)c->buf[0];
-    st->g2 = (const uint64_t*)c->buf[1];
-    st->i1 = st->i2 = nullptr;
-    if (inf1) {
-        if ((rc = ensure(c, 2, np))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->buf[2], inf1, np, hipMemcpyHostToDevice, c->stream));
-        st->i1 = (const uint8_t*)c->buf[2];
+// Staging of a host-pointer call on the context's stream.  in() grows a workspace slot and queues the upload of a host array into it
+// (a null host pointer gives a null device pointer and grows nothing); out() grows a slot and notes its download into a host array
+// (none for a null one), which send() queues behind the work.  The first failure is kept (status()) and makes every later step a
+// no-op, so one check before the launch covers them all.
+struct Staging {
+    zkp_ctx* c;
+    int rc = ZKP_OK;
+    struct Copy { void* host; const void* dev; size_t bytes; } down[4];   // the most a call needs: the points check's
+    int n_down = 0;
+    explicit Staging(zkp_ctx* ctx) : c(ctx) {}
+    int status() const { return rc; }
+    void* slot(int i, size_t bytes) {
+        if (!rc) rc = ensure(c, i, bytes);
+        return rc ? nullptr : c->buf[i];
     }
-    if (inf2) {
-        if ((rc = ensure(c, 3, np))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->buf[3], inf2, np, hipMemcpyHostToDevice, c->stream));
-        st->i2 = (const uint8_t*)c->buf[3];
+    const void* put(void* dev, const void* host, size_t bytes) {
+        if (!rc && host && bytes) rc = coop_rc(c, "hipMemcpyAsync (upload)", hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+        return host ? dev : nullptr;
     }
-    if ((rc = validate_dev(c, st->g1, np * 2)) || (rc = validate_dev(c, st->g2, np * 4))) return rc;
-    return ZKP_OK;
-}
-
-}  // namespace
+    void get(void* host, const void* dev, size_t bytes) {
+        if (!host || !bytes || rc) return;
+        if (n_down == 4) { c->err = "Staging: more than four downloads"; rc = ZKP_ERR_ARG; return; }
+        down[n_down++] = {host, dev, bytes};
+    }
+    const void* in(int i, const void* host, size_t bytes) { return host ? put(slot(i, bytes), host, bytes) : nullptr; }
+    void* out(int i, void* host, size_t bytes) {
+        void* d = slot(i, bytes);
+        get(host, d, bytes);
+        return d;
+    }
+    int send() {
+        for (int i = 0; i < n_down && !rc; i++)
+            rc = coop_rc(c, "hipMemcpyAsync (download)", hipMemcpyAsync(down[i].host, down[i].dev, down[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        return rc;
+    }
+};
 
 // Host-pointer entry points copy from / into the caller's arrays asynchronously: whatever way such a call returns
 // (HIPCHK included), nothing may still be in flight - the context's stream is drained on the way out.
-namespace {
-struct HostCall {
-    zkp_ctx* c;
-    explicit HostCall(zkp_ctx* ctx) : c(ctx) {   // earlier *_dev calls may still be using the workspace on other streams
-        if (c && c->stream && c->ws_busy) (void)hipStreamWaitEvent(c->stream, c->ws_busy, 0);
+struct HostIO : Staging {
+    bool bound;
+    explicit HostIO(zkp_ctx* ctx) : Staging(ctx) {
+        rc = bind(c);
+        bound = rc == ZKP_OK;
+        if (bound) (void)hipStreamWaitEvent(c->stream, c->ws_busy, 0);   // earlier *_dev calls may still be using the workspace on other streams
     }
-    ~HostCall() {
-        if (!c || !c->stream) return;
-        if (c->ws_busy) (void)hipEventRecord(c->ws_busy, c->stream);
+    ~HostIO() {
+        if (!bound) return;
+        (void)hipEventRecord(c->ws_busy, c->stream);
         (void)hipStreamSynchronize(c->stream);
     }
+    // the noted downloads, then one synchronisation
+    int finish() {
+        if (!send()) rc = coop_rc(c, "hipStreamSynchronize", hipStreamSynchronize(c->stream));
+        return rc;
+    }
 };
+
+// a (g1,g2,inf1,inf2) pair batch to workspace slots 0..3, range-checked in validation mode
+int stage_pairs(Staging& io, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t np, Staged* st) {
+    st->g1 = (const uint64_t*)io.in(0, g1, np * 96);
+    st->g2 = (const uint64_t*)io.in(1, g2, np * 192);
+    st->i1 = (const uint8_t*)io.in(2, inf1, np);
+    st->i2 = (const uint8_t*)io.in(3, inf2, np);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(io.c, st->g1, np * 2)) || (rc = validate_dev(io.c, st->g2, np * 4))) return rc;
+    return ZKP_OK;
+}
+
 }  // namespace
 
 // =============================================================================== C ABI
@@ -903,6 +933,11 @@ int validate_on_stream(zkp_ctx* c, const void* d, size_t n_fp, hipStream_t s) {
     HIPCHK(c, hipGetLastError());
     return ZKP_OK;
 }
+// ... of the G1 and G2 points of n pairs
+int validate_pairs_on_stream(zkp_ctx* c, const void* g1, const void* g2, size_t n, hipStream_t s) {
+    const int rc = validate_on_stream(c, g1, n * 2, s);
+    return rc ? rc : validate_on_stream(c, g2, n * 4, s);
+}
 }  // namespace
 #define DEV_ENTER(ctx, stream)      \
     DevCall dc__((ctx), (stream)); \
@@ -913,16 +948,14 @@ using zkp::plan::too_many;   // zkp_plan.hpp: n <= 2^31 - 1, k <= 65535, n * k <
 int zkp_pairing_batch_dev(zkp_ctx* c, const void* g1, const void* g2, const void* i1, const void* i2, size_t n, void* out, void* stream) {
     if (!c || too_many(n) || (n && (!g1 || !g2 || !out))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n * 2, S(stream))) || (rc = validate_on_stream(c, g2, n * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n, S(stream))) return rc;
     return pairing_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n, 1, (uint64_t*)out, nullptr, nullptr, S(stream));
 }
 int zkp_multi_miller_loop_batch_dev(zkp_ctx* c, const void* g1, const void* g2, const void* i1, const void* i2, size_t n_checks, size_t k,
                                     void* out, void* stream) {
     if (!c || too_many(n_checks, k) || (n_checks && (!out || (k && (!g1 || !g2))))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n_checks * k * 2, S(stream))) || (rc = validate_on_stream(c, g2, n_checks * k * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n_checks * k, S(stream))) return rc;
     return miller_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n_checks, k, (uint64_t*)out, S(stream));
 }
 int zkp_final_exponentiation_batch_dev(zkp_ctx* c, const void* f, size_t n, void* out, void* stream) {
@@ -940,16 +973,14 @@ int zkp_fp12_product_dev(zkp_ctx* c, const void* f, size_t n, void* out, void* s
 int zkp_miller_product_dev(zkp_ctx* c, const void* g1, const void* g2, const void* i1, const void* i2, size_t n, void* out_ml, void* stream) {
     if (!c || !out_ml || (n && (!g1 || !g2)) || too_many(n)) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n * 2, S(stream))) || (rc = validate_on_stream(c, g2, n * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n, S(stream))) return rc;
     return miller_product_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n, (uint64_t*)out_ml, S(stream));
 }
 int zkp_pairing_product_check_dev(zkp_ctx* c, const void* g1, const void* g2, const void* i1, const void* i2, size_t n, void* out_gt,
                                   void* is_one, void* stream) {
     if (!c || (n && (!g1 || !g2)) || too_many(n)) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n * 2, S(stream))) || (rc = validate_on_stream(c, g2, n * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n, S(stream))) return rc;
     return product_check_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n, (uint64_t*)out_gt, (int*)is_one,
                              S(stream));
 }
@@ -957,8 +988,7 @@ int zkp_pairing_check_batch_dev(zkp_ctx* c, const void* g1, const void* g2, cons
                                 void* ok, void* all_ok, void* stream) {
     if (!c || too_many(n_checks, k) || (n_checks && k && (!g1 || !g2))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n_checks * k * 2, S(stream))) || (rc = validate_on_stream(c, g2, n_checks * k * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n_checks * k, S(stream))) return rc;
     return pairing_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n_checks, k, nullptr, (uint8_t*)ok,
                        (int*)all_ok, S(stream));
 }
@@ -966,8 +996,7 @@ int zkp_pairing_gt_check_batch_dev(zkp_ctx* c, const void* g1, const void* g2, c
                                    void* out_gt, void* ok, void* all_ok, void* stream) {
     if (!c || too_many(n_checks, k) || (n_checks && k && (!g1 || !g2))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    int rc;
-    if ((rc = validate_on_stream(c, g1, n_checks * k * 2, S(stream))) || (rc = validate_on_stream(c, g2, n_checks * k * 4, S(stream)))) return rc;
+    if (int rc = validate_pairs_on_stream(c, g1, g2, n_checks * k, S(stream))) return rc;
     return pairing_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, (const uint8_t*)i1, (const uint8_t*)i2, n_checks, k, (uint64_t*)out_gt,
                        (uint8_t*)ok, (int*)all_ok, S(stream));
 }
@@ -1000,10 +1029,15 @@ int zkp_g2_is_valid_batch_dev(zkp_ctx* c, const void* g2, const void* inf, size_
     if (int rc = validate_on_stream(c, g2, n * 4, S(stream))) return rc;
     return valid_dev(c, 2, g2, inf, n, status, S(stream));
 }
-// ---- uncompressed point codec on resident buffers (round 4): the decode / encode kernels without the PCIe round trip
-static int codec_dev(zkp_ctx* c, bool decode, int nfp, const void* in, const void* inf_in, size_t n, void* out, void* out_inf, void* status,
-                     hipStream_t s) {
+// ---- point codecs on resident buffers: uncompressed (96 / 192 B per G1 / G2 point, round 4: the decode / encode kernels above) or
+// compressed (48 / 96 B, zkp_compress.hip).  decode: bytes -> points, infinity flags, status bytes; encode: points (+ flags) -> bytes
+static int codec_dev(zkp_ctx* c, bool compressed, bool decode, int which, const void* in, const void* inf_in, size_t n, void* out, void* out_inf,
+                     void* status, hipStream_t s) {
     if (!n) return ZKP_OK;
+    if (compressed)
+        return decode ? coop_rc(c, which == 1 ? "g1_decompress" : "g2_decompress", zkp_cmp::decompress(which, in, n, out, out_inf, status, s))
+                      : coop_rc(c, which == 1 ? "g1_compress" : "g2_compress", zkp_cmp::compress(which, in, inf_in, n, out, s));
+    const int nfp = 2 * which;
     const bool aligned = (((uintptr_t)in | (uintptr_t)out) & 7u) == 0;
     if (decode) {
         if (aligned)
@@ -1022,22 +1056,22 @@ static int codec_dev(zkp_ctx* c, bool decode, int nfp, const void* in, const voi
 int zkp_g1_decode_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g1, void* out_inf, void* status, void* stream) {
     if (!c || too_many(n) || (n && (!bytes || !out_g1 || !out_inf || !status))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return codec_dev(c, true, 2, bytes, nullptr, n, out_g1, out_inf, status, S(stream));
+    return codec_dev(c, false, true, 1, bytes, nullptr, n, out_g1, out_inf, status, S(stream));
 }
 int zkp_g2_decode_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g2, void* out_inf, void* status, void* stream) {
     if (!c || too_many(n) || (n && (!bytes || !out_g2 || !out_inf || !status))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return codec_dev(c, true, 4, bytes, nullptr, n, out_g2, out_inf, status, S(stream));
+    return codec_dev(c, false, true, 2, bytes, nullptr, n, out_g2, out_inf, status, S(stream));
 }
 int zkp_g1_encode_batch_dev(zkp_ctx* c, const void* g1, const void* inf, size_t n, void* out_bytes, void* stream) {
     if (!c || too_many(n) || (n && (!g1 || !out_bytes))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return codec_dev(c, false, 2, g1, inf, n, out_bytes, nullptr, nullptr, S(stream));
+    return codec_dev(c, false, false, 1, g1, inf, n, out_bytes, nullptr, nullptr, S(stream));
 }
 int zkp_g2_encode_batch_dev(zkp_ctx* c, const void* g2, const void* inf, size_t n, void* out_bytes, void* stream) {
     if (!c || too_many(n) || (n && (!g2 || !out_bytes))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return codec_dev(c, false, 4, g2, inf, n, out_bytes, nullptr, nullptr, S(stream));
+    return codec_dev(c, false, false, 2, g2, inf, n, out_bytes, nullptr, nullptr, S(stream));
 }
 
 // ---- BASELINE config 5 as ONE call: raw uncompressed bytes -> decode -> is_valid -> pairing check, everything between the byte
@@ -1084,14 +1118,9 @@ static int points_check_dev(zkp_ctx* c, const void* b1, const void* b2, size_t n
     uint8_t* s2 = st2 ? (uint8_t*)st2 : (uint8_t*)c->pc[PC_ST2];
     uint8_t* okb = ok ? (uint8_t*)ok : (uint8_t*)c->pc[PC_OK];
     if (np) {
-        if (compressed) {
-            if ((rc = coop_rc(c, "g1_decompress", zkp_cmp::decompress(1, b1, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s))) ||
-                (rc = coop_rc(c, "g2_decompress", zkp_cmp::decompress(2, b2, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s))))
-                return rc;
-        } else if ((rc = codec_dev(c, true, 2, b1, nullptr, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s)) ||
-                   (rc = codec_dev(c, true, 4, b2, nullptr, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s))) {
+        if ((rc = codec_dev(c, compressed, true, 1, b1, nullptr, np, c->pc[PC_G1], c->pc[PC_INF1], dec1, s)) ||
+            (rc = codec_dev(c, compressed, true, 2, b2, nullptr, np, c->pc[PC_G2], c->pc[PC_INF2], dec2, s)))
             return rc;
-        }
         if ((rc = valid_dev(c, 1, c->pc[PC_G1], c->pc[PC_INF1], np, val1, s)) || (rc = valid_dev(c, 2, c->pc[PC_G2], c->pc[PC_INF2], np, val2, s)))
             return rc;
         hipLaunchKernelGGL(k_points_merge, dim3(grid_for(np, 256)), dim3(256), 0, s, dec1, val1, (uint8_t*)c->pc[PC_INF1], np, s1);
@@ -1143,75 +1172,77 @@ int zkp_points_check_compressed_batch_dev(zkp_ctx* c, const void* g1_bytes, cons
 int zkp_g1_decompress_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g1, void* out_inf, void* status, void* stream) {
     if (!c || too_many(n) || (n && (!bytes || !out_g1 || !out_inf || !status))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return coop_rc(c, "g1_decompress", zkp_cmp::decompress(1, bytes, n, out_g1, out_inf, status, S(stream)));
+    return codec_dev(c, true, true, 1, bytes, nullptr, n, out_g1, out_inf, status, S(stream));
 }
 int zkp_g2_decompress_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out_g2, void* out_inf, void* status, void* stream) {
     if (!c || too_many(n) || (n && (!bytes || !out_g2 || !out_inf || !status))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return coop_rc(c, "g2_decompress", zkp_cmp::decompress(2, bytes, n, out_g2, out_inf, status, S(stream)));
+    return codec_dev(c, true, true, 2, bytes, nullptr, n, out_g2, out_inf, status, S(stream));
 }
 int zkp_g1_compress_batch_dev(zkp_ctx* c, const void* g1, const void* inf, size_t n, void* out_bytes, void* stream) {
     if (!c || too_many(n) || (n && (!g1 || !out_bytes))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return coop_rc(c, "g1_compress", zkp_cmp::compress(1, g1, inf, n, out_bytes, S(stream)));
+    return codec_dev(c, true, false, 1, g1, inf, n, out_bytes, nullptr, nullptr, S(stream));
 }
 int zkp_g2_compress_batch_dev(zkp_ctx* c, const void* g2, const void* inf, size_t n, void* out_bytes, void* stream) {
     if (!c || too_many(n) || (n && (!g2 || !out_bytes))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    return coop_rc(c, "g2_compress", zkp_cmp::compress(2, g2, inf, n, out_bytes, S(stream)));
+    return codec_dev(c, true, false, 2, g2, inf, n, out_bytes, nullptr, nullptr, S(stream));
+}
+
+// [sc_i] base_i of n G1 (which = 1) or G2 (which = 2) points; stride 0: one base point for every scalar
+static int mul_dev(zkp_ctx* c, int which, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, hipStream_t s) {
+    if (zkp::coop_selected(&c->coop, c->kernel)) {
+        HIPCHK(c, which == 1 ? zkp::coop_g1_mul((const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf, s)
+                             : zkp::coop_g2_mul((const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf, s));
+        return ZKP_OK;
+    }
+    if (which == 1)
+        hipLaunchKernelGGL(k_g1_mul, dim3(grid_for(n, TPB)), dim3(TPB), 0, s, (const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf);
+    else
+        hipLaunchKernelGGL(k_g2_mul, dim3(grid_for(n, TPB)), dim3(TPB), 0, s, (const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf);
+    HIPCHK(c, hipGetLastError());
+    return ZKP_OK;
 }
 int zkp_g1_mul_batch_dev(zkp_ctx* c, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, void* stream) {
     if (!c || too_many(n) || (n && (!base || !sc || !out)) || (stride != 0 && stride != 12)) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
     if (!n) return ZKP_OK;
     if (int rc = validate_on_stream(c, base, (stride ? n : 1) * 2, S(stream))) return rc;
-    if (zkp::coop_selected(&c->coop, c->kernel)) {
-        HIPCHK(c, zkp::coop_g1_mul((const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf, S(stream)));
-        return ZKP_OK;
-    }
-    hipLaunchKernelGGL(k_g1_mul, dim3(grid_for(n, TPB)), dim3(TPB), 0, S(stream), (const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf);
-    HIPCHK(c, hipGetLastError());
-    return ZKP_OK;
+    return mul_dev(c, 1, base, stride, sc, n, out, out_inf, S(stream));
 }
 int zkp_g2_mul_batch_dev(zkp_ctx* c, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, void* stream) {
     if (!c || too_many(n) || (n && (!base || !sc || !out)) || (stride != 0 && stride != 24)) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
     if (!n) return ZKP_OK;
     if (int rc = validate_on_stream(c, base, (stride ? n : 1) * 4, S(stream))) return rc;
-    if (zkp::coop_selected(&c->coop, c->kernel)) {
-        HIPCHK(c, zkp::coop_g2_mul((const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf, S(stream)));
-        return ZKP_OK;
-    }
-    hipLaunchKernelGGL(k_g2_mul, dim3(grid_for(n, TPB)), dim3(TPB), 0, S(stream), (const uint64_t*)base, stride, (const uint64_t*)sc, n, (uint64_t*)out, (uint8_t*)out_inf);
-    HIPCHK(c, hipGetLastError());
-    return ZKP_OK;
+    return mul_dev(c, 2, base, stride, sc, n, out, out_inf, S(stream));
 }
-// validation mode of the device-pointer entry points: *bad = 1 if any *_dev call since the last query saw a field
-// element >= p in its inputs (the results of such a call are unspecified).  Waits for `stream`, then clears the word.
+
 // ---- group addition and multi-scalar multiplication (28-bit core whatever zkp_set_kernel says)
-static int add_dev(zkp_ctx* c, int which, const void* a, const void* ia, const void* b, const void* ib, size_t n, void* out, void* out_inf, void* stream) {
+static int add_dev(zkp_ctx* c, int which, const void* a, const void* ia, const void* b, const void* ib, size_t n, void* out, void* out_inf, hipStream_t s) {
+    return coop_rc(c, which == 1 ? "g1_add" : "g2_add",
+                   zkp::coop_add(which, (const uint64_t*)a, (const uint8_t*)ia, (const uint64_t*)b, (const uint8_t*)ib, n, (uint64_t*)out, (uint8_t*)out_inf, s));
+}
+int zkp_g1_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, void* stream) {
     if (!c || too_many(n) || (n && (!a || !b || !out))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
     if (!n) return ZKP_OK;
-    const size_t nfp = n * (which == 1 ? 2 : 4);
     int rc;
-    if ((rc = validate_on_stream(c, a, nfp, S(stream))) || (rc = validate_on_stream(c, b, nfp, S(stream)))) return rc;
-    return coop_rc(c, which == 1 ? "g1_add" : "g2_add",
-                   zkp::coop_add(which, (const uint64_t*)a, (const uint8_t*)ia, (const uint64_t*)b, (const uint8_t*)ib, n, (uint64_t*)out, (uint8_t*)out_inf,
-                                 S(stream)));
-}
-int zkp_g1_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, void* stream) {
-    return add_dev(c, 1, a, inf_a, b, inf_b, n, out, out_inf, stream);
+    if ((rc = validate_on_stream(c, a, n * 2, S(stream))) || (rc = validate_on_stream(c, b, n * 2, S(stream)))) return rc;
+    return add_dev(c, 1, a, inf_a, b, inf_b, n, out, out_inf, S(stream));
 }
 int zkp_g2_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, void* stream) {
-    return add_dev(c, 2, a, inf_a, b, inf_b, n, out, out_inf, stream);
-}
-static int msm_dev(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, int shared, void* out, void* out_inf,
-                   void* stream, float* phase_ms) {
-    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!pts || !sc || !out))) return ZKP_ERR_ARG;
+    if (!c || too_many(n) || (n && (!a || !b || !out))) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
-    if (!n_msm) return ZKP_OK;
-    if (int rc = validate_on_stream(c, pts, (shared ? m : m * n_msm) * (which == 1 ? 2 : 4), S(stream))) return rc;
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = validate_on_stream(c, a, n * 4, S(stream))) || (rc = validate_on_stream(c, b, n * 4, S(stream)))) return rc;
+    return add_dev(c, 2, a, inf_a, b, inf_b, n, out, out_inf, S(stream));
+}
+// n_msm >= 1 sums; grows the context's MSM workspace (an allocation synchronises the device) before it queues anything
+static int msm_dev(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, int shared, void* out, void* out_inf,
+                   hipStream_t s, float* phase_ms) {
     const size_t bytes = zkp::msm_workspace_bytes(which, m, n_msm, shared);
     if (!bytes) { c->err = "msm: workspace size"; return ZKP_ERR_ARG; }
     if (bytes > c->msm_cap) {
@@ -1222,23 +1253,37 @@ static int msm_dev(zkp_ctx* c, int which, const void* pts, const void* inf, cons
     }
     return coop_rc(c, which == 1 ? "g1_msm" : "g2_msm",
                    zkp::msm_run(which, c->msm_ws, (const uint64_t*)pts, (const uint8_t*)inf, (const uint64_t*)sc, m, n_msm, shared ? 1 : 0, (uint64_t*)out,
-                                (uint8_t*)out_inf, S(stream), phase_ms));
+                                (uint8_t*)out_inf, s, phase_ms));
 }
 int zkp_g1_msm_batch_dev(zkp_ctx* c, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases, void* out,
                          void* out_inf, void* stream) {
-    return msm_dev(c, 1, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, nullptr);
+    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!points || !scalars || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_msm) return ZKP_OK;
+    if (int rc = validate_on_stream(c, points, (shared_bases ? m : m * n_msm) * 2, S(stream))) return rc;
+    return msm_dev(c, 1, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, S(stream), nullptr);
 }
 int zkp_g2_msm_batch_dev(zkp_ctx* c, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases, void* out,
                          void* out_inf, void* stream) {
-    return msm_dev(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, nullptr);
+    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!points || !scalars || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_msm) return ZKP_OK;
+    if (int rc = validate_on_stream(c, points, (shared_bases ? m : m * n_msm) * 4, S(stream))) return rc;
+    return msm_dev(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, S(stream), nullptr);
 }
 int zkp_msm_profile_dev(zkp_ctx* c, int which, const void* points, const void* inf, const void* scalars, size_t m, size_t n_msm, int shared_bases,
                         void* out, void* out_inf, void* stream, float* phase_ms) {
     if (!phase_ms || (which != 1 && which != 2)) return ZKP_ERR_ARG;
     for (int i = 0; i < zkp::MSM_PHASES; i++) phase_ms[i] = 0;
-    return msm_dev(c, which, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, stream, phase_ms);
+    if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!points || !scalars || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_msm) return ZKP_OK;
+    if (int rc = validate_on_stream(c, points, (shared_bases ? m : m * n_msm) * 2 * which, S(stream))) return rc;
+    return msm_dev(c, which, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, S(stream), phase_ms);
 }
 
+// validation mode of the device-pointer entry points: *bad = 1 if any *_dev call since the last query saw a field
+// element >= p in its inputs (the results of such a call are unspecified).  Waits for `stream`, then clears the word.
 int zkp_take_validation_status_dev(zkp_ctx* c, void* stream, int* bad) {
     if (!c || !bad) return ZKP_ERR_ARG;
     DEV_ENTER(c, stream);
@@ -1251,75 +1296,63 @@ int zkp_take_validation_status_dev(zkp_ctx* c, void* stream, int* bad) {
 }
 
 // ---------------------------------------------------------------- host-pointer API
+// Each call: argument checks, its inputs staged in the context's workspace (HostIO), the inputs range-checked in validation mode
+// (validate_dev), the same launch-only function as the *_dev flavour on the context's stream, the downloads and one synchronisation.
 int zkp_pairing_batch(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t n, uint64_t* out_gt) {
     if (!c || (n && (!g1 || !g2 || !out_gt))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
+    int rc;
+    if ((rc = io.status())) return rc;
     if (n > c->host_slice && !c->validate) return host_sliced(c, g1, g2, inf1, inf2, n, 1, out_gt, nullptr, nullptr);
     Staged st;
-    if ((rc = stage_pairs(c, g1, g2, inf1, inf2, n, &st)) || (rc = ensure(c, 4, n * 576))) return rc;
-    if ((rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, n, 1, (uint64_t*)c->buf[4], nullptr, nullptr, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_gt, c->buf[4], n * 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    if ((rc = stage_pairs(io, g1, g2, inf1, inf2, n, &st))) return rc;
+    void* gt = io.out(4, out_gt, n * 576);
+    if ((rc = io.status()) || (rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, n, 1, (uint64_t*)gt, nullptr, nullptr, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_multi_miller_loop_batch(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t n_checks,
                                 size_t k, uint64_t* out_ml) {
     if (!c || (n_checks && (!out_ml || (k && (!g1 || !g2))))) return ZKP_ERR_ARG;
     if (!n_checks) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
     Staged st = {nullptr, nullptr, nullptr, nullptr};
-    if (k && (rc = stage_pairs(c, g1, g2, inf1, inf2, n_checks * k, &st))) return rc;
-    if ((rc = ensure(c, 4, n_checks * 576))) return rc;
-    if ((rc = miller_dev(c, st.g1, st.g2, st.i1, st.i2, n_checks, k, (uint64_t*)c->buf[4], c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_ml, c->buf[4], n_checks * 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    int rc;
+    if (k && (rc = stage_pairs(io, g1, g2, inf1, inf2, n_checks * k, &st))) return rc;
+    void* out = io.out(4, out_ml, n_checks * 576);
+    if ((rc = io.status()) || (rc = miller_dev(c, st.g1, st.g2, st.i1, st.i2, n_checks, k, (uint64_t*)out, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_final_exponentiation_batch(zkp_ctx* c, const uint64_t* f, size_t n, uint64_t* out_gt) {
     if (!c || (n && (!f || !out_gt))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    if ((rc = ensure(c, 5, n * 576)) || (rc = ensure(c, 4, n * 576))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[5], f, n * 576, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[5], n * 12))) return rc;
-    if ((rc = final_exp_dev(c, (const uint64_t*)c->buf[5], n, (uint64_t*)c->buf[4], c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_gt, c->buf[4], n * 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    const uint64_t* df = (const uint64_t*)io.in(5, f, n * 576);
+    void* out = io.out(4, out_gt, n * 576);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, df, n * 12)) || (rc = final_exp_dev(c, df, n, (uint64_t*)out, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_fp12_product(zkp_ctx* c, const uint64_t* f, size_t n, uint64_t* out) {
     if (!c || !out || (n && !f) || n > 0x7fffffffu) return ZKP_ERR_ARG;
     if (!n) { memcpy(out, GT_IDENTITY, 576); return ZKP_OK; }
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    if ((rc = ensure_prod(c, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->prod, f, n * 576, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, c->prod, n * 12))) return rc;
-    if ((rc = fp12_product_inplace(c, c->prod, n, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->prod, 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    int rc;
+    if ((rc = io.status()) || (rc = ensure_prod(c, n))) return rc;
+    io.put(c->prod, f, n * 576);
+    io.get(out, c->prod, 576);
+    if ((rc = io.status()) || (rc = validate_dev(c, c->prod, n * 12)) || (rc = fp12_product_inplace(c, c->prod, n, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_miller_product(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t n, uint64_t* out_ml) {
     if (!c || !out_ml || (n && (!g1 || !g2)) || n > 0x7fffffffu) return ZKP_ERR_ARG;
     if (!n) { memcpy(out_ml, GT_IDENTITY, 576); return ZKP_OK; }
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    Staged st = {nullptr, nullptr, nullptr, nullptr};
-    if ((rc = stage_pairs(c, g1, g2, inf1, inf2, n, &st))) return rc;
-    if ((rc = miller_product_dev(c, st.g1, st.g2, st.i1, st.i2, n, nullptr, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_ml, c->prod, 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    Staged st;
+    int rc;
+    if ((rc = stage_pairs(io, g1, g2, inf1, inf2, n, &st)) || (rc = miller_product_dev(c, st.g1, st.g2, st.i1, st.i2, n, nullptr, c->stream))) return rc;
+    io.get(out_ml, c->prod, 576);   // the product tree's root (ensure_prod may have moved the tree)
+    return io.finish();
 }
 int zkp_pairing_product_check(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t n,
                               uint64_t* out_gt, int* is_one) {
@@ -1329,86 +1362,60 @@ int zkp_pairing_product_check(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2
         if (is_one) *is_one = 1;
         return ZKP_OK;
     }
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    Staged st = {nullptr, nullptr, nullptr, nullptr};
-    if ((rc = stage_pairs(c, g1, g2, inf1, inf2, n, &st))) return rc;
-    if ((rc = ensure(c, 4, 576))) return rc;
-    if ((rc = product_check_dev(c, st.g1, st.g2, st.i1, st.i2, n, (uint64_t*)c->buf[4], c->d_flag, c->stream))) return rc;
-    int one = 0;
-    if (out_gt) HIPCHK(c, hipMemcpyAsync(out_gt, c->buf[4], 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&one, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (is_one) *is_one = one;
-    return ZKP_OK;
+    HostIO io(c);
+    Staged st;
+    int rc;
+    if ((rc = stage_pairs(io, g1, g2, inf1, inf2, n, &st))) return rc;
+    void* gt = io.out(4, out_gt, 576);
+    io.get(is_one, c->d_flag, sizeof(int));
+    if ((rc = io.status()) || (rc = product_check_dev(c, st.g1, st.g2, st.i1, st.i2, n, (uint64_t*)gt, c->d_flag, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_pairing_check_batch(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, size_t n_checks,
                             size_t k, uint8_t* ok, int* all_ok) {
     if (!c || (n_checks && k && (!g1 || !g2))) return ZKP_ERR_ARG;
     if (all_ok) *all_ok = 1;
     if (!n_checks) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
+    int rc;
+    if ((rc = io.status())) return rc;
     // flags-only results need no large download: one shot is faster (measured) until the upload workspace gets large
     if (k && n_checks * k > 8 * c->host_slice && !c->validate) return host_sliced(c, g1, g2, inf1, inf2, n_checks, k, nullptr, ok, all_ok);
     Staged st = {nullptr, nullptr, nullptr, nullptr};
-    if (k && (rc = stage_pairs(c, g1, g2, inf1, inf2, n_checks * k, &st))) return rc;
-    if ((rc = ensure(c, 6, n_checks))) return rc;
-    if ((rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, n_checks, k, nullptr, (uint8_t*)c->buf[6], c->d_flag + 1, c->stream))) return rc;
-    if (ok) HIPCHK(c, hipMemcpyAsync(ok, c->buf[6], n_checks, hipMemcpyDeviceToHost, c->stream));
-    int flag = 1;
-    HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (all_ok) *all_ok = flag;
-    return ZKP_OK;
+    if (k && (rc = stage_pairs(io, g1, g2, inf1, inf2, n_checks * k, &st))) return rc;
+    void* dok = io.out(6, ok, n_checks);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    if ((rc = io.status()) || (rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, n_checks, k, nullptr, (uint8_t*)dok, c->d_flag + 1, c->stream))) return rc;
+    return io.finish();
 }
 static int valid_host(zkp_ctx* c, int which, const uint64_t* pts, const uint8_t* inf, size_t n, uint8_t* status) {
-    if (!c || (n && (!pts || !status))) return ZKP_ERR_ARG;
+    if (!c || too_many(n) || (n && (!pts || !status))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    size_t sz = which == 1 ? 96 : 192;
-    if ((rc = ensure(c, 0, n * sz)) || (rc = ensure(c, 6, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], pts, n * sz, hipMemcpyHostToDevice, c->stream));
-    const uint8_t* di = nullptr;
-    if (inf) {
-        if ((rc = ensure(c, 2, n))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->buf[2], inf, n, hipMemcpyHostToDevice, c->stream));
-        di = (const uint8_t*)c->buf[2];
-    }
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n * sz / 48))) return rc;
-    rc = which == 1 ? zkp_g1_is_valid_batch_dev(c, c->buf[0], di, n, c->buf[6], c->stream)
-                    : zkp_g2_is_valid_batch_dev(c, c->buf[0], di, n, c->buf[6], c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(status, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    const uint64_t* dp = (const uint64_t*)io.in(0, pts, n * 96 * which);
+    void* dst = io.out(6, status, n);
+    const void* di = io.in(2, inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, dp, n * 2 * which)) || (rc = valid_dev(c, which, dp, di, n, dst, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_g1_is_valid_batch(zkp_ctx* c, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* status) { return valid_host(c, 1, g1, inf, n, status); }
 int zkp_g2_is_valid_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* status) { return valid_host(c, 2, g2, inf, n, status); }
 
+// mul, add and MSM always hand their kernels the infinity-flag buffer (slot 6), whether or not the caller wants the flags
 static int mul_host(zkp_ctx* c, int which, const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf) {
-    size_t w = which == 1 ? 12 : 24;
-    if (!c || (n && (!base || !sc || !out)) || (stride != 0 && stride != w)) return ZKP_ERR_ARG;
+    const size_t w = which == 1 ? 12 : 24;
+    if (!c || too_many(n) || (n && (!base || !sc || !out)) || (stride != 0 && stride != w)) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    size_t nb = stride ? n : 1;
-    if ((rc = ensure(c, 0, nb * w * 8)) || (rc = ensure(c, 1, n * 32)) || (rc = ensure(c, 4, n * w * 8)) || (rc = ensure(c, 6, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], base, nb * w * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[1], sc, n * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], nb * w / 6))) return rc;
-    rc = which == 1 ? zkp_g1_mul_batch_dev(c, c->buf[0], stride, c->buf[1], n, c->buf[4], c->buf[6], c->stream)
-                    : zkp_g2_mul_batch_dev(c, c->buf[0], stride, c->buf[1], n, c->buf[4], c->buf[6], c->stream);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n * w * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_inf) HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    const size_t nb = stride ? n : 1;
+    const uint64_t* db = (const uint64_t*)io.in(0, base, nb * w * 8);
+    const void* ds = io.in(1, sc, n * 32);
+    void* dout = io.out(4, out, n * w * 8);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, db, nb * w / 6)) || (rc = mul_dev(c, which, db, stride, ds, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_g1_mul_batch(zkp_ctx* c, const uint64_t* base, size_t stride, const uint64_t* sc, size_t n, uint64_t* out, uint8_t* out_inf) {
     return mul_host(c, 1, base, stride, sc, n, out, out_inf);
@@ -1421,22 +1428,18 @@ static int add_host(zkp_ctx* c, int which, const uint64_t* a, const uint8_t* ia,
     const size_t w = which == 1 ? 12 : 24;
     if (!c || too_many(n) || (n && (!a || !b || !out))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    if ((rc = ensure(c, 0, n * w * 8)) || (rc = ensure(c, 1, n * w * 8)) || (rc = ensure(c, 4, n * w * 8)) || (rc = ensure(c, 6, n)) ||
-        (ia && (rc = ensure(c, 2, n))) || (ib && (rc = ensure(c, 3, n))))
+    HostIO io(c);
+    const uint64_t* da = (const uint64_t*)io.in(0, a, n * w * 8);
+    const uint64_t* db = (const uint64_t*)io.in(1, b, n * w * 8);
+    void* dout = io.out(4, out, n * w * 8);
+    void* dinf = io.out(6, out_inf, n);
+    const void* dia = io.in(2, ia, n);
+    const void* dib = io.in(3, ib, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, da, n * w / 6)) || (rc = validate_dev(c, db, n * w / 6)) ||
+        (rc = add_dev(c, which, da, dia, db, dib, n, dout, dinf, c->stream)))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], a, n * w * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[1], b, n * w * 8, hipMemcpyHostToDevice, c->stream));
-    if (ia) HIPCHK(c, hipMemcpyAsync(c->buf[2], ia, n, hipMemcpyHostToDevice, c->stream));
-    if (ib) HIPCHK(c, hipMemcpyAsync(c->buf[3], ib, n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n * w / 6)) || (rc = validate_dev(c, (const uint64_t*)c->buf[1], n * w / 6))) return rc;
-    if ((rc = add_dev(c, which, c->buf[0], ia ? c->buf[2] : nullptr, c->buf[1], ib ? c->buf[3] : nullptr, n, c->buf[4], c->buf[6], c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n * w * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_inf) HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    return io.finish();
 }
 int zkp_g1_add_batch(zkp_ctx* c, const uint64_t* a, const uint8_t* inf_a, const uint64_t* b, const uint8_t* inf_b, size_t n, uint64_t* out, uint8_t* out_inf) {
     return add_host(c, 1, a, inf_a, b, inf_b, n, out, out_inf);
@@ -1449,22 +1452,18 @@ static int msm_host(zkp_ctx* c, int which, const uint64_t* pts, const uint8_t* i
     const size_t w = which == 1 ? 12 : 24;
     if (!c || zkp::msm::msm_args_bad(m, n_msm) || (n_msm && (!pts || !sc || !out))) return ZKP_ERR_ARG;
     if (!n_msm) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
     const size_t terms = m * n_msm, np = shared ? m : terms;
-    if ((rc = ensure(c, 0, np * w * 8)) || (rc = ensure(c, 1, terms * 32)) || (rc = ensure(c, 4, n_msm * w * 8)) || (rc = ensure(c, 6, n_msm)) ||
-        (inf && (rc = ensure(c, 2, np))))
+    const uint64_t* dp = (const uint64_t*)io.in(0, pts, np * w * 8);
+    const void* ds = io.in(1, sc, terms * 32);
+    void* dout = io.out(4, out, n_msm * w * 8);
+    void* dinf = io.out(6, out_inf, n_msm);
+    const void* di = io.in(2, inf, np);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, dp, np * w / 6)) ||
+        (rc = msm_dev(c, which, dp, di, ds, m, n_msm, shared, dout, dinf, c->stream, nullptr)))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], pts, np * w * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[1], sc, terms * 32, hipMemcpyHostToDevice, c->stream));
-    if (inf) HIPCHK(c, hipMemcpyAsync(c->buf[2], inf, np, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], np * w / 6))) return rc;
-    if ((rc = msm_dev(c, which, c->buf[0], inf ? c->buf[2] : nullptr, c->buf[1], m, n_msm, shared, c->buf[4], c->buf[6], c->stream, nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n_msm * w * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_inf) HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[6], n_msm, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    return io.finish();
 }
 int zkp_g1_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases, uint64_t* out,
                      uint8_t* out_inf) {
@@ -1474,76 +1473,69 @@ int zkp_g2_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, con
                      uint8_t* out_inf) {
     return msm_host(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf);
 }
-static int codec_host(zkp_ctx* c, bool decode, int nfp, const void* in, const uint8_t* inf_in, size_t n, void* out, uint8_t* out_inf, uint8_t* status) {
-    if (!c || (n && (!in || !out)) || (decode && n && (!out_inf || !status))) return ZKP_ERR_ARG;
+
+// both point codecs, host pointers (only the compressed flavours cap n): slot 0 the input, slot 4 the output, slot 2 the infinity
+// flags (written by a decode, read by an encode), slot 6 the status bytes of a decode
+static int codec_host(zkp_ctx* c, bool compressed, bool decode, int which, const void* in, const uint8_t* inf_in, size_t n, void* out,
+                      uint8_t* out_inf, uint8_t* status) {
+    if (!c || (compressed && too_many(n)) || (n && (!in || !out)) || (decode && n && (!out_inf || !status))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    const size_t nb = n * 48 * nfp;
-    if ((rc = ensure(c, 0, nb)) || (rc = ensure(c, 4, nb)) || (rc = ensure(c, 2, n)) || (rc = ensure(c, 6, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], in, nb, hipMemcpyHostToDevice, c->stream));
-    if (decode) {
-        hipLaunchKernelGGL(k_decode<true>, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint8_t*)c->buf[0], n, nfp, (uint64_t*)c->buf[4],
-                           (uint8_t*)c->buf[2], (uint8_t*)c->buf[6]);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, c->buf[4], nb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[2], n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(status, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        const uint8_t* di = nullptr;
-        if (inf_in) {
-            HIPCHK(c, hipMemcpyAsync(c->buf[2], inf_in, n, hipMemcpyHostToDevice, c->stream));
-            di = (const uint8_t*)c->buf[2];
-        }
-        hipLaunchKernelGGL(k_encode<true>, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint64_t*)c->buf[0], di, n, nfp, (uint8_t*)c->buf[4]);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, c->buf[4], nb, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    HostIO io(c);
+    const size_t nw = n * 96 * which, nb = compressed ? nw / 2 : nw;   // wire-point bytes, encoded bytes
+    const void* din = io.in(0, in, decode ? nb : nw);
+    void* dout = io.out(4, out, decode ? nw : nb);
+    void* dinf = decode ? io.out(2, out_inf, n) : (void*)io.in(2, inf_in, n);
+    void* dst = io.out(6, status, n);
+    int rc;
+    if ((rc = io.status()) || (rc = codec_dev(c, compressed, decode, which, din, dinf, n, dout, dinf, dst, c->stream))) return rc;
+    return io.finish();
 }
 int zkp_g1_decode_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out, uint8_t* out_inf, uint8_t* status) {
-    return codec_host(c, true, 2, bytes, nullptr, n, out, out_inf, status);
+    return codec_host(c, false, true, 1, bytes, nullptr, n, out, out_inf, status);
 }
 int zkp_g2_decode_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out, uint8_t* out_inf, uint8_t* status) {
-    return codec_host(c, true, 4, bytes, nullptr, n, out, out_inf, status);
+    return codec_host(c, false, true, 2, bytes, nullptr, n, out, out_inf, status);
 }
 int zkp_g1_encode_batch(zkp_ctx* c, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* out) {
-    return codec_host(c, false, 2, g1, inf, n, out, nullptr, nullptr);
+    return codec_host(c, false, false, 1, g1, inf, n, out, nullptr, nullptr);
 }
 int zkp_g2_encode_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* out) {
-    return codec_host(c, false, 4, g2, inf, n, out, nullptr, nullptr);
+    return codec_host(c, false, false, 2, g2, inf, n, out, nullptr, nullptr);
+}
+int zkp_g1_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g1, uint8_t* out_inf, uint8_t* status) {
+    return codec_host(c, true, true, 1, bytes, nullptr, n, out_g1, out_inf, status);
+}
+int zkp_g2_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g2, uint8_t* out_inf, uint8_t* status) {
+    return codec_host(c, true, true, 2, bytes, nullptr, n, out_g2, out_inf, status);
+}
+int zkp_g1_compress_batch(zkp_ctx* c, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+    return codec_host(c, true, false, 1, g1, inf, n, out_bytes, nullptr, nullptr);
+}
+int zkp_g2_compress_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
+    return codec_host(c, true, false, 2, g2, inf, n, out_bytes, nullptr, nullptr);
 }
 
+// both byte strings go to one buffer (PC_BYTES); points_check_dev grows the status / ok slots it writes
 static int points_check_host(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1, uint8_t* st2,
                              uint8_t* ok, int* all_ok, bool compressed) {
     if (!c || too_many(n_checks, k) || (n_checks && k && (!g1_bytes || !g2_bytes))) return ZKP_ERR_ARG;
     if (all_ok) *all_ok = 1;
     if (!n_checks) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
     const size_t np = n_checks * k;
     const size_t sz1 = compressed ? 48 : 96, sz2 = 2 * sz1;
-    if ((rc = ensure_pc(c, PC_BYTES, np * (sz1 + sz2) + 8)) || (rc = ensure_pc(c, PC_ST1, np + 8)) || (rc = ensure_pc(c, PC_ST2, np + 8)) ||
-        (rc = ensure_pc(c, PC_OK, n_checks + 8)))
-        return rc;
+    int rc;
+    if ((rc = io.status()) || (rc = ensure_pc(c, PC_BYTES, np * (sz1 + sz2) + 8))) return rc;
     uint8_t* d1 = (uint8_t*)c->pc[PC_BYTES];
     uint8_t* d2 = d1 + np * sz1;
-    if (np) {
-        HIPCHK(c, hipMemcpyAsync(d1, g1_bytes, np * sz1, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d2, g2_bytes, np * sz2, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = points_check_dev(c, d1, d2, n_checks, k, nullptr, nullptr, nullptr, c->d_flag + 1, c->stream, compressed))) return rc;
-    if (st1 && np) HIPCHK(c, hipMemcpyAsync(st1, c->pc[PC_ST1], np, hipMemcpyDeviceToHost, c->stream));
-    if (st2 && np) HIPCHK(c, hipMemcpyAsync(st2, c->pc[PC_ST2], np, hipMemcpyDeviceToHost, c->stream));
-    if (ok) HIPCHK(c, hipMemcpyAsync(ok, c->pc[PC_OK], n_checks, hipMemcpyDeviceToHost, c->stream));
-    int flag = 1;
-    HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (all_ok) *all_ok = flag;
-    return ZKP_OK;
+    io.put(d1, g1_bytes, np * sz1);
+    io.put(d2, g2_bytes, np * sz2);
+    if ((rc = io.status()) || (rc = points_check_dev(c, d1, d2, n_checks, k, nullptr, nullptr, nullptr, c->d_flag + 1, c->stream, compressed))) return rc;
+    io.get(st1, c->pc[PC_ST1], np);
+    io.get(st2, c->pc[PC_ST2], np);
+    io.get(ok, c->pc[PC_OK], n_checks);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    return io.finish();
 }
 int zkp_points_check_batch(zkp_ctx* c, const uint8_t* g1_bytes, const uint8_t* g2_bytes, size_t n_checks, size_t k, uint8_t* st1, uint8_t* st2,
                            uint8_t* ok, int* all_ok) {
@@ -1554,64 +1546,20 @@ int zkp_points_check_compressed_batch(zkp_ctx* c, const uint8_t* g1_bytes, const
     return points_check_host(c, g1_bytes, g2_bytes, n_checks, k, st1, st2, ok, all_ok, true);
 }
 
-// compressed point codec, host pointers: which = 1 (48 B <-> 12 u64) or 2 (96 B <-> 24 u64)
-static int cmp_codec_host(zkp_ctx* c, bool decompress, int which, const void* in, const uint8_t* inf_in, size_t n, void* out, uint8_t* out_inf,
-                          uint8_t* status) {
-    if (!c || too_many(n) || (n && (!in || !out)) || (decompress && n && (!out_inf || !status))) return ZKP_ERR_ARG;
-    if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    const size_t nb = n * 48 * which, nw = n * 96 * which;   // compressed bytes, wire-point bytes
-    const size_t in_sz = decompress ? nb : nw, out_sz = decompress ? nw : nb;
-    if ((rc = ensure(c, 0, in_sz)) || (rc = ensure(c, 4, out_sz)) || (rc = ensure(c, 2, n)) || (rc = ensure(c, 6, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], in, in_sz, hipMemcpyHostToDevice, c->stream));
-    if (decompress) {
-        if ((rc = coop_rc(c, "decompress", zkp_cmp::decompress(which, c->buf[0], n, c->buf[4], c->buf[2], c->buf[6], c->stream)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(out_inf, c->buf[2], n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(status, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        const void* di = nullptr;
-        if (inf_in) {
-            HIPCHK(c, hipMemcpyAsync(c->buf[2], inf_in, n, hipMemcpyHostToDevice, c->stream));
-            di = c->buf[2];
-        }
-        if ((rc = coop_rc(c, "compress", zkp_cmp::compress(which, c->buf[0], di, n, c->buf[4], c->stream)))) return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], out_sz, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
-}
-int zkp_g1_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g1, uint8_t* out_inf, uint8_t* status) {
-    return cmp_codec_host(c, true, 1, bytes, nullptr, n, out_g1, out_inf, status);
-}
-int zkp_g2_decompress_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out_g2, uint8_t* out_inf, uint8_t* status) {
-    return cmp_codec_host(c, true, 2, bytes, nullptr, n, out_g2, out_inf, status);
-}
-int zkp_g1_compress_batch(zkp_ctx* c, const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
-    return cmp_codec_host(c, false, 1, g1, inf, n, out_bytes, nullptr, nullptr);
-}
-int zkp_g2_compress_batch(zkp_ctx* c, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* out_bytes) {
-    return cmp_codec_host(c, false, 2, g2, inf, n, out_bytes, nullptr, nullptr);
-}
-
 // square-root hooks (host pointers, like zkp_fp_op_batch): which = 1 Fp::sqrt, 2 Fp2::sqrt
 static int sqrt_host(zkp_ctx* c, int which, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) {
     if (!c || n > 0x7fffffffu || (n && (!a || !out || !is_square))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
     const size_t bytes = n * 48 * which;
-    if ((rc = ensure(c, 0, bytes)) || (rc = ensure(c, 4, bytes)) || (rc = ensure(c, 6, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], a, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n * which))) return rc;
-    if ((rc = coop_rc(c, "sqrt", zkp_cmp::sqrt_ref(which, (const uint64_t*)c->buf[0], n, (uint64_t*)c->buf[4], (uint8_t*)c->buf[6], c->stream))))
+    const uint64_t* da = (const uint64_t*)io.in(0, a, bytes);
+    void* dout = io.out(4, out, bytes);
+    void* dsq = io.out(6, is_square, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, da, n * which)) ||
+        (rc = coop_rc(c, "sqrt", zkp_cmp::sqrt_ref(which, da, n, (uint64_t*)dout, (uint8_t*)dsq, c->stream))))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(is_square, c->buf[6], n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    return io.finish();
 }
 int zkp_fp_sqrt_batch(zkp_ctx* c, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) { return sqrt_host(c, 1, a, n, out, is_square); }
 int zkp_fp2_sqrt_batch(zkp_ctx* c, const uint64_t* a, size_t n, uint64_t* out, uint8_t* is_square) { return sqrt_host(c, 2, a, n, out, is_square); }
@@ -1621,25 +1569,20 @@ int zkp_fp_op_batch(zkp_ctx* c, int op, const uint64_t* a, const uint64_t* b, si
     const bool unary = base == ZKP_FP_NEG || base == ZKP_FP_SQUARE || base == ZKP_FP_INVERT;
     if (!c || op < 0 || base > ZKP_FP_INVERT || n > 0x7fffffffu || (n && (!a || !out || (!unary && !b)))) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
-    if ((rc = ensure(c, 0, n * 48)) || (rc = ensure(c, 1, n * 48)) || (rc = ensure(c, 4, n * 48))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->buf[0], a, n * 48, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, (const uint64_t*)c->buf[0], n))) return rc;
-    if (!unary) {
-        HIPCHK(c, hipMemcpyAsync(c->buf[1], b, n * 48, hipMemcpyHostToDevice, c->stream));
-        if ((rc = validate_dev(c, (const uint64_t*)c->buf[1], n))) return rc;
-    }
+    HostIO io(c);
+    const uint64_t* da = (const uint64_t*)io.in(0, a, n * 48);
+    uint64_t* db = (uint64_t*)io.slot(1, n * 48);   // the kernels take it whether or not the operation reads it
+    io.put(db, unary ? nullptr : b, n * 48);
+    uint64_t* dout = (uint64_t*)io.out(4, out, n * 48);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, da, n)) || (!unary && (rc = validate_dev(c, db, n)))) return rc;
     if (op & ZKP_FP_CORE28) {   // the 14 x 28-bit carry-free core of the cooperative family
-        HIPCHK(c, zkp::coop_fp28_op(base, (const uint64_t*)c->buf[0], (const uint64_t*)c->buf[1], n, (uint64_t*)c->buf[4], c->stream));
+        HIPCHK(c, zkp::coop_fp28_op(base, da, db, n, dout, c->stream));
     } else {
-        hipLaunchKernelGGL(k_fp_op, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, base, (const uint64_t*)c->buf[0], (const uint64_t*)c->buf[1], n, (uint64_t*)c->buf[4]);
+        hipLaunchKernelGGL(k_fp_op, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, base, da, (const uint64_t*)db, n, dout);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    return io.finish();
 }
 
 int zkp_tower_op_batch(zkp_ctx* c, int op, const uint64_t* a, const uint64_t* b, size_t n, uint32_t repeat, uint64_t* out) {
@@ -1649,26 +1592,24 @@ int zkp_tower_op_batch(zkp_ctx* c, int op, const uint64_t* a, const uint64_t* b,
     if (op == ZKP_TOWER_FP12_CYCLOTOMIC_DECOMPRESS && !zkp::coop_selected(&c->coop, c->kernel)) return ZKP_ERR_ARG;
     if (op == ZKP_TOWER_FP12_CYCLOTOMIC_POW2K && (repeat < 1 || repeat > 64)) return ZKP_ERR_ARG;
     if (!n) return ZKP_OK;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall drain(c);
+    HostIO io(c);
     // one buffer: the a records, then the b records (the step programs read record check + n as their second operand)
-    if ((rc = ensure(c, 5, 2 * n * 576)) || (rc = ensure(c, 4, n * 576))) return rc;
-    uint64_t* d_a = (uint64_t*)c->buf[5];
+    uint64_t* d_a = (uint64_t*)io.slot(5, 2 * n * 576);
+    uint64_t* dout = (uint64_t*)io.out(4, out, n * 576);
+    int rc;
+    if ((rc = io.status())) return rc;
     uint64_t* d_b = d_a + 72 * n;
-    HIPCHK(c, hipMemcpyAsync(d_a, a, n * 576, hipMemcpyHostToDevice, c->stream));
-    if (binary) HIPCHK(c, hipMemcpyAsync(d_b, b, n * 576, hipMemcpyHostToDevice, c->stream));
-    if ((rc = validate_dev(c, d_a, (binary ? 2 : 1) * n * 12))) return rc;
+    io.put(d_a, a, n * 576);
+    io.put(d_b, binary ? b : nullptr, n * 576);
+    if ((rc = io.status()) || (rc = validate_dev(c, d_a, (binary ? 2 : 1) * n * 12))) return rc;
     if (zkp::coop_selected(&c->coop, c->kernel)) {
-        const hipError_t e = zkp::coop_tower_op(&c->coop, op, d_a, n, repeat, (uint64_t*)c->buf[4], c->stream);
+        const hipError_t e = zkp::coop_tower_op(&c->coop, op, d_a, n, repeat, dout, c->stream);
         if (e != hipSuccess) { c->err = std::string("coop_tower_op: ") + hipGetErrorString(e); return ZKP_ERR_HIP; }
     } else {
-        hipLaunchKernelGGL(k_tower_op, dim3(grid_for(n, TPB)), dim3(TPB), 0, c->stream, op, d_a, binary ? d_b : nullptr, n, repeat, (uint64_t*)c->buf[4]);
+        hipLaunchKernelGGL(k_tower_op, dim3(grid_for(n, TPB)), dim3(TPB), 0, c->stream, op, d_a, binary ? d_b : nullptr, n, repeat, dout);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(out, c->buf[4], n * 576, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZKP_OK;
+    return io.finish();
 }
 
 // ---------------------------------------------------------------- several GPUs behind one call
@@ -1711,17 +1652,16 @@ static int multi_impl(zkp_ctx* const* ctxs, int n_ctx, const uint64_t* g1, const
         if (!m) continue;
         if ((rc = bind(c))) break;
         if (c->ws_busy) (void)hipStreamWaitEvent(c->stream, c->ws_busy, 0);
+        Staging io(c);   // not a HostIO: the contexts are drained together below
         Staged st = {nullptr, nullptr, nullptr, nullptr};
-        if (k && (rc = stage_pairs(c, g1 + 12 * p0, g2 + 24 * p0, inf1 ? inf1 + p0 : nullptr, inf2 ? inf2 + p0 : nullptr, m * k, &st))) break;
-        if ((out_gt && (rc = ensure(c, 4, m * 576))) || (rc = ensure(c, 6, m))) break;
-        if ((rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, m, k, out_gt ? (uint64_t*)c->buf[4] : nullptr, (uint8_t*)c->buf[6], c->d_flag + 1, c->stream)))
+        if (k && (rc = stage_pairs(io, g1 + 12 * p0, g2 + 24 * p0, inf1 ? inf1 + p0 : nullptr, inf2 ? inf2 + p0 : nullptr, m * k, &st))) break;
+        void* dgt = out_gt ? io.out(4, out_gt + 72 * lo, m * 576) : nullptr;
+        void* dok = io.out(6, ok ? ok + lo : nullptr, m);
+        io.get(&flags[j], c->d_flag + 1, sizeof(int));
+        if ((rc = io.status()) || (rc = pairing_dev(c, st.g1, st.g2, st.i1, st.i2, m, k, (uint64_t*)dgt, (uint8_t*)dok, c->d_flag + 1, c->stream)) ||
+            (rc = io.send()))
             break;
-        hipError_t e = hipSuccess;
-        if (out_gt) e = hipMemcpyAsync(out_gt + 72 * lo, c->buf[4], m * 576, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && ok) e = hipMemcpyAsync(ok + lo, c->buf[6], m, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&flags[j], c->d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ws_busy, c->stream);
-        if (e != hipSuccess) { c->err = std::string("zkp_pairing_*_multi: ") + hipGetErrorString(e); rc = ZKP_ERR_HIP; }
+        if (hipEventRecord(c->ws_busy, c->stream) != hipSuccess) { c->err = "zkp_pairing_*_multi: hipEventRecord failed"; rc = ZKP_ERR_HIP; }
     }
     // whatever happened, nothing may still be copying from or into the caller's arrays when the call returns
     for (int j = 0; j < used; j++) {
@@ -1835,9 +1775,9 @@ static int reduce_after_local(zkp_ctx* c, int rc_local, int* d_all_ok, hipStream
 static int host_flag_allreduce(zkp_ctx* c, int rc_local, int local, int* all_ok) {
     if (rc_local) local = 0;
     const std::string first = c->err;
-    int rc = bind(c);
+    HostIO io(c);
+    int rc = io.status();
     if (rc) return rc_local ? rc_local : rc;
-    HostCall drain(c);
     // the flag reaches the device by a kernel argument, not by a copy that could fail before the collective: whatever happened locally,
     // this rank enters the all-reduce its peers are waiting in
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, c->stream, c->d_flag + 1, local ? 1 : 0);
@@ -1907,9 +1847,9 @@ int zkp_pairing_product_check_allgather(zkp_ctx* c, const uint64_t* g1, const ui
     if (!c->comm) { c->err = "no communicator: call zkp_comm_init_rank first"; return ZKP_ERR_COMM; }
     const bool bad_args = (n && (!g1 || !g2)) || n > 0x7fffffffu;
     if (bad_args) { n = 0; c->err = "zkp_pairing_product_check_allgather: null points / too many pairs"; }
-    int rc = bind(c);
+    HostIO io(c);
+    int rc = io.status();
     if (rc) return rc;
-    HostCall drain(c);
     const size_t R = (size_t)c->comm_nranks;
     // this rank's Miller product -> the communicator's record 0 (the identity for an empty block), gathered into records 1..R.  A rank
     // whose own part fails - bad arguments, staging, an allocation that runs out of memory, a launch error - still joins the collective,
@@ -1922,7 +1862,7 @@ int zkp_pairing_product_check_allgather(zkp_ctx* c, const uint64_t* g1, const ui
     uint64_t* const gt = c->comm_buf + 72 * (R + 2);
     Staged st = {nullptr, nullptr, nullptr, nullptr};
     int rc_local = bad_args ? ZKP_ERR_ARG : ZKP_OK;
-    if (!rc_local && n) rc_local = stage_pairs(c, g1, g2, inf1, inf2, n, &st);
+    if (!rc_local && n) rc_local = stage_pairs(io, g1, g2, inf1, inf2, n, &st);
     if (!rc_local) rc_local = miller_product_dev(c, st.g1, st.g2, st.i1, st.i2, n, mine, c->stream);
     const std::string first = c->err;
     if (rc_local) {
@@ -1985,18 +1925,17 @@ int zkp_clock_probe_dev(zkp_ctx* c, void* stream, unsigned spin_us, void* d_out,
 
 int zkp_time_coop_step(zkp_ctx* c, int which, size_t n, float* ms) {
     if (!c || !ms) return ZKP_ERR_ARG;
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall hc(c);   // the timing programs reuse the workspace of pipeline 0: wait for *_dev calls queued on other streams, drain on exit
+    HostIO io(c);   // the timing programs reuse the workspace of pipeline 0: wait for *_dev calls queued on other streams, drain on exit
+    if (int rc = io.status()) return rc;
     HIPCHK(c, zkp::coop_time_prog(&c->coop, which, n, c->stream, c->ev0, c->ev1, ms));
     return ZKP_OK;
 }
 
 int zkp_time_pairing_dev(zkp_ctx* c, const void* g1, const void* g2, size_t n, void* out, int reps, float* avg_ms) {
     if (!c || !g1 || !g2 || !out || reps <= 0 || !avg_ms) return ZKP_ERR_ARG;
-    int rc = bind(c);
+    HostIO io(c);   // same workspace discipline as every host-synchronous entry point
+    int rc = io.status();
     if (rc) return rc;
-    HostCall hc(c);   // same workspace discipline as every host-synchronous entry point
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (int r = 0; r < reps; r++)
         if ((rc = pairing_dev(c, (const uint64_t*)g1, (const uint64_t*)g2, nullptr, nullptr, n, 1, (uint64_t*)out, nullptr, nullptr, c->stream))) return rc;
@@ -2012,9 +1951,8 @@ int zkp_time_pairing_dev(zkp_ctx* c, const void* g1, const void* g2, size_t n, v
 int zkp_profile_pairing_dev(zkp_ctx* c, const void* g1, const void* g2, size_t n, void* out, float* ms, int* launches) {
     if (!c || !g1 || !g2 || !out || !ms || !launches || !n || too_many(n)) return ZKP_ERR_ARG;
     if (!zkp::coop_selected(&c->coop, c->kernel)) { c->err = "zkp_profile_pairing_dev: the cooperative kernel family is not selected"; return ZKP_ERR_ARG; }
-    int rc = bind(c);
-    if (rc) return rc;
-    HostCall hc(c);
+    HostIO io(c);
+    if (int rc = io.status()) return rc;
     return coop_rc(c, "coop_profile_pairing", zkp::coop_profile_pairing(&c->coop, (const uint64_t*)g1, (const uint64_t*)g2, n, (uint64_t*)out, ms, launches, c->stream));
 }
 
