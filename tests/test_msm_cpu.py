@@ -1,6 +1,7 @@
 """CPU gate for group addition and the bucket MSM: the new entry points are exported and bound, a Python model of the signed-digit
 decomposition (k_msm_digits) gives back every scalar exactly, the MSM planner (csrc/zkp_msm_plan.hpp) keeps every per-launch count in
-32 bits at the ABI maxima under ASan and UBSan, and the new kernels neither spill nor use scratch in the built code object."""
+32 bits at the ABI maxima under ASan and UBSan, the GPU tests' shape table (tests/msm_shapes.py) reaches the plans it claims, and the
+new kernels neither spill nor use scratch in the built code object."""
 import os
 import re
 import subprocess
@@ -137,6 +138,64 @@ def test_msm_planner_under_asan_and_ubsan_at_the_abi_maxima(tmp_path):
     assert "msm plan_check ok" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
     with open(os.path.join(ROOT, "zkvm_pairings_amd", "csrc", "zkp_msm.hip")) as f:
         assert '#include "zkp_msm_plan.hpp"' in f.read()
+
+
+SHAPE_PLAN = r"""
+#include <cstdio>
+#include "zkp_msm_plan.hpp"
+using namespace zkp::msm;
+int main() {
+    size_t m, n;
+    int sh;
+    while (std::scanf("%zu %zu %d", &m, &n, &sh) == 3) {
+        Plan p;
+        const int ok = make_plan(m, n, sh != 0, &p) ? 1 : 0;
+        std::printf("%d %u %u %u %u %d %u %u %u\n", ok, p.c, p.passes, p.split, p.chunk, p.levels, p.segs, m > 1 ? choose_c(m - 1) : 0u,
+                    m < MAX_TERMS ? choose_c(m + 1) : 0u);
+    }
+    return 0;
+}
+"""
+
+
+def test_msm_shape_table_reaches_the_plans_it_claims(tmp_path):
+    """tests/msm_shapes.py lists the shapes the GPU MSM tests run; make_plan must give each row exactly its fields, and the rows
+    together must cover every window width for G1 and G2, both ends of every c range for G1, passes >= 3 with a partial last pass
+    (shared and not), split 1 with chunk > 1, and the largest admitted call"""
+    import msm_shapes as ms
+    src = tmp_path / "msm_shape_plan.cpp"
+    src.write_text(SHAPE_PLAN)
+    exe = str(tmp_path / "msm_shape_plan")
+    cc = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "zkvm_pairings_amd", "csrc"), "-o", exe,
+                         str(src)], capture_output=True, text=True, timeout=600)
+    assert cc.returncode == 0, cc.stdout[-3000:] + cc.stderr[-3000:]
+    rows = ms.ALL
+    feed = "".join("%d %d %d\n" % (s.m, s.n_msm, int(s.shared)) for s in rows)
+    out = subprocess.run([exe], input=feed, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.split("\n")[:len(rows)]
+    assert len(lines) == len(rows)
+    ends = {}
+    for s, line in zip(rows, lines):
+        ok, c, passes, split, chunk, levels, segs, c_prev, c_next = map(int, line.split())
+        assert ok == 1 and s.m * s.n_msm <= ms.MAX_TERMS, s
+        assert (c, passes, split, chunk, levels, segs) == (s.c, s.passes, s.split, s.chunk, s.levels, s.segs), (s, line)
+        if s.passes > 1:
+            assert s.n_msm % segs != 0, s                               # the last pass is partial
+        if 1 in s.groups:
+            ends.setdefault(c, set())
+            if c_prev != c:
+                ends[c].add("low")
+            if c_next != c:
+                ends[c].add("high")
+    for which in (1, 2):
+        assert {s.c for s in rows if which in s.groups} == set(range(2, 17)), which
+    assert all(ends.get(c) == {"low", "high"} for c in range(2, 17)), ends
+    multi = [s for s in rows if s.passes >= 3]
+    assert {s.shared for s in multi} == {False, True}
+    assert any(s.split == 1 and s.chunk > 1 for s in rows)
+    assert any(s.m * s.n_msm == ms.MAX_TERMS and 1 in s.groups for s in rows)
+    assert {s.split for s in rows if s.chunk > 1} >= {1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024}
 
 
 def _kernels():
