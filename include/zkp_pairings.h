@@ -185,6 +185,45 @@ int zkp_g1_msm_batch(zkp_ctx* ctx, const uint64_t* points, const uint8_t* inf, c
                      uint64_t* out, uint8_t* out_inf);
 int zkp_g2_msm_batch(zkp_ctx* ctx, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases,
                      uint64_t* out, uint8_t* out_inf);
+/* ---- batch verification by random linear combination (RLC) ------------------------------------------------------------------------
+ * zkp_g1_mul_endo_batch: out[i] = [a_i] P_i + [b_i] (beta x_i, -y_i), ab = 2 u64 per point (a_i, b_i), on the 28-bit core whatever
+ * zkp_set_kernel says; inf / out_inf may be NULL; an infinite result is (0, 1) with out_inf = 1.  For P in G1 (beta x, -y) = [z^2] P with
+ * z = 0xd201000000010000, so the result equals [a_i + b_i z^2] P_i: a 128-bit multiple for 64 doublings.  Outside G1 it is still exactly
+ * [a] P + [b] (beta x, -y).
+ * zkp_pairing_check_batch_rlc: n_checks independent checks verified as ONE,
+ *     *all_ok = ( prod_c ( prod_j e(P_cj, Q_cj) )^(r_c) == Gt::identity() )  AND every point valid AND no (a_c, b_c) = (0, 0),
+ * r_c = a_c + b_c z^2 from rand[2c], rand[2c + 1] (draw them uniformly at random, per call, from a cryptographic source: a batch of
+ * checks that do not all hold then passes with probability at most 2^-128 plus the chance of guessing rand).  Check c is the product of
+ * its k free pairs (g1 / g2 / inf1 / inf2 laid out as zkp_pairing_check_batch), its s2 pairs (col_g1[c][j], fixed_g2[j]) and its s1 pairs
+ * (fixed_g1[j], col_g2[c][j]) - col_* are n_checks x s rows (one row per check), fixed_* hold s points; every inf* may be NULL.  Expanded
+ * into k + s1 + s2 pairs per check, it is exactly what zkp_pairing_check_batch tests: *all_ok = 1 implies (with the probability above)
+ * that every check holds, and a batch of valid checks always gives 1.  Cost: N k endomorphism scalings + one Miller product over them, one
+ * G1 MSM of n_checks terms per fixed-G2 column, one G2 MSM per fixed-G1 column, one Miller product over the s1 + s2 column pairs, ONE
+ * final exponentiation.  RLC is sound for prime-order points only: unless flags has ZKP_RLC_POINTS_CHECKED every input point (fixed ones
+ * included) goes through is_valid first.  Invalid points and zero scalars give *all_ok = 0, not an error.  n_checks == 0 gives 1; k == 0
+ * needs s1 + s2 > 0.  ZKP_ERR_ARG: null pointers with nonzero counts, n_checks * k beyond zkp_pairing_check_batch's limits (n <= 2^31 - 1,
+ * k <= 65535, n k <= 2^31 - 1), s1 or s2 > 65535, n_checks > 2^24 with any column, flags other than ZKP_RLC_POINTS_CHECKED.  Validation
+ * mode covers every coordinate array.  The _dev flavour is asynchronous (no host read-back) and capturable into a hipGraph once the
+ * context's workspaces have reached the call's size; d_all_ok (one int32) is required.
+ * Workspace (grow-only, layout zkvm_pairings_amd/csrc/zkp_rlc_plan.hpp) per check: 97 B per free pair (scaled point + flag), 97 B per
+ * fixed-G2 column and 193 B per fixed-G1 column (the column-major copy), 32 B of scalar per column (at most one copy per column), 2 B
+ * per free pair and 1 B per column point of status without ZKP_RLC_POINTS_CHECKED; plus the MSM workspace of n_checks terms per column
+ * (about 1.0 KB per G1 term and 1.6 KB per G2 term, see above) and, as for zkp_pairing_check_batch, the Miller loop's own workspace. */
+typedef struct {
+    size_t n_checks;
+    size_t k;  const void *g1, *g2, *inf1, *inf2;                         /* k free pairs per check, laid out as zkp_pairing_check_batch */
+    size_t s2; const void *col_g1, *col_inf1, *fixed_g2, *fixed_inf2;     /* s2 columns: one G1 per check (n_checks x s2, row per check), one fixed G2 each */
+    size_t s1; const void *col_g2, *col_inf2, *fixed_g1, *fixed_inf1;     /* s1 columns: one G2 per check, one fixed G1 each */
+} zkp_rlc_batch;
+#define ZKP_RLC_POINTS_CHECKED 1   /* flags: skip the subgroup checks (caller guarantees every point is valid) */
+int zkp_g1_mul_endo_batch(zkp_ctx* ctx, const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint64_t* out, uint8_t* out_inf);
+int zkp_g1_mul_endo_batch_dev(zkp_ctx* ctx, const void* d_base, const void* d_inf, const void* d_ab, size_t n, void* d_out, void* d_out_inf,
+                              void* stream);
+/* host flavour: the batch's pointers are host arrays */
+int zkp_pairing_check_batch_rlc(zkp_ctx* ctx, const zkp_rlc_batch* b, const uint64_t* rand /* 2 u64 per check */, int flags, int* all_ok);
+/* device flavour: the batch's pointers, d_rand and d_all_ok are device pointers (the descriptor itself is a host struct) */
+int zkp_pairing_check_batch_rlc_dev(zkp_ctx* ctx, const zkp_rlc_batch* b, const void* d_rand, int flags, void* d_all_ok, void* stream);
+
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).
  * G1: x(48) | y(48) = 96 bytes; G2: x.c1 | x.c0 | y.c1 | y.c0 = 192 bytes (c1 first, the usual BLS12-381

@@ -29,6 +29,31 @@ pub const ZKP_POINT_MALFORMED: u8 = 2;
 pub const ZKP_POINT_NOT_ON_CURVE: u8 = 3;
 pub const ZKP_POINT_NOT_IN_SUBGROUP: u8 = 4;
 
+/// the shape of a batch for `zkp_pairing_check_batch_rlc[_dev]` (include/zkp_pairings.h `zkp_rlc_batch`, same field order): k free pairs per
+/// check, s2 columns (one G1 per check, n_checks x s2 rows, one fixed G2 each), s1 columns (one G2 per check, one fixed G1 each)
+#[repr(C)]
+#[allow(non_camel_case_types)]
+pub struct zkp_rlc_batch {
+    pub n_checks: usize,
+    pub k: usize,
+    pub g1: *const c_void,
+    pub g2: *const c_void,
+    pub inf1: *const c_void,
+    pub inf2: *const c_void,
+    pub s2: usize,
+    pub col_g1: *const c_void,
+    pub col_inf1: *const c_void,
+    pub fixed_g2: *const c_void,
+    pub fixed_inf2: *const c_void,
+    pub s1: usize,
+    pub col_g2: *const c_void,
+    pub col_inf2: *const c_void,
+    pub fixed_g1: *const c_void,
+    pub fixed_inf1: *const c_void,
+}
+/// flags of `zkp_pairing_check_batch_rlc`: skip the subgroup checks (the caller guarantees every point is valid)
+pub const ZKP_RLC_POINTS_CHECKED: c_int = 1;
+
 /// zkp_fp_op: 0 and 1 are the zkVM precompile's op numbers (reference src/fp.rs:376,443)
 pub const ZKP_FP_MUL: c_int = 0;
 pub const ZKP_FP_ADD: c_int = 1;
@@ -148,6 +173,14 @@ extern "C" {
     pub fn zkp_msm_profile_dev(ctx: *mut ZkpCtx, which: c_int, d_points: *const c_void, d_inf: *const c_void, d_scalars: *const c_void, m: usize,
                                n_msm: usize, shared_bases: c_int, d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void,
                                phase_ms: *mut f32) -> c_int;
+    // batch verification by random linear combination: [a] P + [b] (beta x, -y) (= [a + b z^2] P in G1), and the one-exponentiation check
+    pub fn zkp_g1_mul_endo_batch(ctx: *mut ZkpCtx, base: *const u64, inf: *const u8, ab: *const u64, n: usize, out: *mut u64,
+                                 out_inf: *mut u8) -> c_int;
+    pub fn zkp_g1_mul_endo_batch_dev(ctx: *mut ZkpCtx, d_base: *const c_void, d_inf: *const c_void, d_ab: *const c_void, n: usize,
+                                     d_out: *mut c_void, d_out_inf: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_pairing_check_batch_rlc(ctx: *mut ZkpCtx, b: *const zkp_rlc_batch, rand: *const u64, flags: c_int, all_ok: *mut c_int) -> c_int;
+    pub fn zkp_pairing_check_batch_rlc_dev(ctx: *mut ZkpCtx, b: *const zkp_rlc_batch, d_rand: *const c_void, flags: c_int, d_all_ok: *mut c_void,
+                                           stream: *mut c_void) -> c_int;
     pub fn zkp_g1_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g1: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g2_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g2: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g1_compress_batch(ctx: *mut ZkpCtx, g1: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;

@@ -15,6 +15,17 @@ c_vp = ctypes.c_void_p
 c_sz = ctypes.c_size_t
 c_int = ctypes.c_int
 
+RLC_POINTS_CHECKED = 1   # ZKP_RLC_POINTS_CHECKED
+
+
+class RlcBatch(ctypes.Structure):
+    """zkp_rlc_batch: the shape of a batch for zkp_pairing_check_batch_rlc[_dev] (field order of include/zkp_pairings.h)"""
+    _fields_ = [("n_checks", c_sz),
+                ("k", c_sz), ("g1", c_vp), ("g2", c_vp), ("inf1", c_vp), ("inf2", c_vp),
+                ("s2", c_sz), ("col_g1", c_vp), ("col_inf1", c_vp), ("fixed_g2", c_vp), ("fixed_inf2", c_vp),
+                ("s1", c_sz), ("col_g2", c_vp), ("col_inf2", c_vp), ("fixed_g1", c_vp), ("fixed_inf1", c_vp)]
+
+
 # name -> (restype, argtypes); MUST list every symbol include/zkp_pairings.h declares
 SIGNATURES = {
     "zkp_abi_version": (c_int, []),
@@ -72,6 +83,10 @@ SIGNATURES = {
     "zkp_g1_msm_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
     "zkp_g2_msm_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp]),
     "zkp_msm_profile_dev": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_sz, c_int, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "zkp_g1_mul_endo_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_mul_endo_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_pairing_check_batch_rlc": (c_int, [c_vp, ctypes.POINTER(RlcBatch), c_vp, c_int, ctypes.POINTER(c_int)]),
+    "zkp_pairing_check_batch_rlc_dev": (c_int, [c_vp, ctypes.POINTER(RlcBatch), c_vp, c_int, c_vp, c_vp]),
     "zkp_g1_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g2_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g1_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),

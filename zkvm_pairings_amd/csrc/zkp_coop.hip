@@ -2426,6 +2426,52 @@ __global__ void __launch_bounds__(64, 2) k_add28(const uint64_t* a, const uint8_
     }
 }
 
+// out[i] = [a] P + [b] phi'(P), phi'(P) = (beta x, -y), a and b 64-bit: for P in G1, phi'(P) = [z^2] P (the relation k_g1_valid28
+// tests), so out[i] = [a + b z^2] P - a 128-bit scalar multiplication in 64 doublings (zkp_g1_mul_endo_batch, the batch check's scaling).
+// One lane per point; points i share the (a, b) of ab[2 (i / per)].  Joint double-and-add over the 64 bit pairs with the table P, phi'(P),
+// T = P + phi'(P) in LDS: every lane adds ITS entry through one full addition (jac_add, every exceptional case; T is Jacobian, and infinite
+// when phi'(P) = -P), so a wavefront runs one addition per bit pair whatever its lanes' bits.  phi'(P) is not stored: its x costs one
+// product at the load (five LDS slots, 20 KB: two workgroups per SIMD as the launch bounds ask).
+__global__ void __launch_bounds__(64, 2) k_g1_mul_endo28(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, uint32_t n, uint32_t per,
+                                                         uint64_t* out, uint8_t* out_inf) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[5 * 4 * 64];   // 0 x, 1 y of P; 2..4 T (Jacobian)
+    const uint32_t g = i / per;
+    const uint64_t a = ab[2 * (size_t)g], b = ab[2 * (size_t)g + 1];
+    JacP p;
+    fp28_from_wire(p.x, base + 12 * (size_t)i);
+    fp28_from_wire(p.y, base + 12 * (size_t)i + 6);
+    valid_park(park, lane, 0, p.x);
+    valid_park(park, lane, 1, p.y);
+    p.z = f.one();
+    jac_madd(f, p, [&](int v) -> Fp28 { return v == 0 ? f.mul(valid_unpark(park, lane, 0), f_const(K28_BETA)) : c_neg(valid_unpark(park, lane, 1)); });
+    jac_park(park, lane, 2, p);
+    jac_set_inf(f, p);
+    if (!(inf && inf[i])) {
+#pragma unroll 1
+        for (int bit = 63; bit >= 0; bit--) {
+            jac_dbl(f, p);
+            const int sel = (int)((a >> bit) & 1) | (int)((b >> bit) & 1) << 1;   // 1: P, 2: phi'(P), 3: T
+            if (sel)
+                jac_add(f, p, [&](int v) -> Fp28 {
+                    if (sel == 3) return valid_unpark(park, lane, 2 + v);
+                    if (v == 2) return f.one();
+                    const Fp28 q = valid_unpark(park, lane, v);
+                    if (sel == 1) return q;
+                    return v == 0 ? f.mul(q, f_const(K28_BETA)) : c_neg(q);
+                });
+        }
+    }
+    Fp28 ax, ay;
+    const bool pinf = jac_affine(f, p, ax, ay);
+    fp28_to_wire(out + 12 * (size_t)i, ax);
+    fp28_to_wire(out + 12 * (size_t)i + 6, ay);
+    if (out_inf) out_inf[i] = pinf ? 1 : 0;
+}
+
 // ---- MSM 1: n wire Fp elements -> Montgomery records (the points' coordinates, converted once per pass)
 __global__ void __launch_bounds__(256) k_msm_points(const uint64_t* w, uint32_t n_fp, int4* rec) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -3398,6 +3444,13 @@ hipError_t coop_add(int which, const uint64_t* a, const uint8_t* ia, const uint6
         hipLaunchKernelGGL(k_add28<1>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a, ia, b, ib, (uint32_t)n, out, out_inf);
     else
         hipLaunchKernelGGL(k_add28<2>, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, s, a, ia, b, ib, (uint32_t)n, out, out_inf);
+    return hipGetLastError();
+}
+hipError_t coop_g1_mul_endo(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint32_t per, uint64_t* out, uint8_t* out_inf,
+                            hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (!per) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_g1_mul_endo28, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, base, inf, ab, (uint32_t)n, per, out, out_inf);
     return hipGetLastError();
 }
 hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s) {

@@ -32,6 +32,9 @@ hipError_t coop_g2_mul(const uint64_t* base, size_t stride, const uint64_t* sc, 
 // out[i] = a[i] + b[i] on the 28-bit core, which = 1 (G1) or 2 (G2); ia / ib / out_inf may be null
 hipError_t coop_add(int which, const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, size_t n, uint64_t* out, uint8_t* out_inf,
                     hipStream_t s);
+// out[i] = [a] P_i + [b] (beta x_i, -y_i) with (a, b) = ab[2 (i / per)], ab[2 (i / per) + 1] (= [a + b z^2] P_i in G1); inf / out_inf may be null
+hipError_t coop_g1_mul_endo(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint32_t per, uint64_t* out, uint8_t* out_inf,
+                            hipStream_t s);
 // the bucket MSM's launches (zkp_coop.hip, "group addition and bucket MSM"; driven by zkp_msm.hip, sized by zkp_msm_plan.hpp)
 hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s);
 hipError_t msm_digits(const uint64_t* sc, const uint8_t* inf, uint32_t terms, uint32_t m, int shared, uint32_t c, uint32_t windows, uint32_t* keys,

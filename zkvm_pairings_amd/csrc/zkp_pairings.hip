@@ -20,6 +20,8 @@
 #include "zkp_compress.hpp"
 #include "zkp_msm.hpp"
 #include "zkp_msm_plan.hpp"
+#include "zkp_rlc.hpp"
+#include "zkp_rlc_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -450,6 +452,8 @@ struct zkp_ctx {
     hipEvent_t ws_busy = nullptr;   // recorded at the end of every *_dev call: the next call (on whatever stream) waits for it
     void* msm_ws = nullptr;     // grow-only workspace of the MSM calls (zkp_msm_plan.hpp layout)
     size_t msm_cap = 0;
+    void* rlc_ws = nullptr;     // grow-only workspace of the RLC batch check (zkp_rlc_plan.hpp layout)
+    size_t rlc_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -870,6 +874,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->d_flag) (void)hipFree(c->d_flag);
     if (c->prod) (void)hipFree(c->prod);
     if (c->msm_ws) (void)hipFree(c->msm_ws);
+    if (c->rlc_ws) (void)hipFree(c->rlc_ws);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1240,17 +1245,20 @@ int zkp_g2_add_batch_dev(zkp_ctx* c, const void* a, const void* inf_a, const voi
     if ((rc = validate_on_stream(c, a, n * 4, S(stream))) || (rc = validate_on_stream(c, b, n * 4, S(stream)))) return rc;
     return add_dev(c, 2, a, inf_a, b, inf_b, n, out, out_inf, S(stream));
 }
+static int msm_grow(zkp_ctx* c, size_t bytes) {
+    if (bytes <= c->msm_cap) return ZKP_OK;
+    if (c->msm_ws) { HIPCHK(c, hipFree(c->msm_ws)); c->msm_ws = nullptr; c->msm_cap = 0; }
+    if (hipMalloc(&c->msm_ws, bytes) != hipSuccess) { c->msm_ws = nullptr; c->err = "msm: workspace allocation"; return ZKP_ERR_OOM; }
+    zkp_dbg_alloc("ctx.msm", c->msm_ws, bytes);
+    c->msm_cap = bytes;
+    return ZKP_OK;
+}
 // n_msm >= 1 sums; grows the context's MSM workspace (an allocation synchronises the device) before it queues anything
 static int msm_dev(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, int shared, void* out, void* out_inf,
                    hipStream_t s, float* phase_ms) {
     const size_t bytes = zkp::msm_workspace_bytes(which, m, n_msm, shared);
     if (!bytes) { c->err = "msm: workspace size"; return ZKP_ERR_ARG; }
-    if (bytes > c->msm_cap) {
-        if (c->msm_ws) { HIPCHK(c, hipFree(c->msm_ws)); c->msm_ws = nullptr; c->msm_cap = 0; }
-        if (hipMalloc(&c->msm_ws, bytes) != hipSuccess) { c->msm_ws = nullptr; c->err = "msm: workspace allocation"; return ZKP_ERR_OOM; }
-        zkp_dbg_alloc("ctx.msm", c->msm_ws, bytes);
-        c->msm_cap = bytes;
-    }
+    if (int rc = msm_grow(c, bytes)) return rc;
     return coop_rc(c, which == 1 ? "g1_msm" : "g2_msm",
                    zkp::msm_run(which, c->msm_ws, (const uint64_t*)pts, (const uint8_t*)inf, (const uint64_t*)sc, m, n_msm, shared ? 1 : 0, (uint64_t*)out,
                                 (uint8_t*)out_inf, s, phase_ms));
@@ -1280,6 +1288,43 @@ int zkp_msm_profile_dev(zkp_ctx* c, int which, const void* points, const void* i
     if (!n_msm) return ZKP_OK;
     if (int rc = validate_on_stream(c, points, (shared_bases ? m : m * n_msm) * 2 * which, S(stream))) return rc;
     return msm_dev(c, which, points, inf, scalars, m, n_msm, shared_bases, out, out_inf, S(stream), phase_ms);
+}
+
+// ---- batch verification by random linear combination (zkp_rlc.hip drives it; 28-bit core for the scaling, the context's family for
+// the pairing)
+static int endo_dev(zkp_ctx* c, const void* base, const void* inf, const void* ab, size_t n, void* out, void* out_inf, hipStream_t s) {
+    return coop_rc(c, "g1_mul_endo",
+                   zkp::coop_g1_mul_endo((const uint64_t*)base, (const uint8_t*)inf, (const uint64_t*)ab, n, 1, (uint64_t*)out, (uint8_t*)out_inf, s));
+}
+int zkp_g1_mul_endo_batch_dev(zkp_ctx* c, const void* base, const void* inf, const void* ab, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || too_many(n) || (n && (!base || !ab || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    if (int rc = validate_on_stream(c, base, n * 2, S(stream))) return rc;
+    return endo_dev(c, base, inf, ab, n, out, out_inf, S(stream));
+}
+// the argument check of both flavours (zkp_rlc_plan.hpp: the size limits)
+static bool rlc_args_bad(const zkp_ctx* c, const zkp_rlc_batch* b, const void* rand, int flags, const void* all_ok) {
+    if (!c || !b || !all_ok || (flags & ~ZKP_RLC_POINTS_CHECKED) || zkp::rlc::args_bad(b->n_checks, b->k, b->s1, b->s2)) return true;
+    if (!b->n_checks) return false;
+    return !rand || (b->k && (!b->g1 || !b->g2)) || (b->s2 && (!b->col_g1 || !b->fixed_g2)) || (b->s1 && (!b->col_g2 || !b->fixed_g1));
+}
+// validation mode: v(pointer, Fp count) over every coordinate array of the batch
+extern "C++" template <class V>
+static int rlc_validate(const zkp_rlc_batch* b, V&& v) {
+    const size_t n = b->n_checks;
+    int rc;
+    if ((rc = v(b->g1, n * b->k * 2)) || (rc = v(b->g2, n * b->k * 4)) || (rc = v(b->col_g1, n * b->s2 * 2)) || (rc = v(b->fixed_g2, b->s2 * 4)) ||
+        (rc = v(b->col_g2, n * b->s1 * 4)) || (rc = v(b->fixed_g1, b->s1 * 2)))
+        return rc;
+    return ZKP_OK;
+}
+int zkp_pairing_check_batch_rlc_dev(zkp_ctx* c, const zkp_rlc_batch* b, const void* rand, int flags, void* all_ok, void* stream) {
+    if (rlc_args_bad(c, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (b->n_checks)
+        if (int rc = rlc_validate(b, [&](const void* d, size_t n_fp) { return validate_on_stream(c, d, n_fp, S(stream)); })) return rc;
+    return zkp::rlc_check_dev(c, b, (const uint64_t*)rand, flags, (int*)all_ok, S(stream));
 }
 
 // validation mode of the device-pointer entry points: *bad = 1 if any *_dev call since the last query saw a field
@@ -1472,6 +1517,81 @@ int zkp_g1_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, con
 int zkp_g2_msm_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, const uint64_t* scalars, size_t m, size_t n_msm, int shared_bases, uint64_t* out,
                      uint8_t* out_inf) {
     return msm_host(c, 2, points, inf, scalars, m, n_msm, shared_bases, out, out_inf);
+}
+
+}  // extern "C"
+
+// what the RLC batch check (zkp_rlc.hip) borrows from the context: the same launch-only pieces the entry points above use
+namespace zkp {
+namespace ctxop {
+int fail(zkp_ctx* c, const char* what, hipError_t e) { return coop_rc(c, what, e); }
+int grow_rlc(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->rlc_cap) {
+        if (c->rlc_ws) { HIPCHK(c, hipFree(c->rlc_ws)); c->rlc_ws = nullptr; c->rlc_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->rlc_ws, bytes));
+        zkp_dbg_alloc("ctx.rlc", c->rlc_ws, bytes);
+        c->rlc_cap = bytes;
+    }
+    *ws = c->rlc_ws;
+    return ZKP_OK;
+}
+int grow_msm(zkp_ctx* c, size_t bytes) { return msm_grow(c, bytes); }
+int msm(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, void* out, void* out_inf, hipStream_t s) {
+    return msm_dev(c, which, pts, inf, sc, m, n_msm, 0, out, out_inf, s, nullptr);
+}
+int valid(zkp_ctx* c, int which, const void* pts, const void* inf, size_t n, void* status, hipStream_t s) { return valid_dev(c, which, pts, inf, n, status, s); }
+int miller_product(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* i1, const uint8_t* i2, size_t n, uint64_t* out, hipStream_t s) {
+    return miller_product_dev(c, g1, g2, i1, i2, n, out, s);
+}
+int gt_is_one(zkp_ctx* c, uint64_t* f, size_t n, uint64_t* gt, int* is_one, hipStream_t s) {
+    int rc;
+    if ((rc = fp12_product_inplace(c, f, n, s)) || (rc = final_exp_dev(c, f, 1, gt, s))) return rc;
+    hipLaunchKernelGGL(k_gt_is_one, dim3(1), dim3(64), 0, s, gt, is_one);
+    HIPCHK(c, hipGetLastError());
+    return ZKP_OK;
+}
+}  // namespace ctxop
+}  // namespace zkp
+
+extern "C" {
+
+int zkp_g1_mul_endo_batch(zkp_ctx* c, const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint64_t* out, uint8_t* out_inf) {
+    if (!c || too_many(n) || (n && (!base || !ab || !out))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const uint64_t* db = (const uint64_t*)io.in(0, base, n * 96);
+    const void* dab = io.in(1, ab, n * 16);
+    void* dout = io.out(4, out, n * 96);
+    void* dinf = io.out(6, out_inf, n);
+    const void* di = io.in(2, inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, db, n * 2)) || (rc = endo_dev(c, db, di, dab, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+// the batch's thirteen arrays one after the other in slot 0 (256-byte aligned), then the same driver as the _dev flavour
+int zkp_pairing_check_batch_rlc(zkp_ctx* c, const zkp_rlc_batch* b, const uint64_t* rand, int flags, int* all_ok) {
+    if (rlc_args_bad(c, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    if (!b->n_checks) { *all_ok = 1; return ZKP_OK; }
+    const size_t n = b->n_checks, np = n * b->k, t2 = n * b->s2, t1 = n * b->s1;
+    zkp_rlc_batch d = *b;
+    const void* drand = rand;
+    const void** field[13] = {&d.g1, &d.g2, &d.inf1, &d.inf2, &d.col_g1, &d.col_inf1, &d.fixed_g2, &d.fixed_inf2, &d.col_g2, &d.col_inf2, &d.fixed_g1,
+                              &d.fixed_inf1, &drand};
+    const size_t bytes[13] = {np * 96, np * 192, np, np, t2 * 96, t2, b->s2 * 192, b->s2, t1 * 192, t1, b->s1 * 96, b->s1, n * 16};
+    size_t off[13], total = 0;
+    for (int i = 0; i < 13; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    char* dev = (char*)io.slot(0, total);
+    for (int i = 0; i < 13; i++) *field[i] = bytes[i] ? io.put(dev + off[i], *field[i], bytes[i]) : nullptr;
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = rlc_validate(&d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
+        (rc = zkp::rlc_check_dev(c, &d, (const uint64_t*)drand, flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
 }
 
 // both point codecs, host pointers (only the compressed flavours cap n): slot 0 the input, slot 4 the output, slot 2 the infinity

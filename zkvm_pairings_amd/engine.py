@@ -333,6 +333,149 @@ class PairingEngine:
         self._chk(fn(self._h, _ptr(pts), _ptr(i), _ptr(sc), m, n_msm, 1 if shared else 0, _ptr(out), _ptr(oi)))
         return out, oi
 
+    # ---- batch verification by random linear combination
+    def g1_mul_endo(self, base, ab, inf=None):
+        """[a_i] P_i + [b_i] (beta x_i, -y_i), ab (n, 2) uint64 = (a_i, b_i): for P_i in G1 this is [a_i + b_i z^2] P_i (z the BLS parameter).
+        -> (points (n,12), inf (n,)).  torch tensors stay on the GPU (the engine's stream)."""
+        if _is_torch(base):
+            import torch
+            self._t_check(base, 12, "base")
+            n = base.numel() // 12
+            self._t_check(ab, 2, "ab")
+            if ab.numel() != 2 * n:
+                raise ValueError("ab holds %d pairs for %d points" % (ab.numel() // 2, n))
+            self._t_bytes(inf, n, "inf")
+            out = torch.empty((n, 12), dtype=base.dtype, device=base.device)
+            oi = torch.empty(n, dtype=torch.uint8, device=base.device)
+            self._chk(self._lib.zkp_g1_mul_endo_batch_dev(self._h, self._tp(base), self._tp(inf), self._tp(ab), n, self._tp(out), self._tp(oi),
+                                                          self._stream()))
+            return out, oi
+        base, ab = _np(base, 12), _np(ab, 2)
+        n = base.shape[0]
+        if ab.shape[0] != n:
+            raise ValueError("ab holds %d pairs for %d points" % (ab.shape[0], n))
+        i = _flags(inf, n, "inf")
+        out, oi = np.empty((n, 12), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_g1_mul_endo_batch(self._h, _ptr(base), _ptr(i), _ptr(ab), n, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    @staticmethod
+    def rlc_random(n):
+        """(n, 2) uint64 scalars (a_c, b_c) for pairing_check_rlc from the operating system's CSPRNG (os.urandom), no pair (0, 0)"""
+        import os
+        r = np.frombuffer(os.urandom(16 * n), dtype=np.uint64).reshape(n, 2).copy()
+        while n and (r == 0).all(axis=1).any():
+            z = (r == 0).all(axis=1)
+            r[z] = np.frombuffer(os.urandom(16 * int(z.sum())), dtype=np.uint64).reshape(-1, 2)
+        return r
+
+    def pairing_check_rlc(self, g1, g2, k, *, col_g1=None, fixed_g2=None, col_g2=None, fixed_g1=None, inf1=None, inf2=None, col_inf1=None,
+                          fixed_inf2=None, col_inf2=None, fixed_inf1=None, rand=None, points_checked=False, locate=False):
+        """n independent pairing checks verified as ONE (zkp_pairing_check_batch_rlc): check c is the product of its k free pairs
+        (g1[c k + j], g2[c k + j]), its s2 pairs (col_g1[c s2 + j], fixed_g2[j]) and its s1 pairs (fixed_g1[j], col_g2[c s1 + j]).
+        True iff prod_c (check c)^(a_c + b_c z^2) == 1, every point is valid (unless points_checked) and no (a_c, b_c) is zero;
+        a batch with a failing check passes with probability <= 2^-128.  rand (n, 2) uint64: the scalars, by default fresh from
+        os.urandom (rlc_random) - never a seeded generator.  Host arrays return a bool; resident torch tensors an int32 tensor (1,)
+        without synchronising.  locate=True returns (all_ok, ok bytes (n,)): when the batch fails, the per-check flags of
+        pairing_check on the expanded checks (ANDed with the points' validity unless points_checked)."""
+        torch_in = any(_is_torch(x) for x in (g1, col_g1, col_g2))
+        cols = lambda x, w: 0 if x is None else (x.numel() if _is_torch(x) else np.asarray(x).size) // w
+        k = int(k)
+        s2, s1 = cols(fixed_g2, 24), cols(fixed_g1, 12)
+        if k < 0 or (k and g1 is None):
+            raise ValueError("k = %d free pairs per check without g1 / g2" % k)
+        if k:
+            n, n_from = cols(g1, 12) // k, cols(g1, 12)
+            if n_from % k:
+                raise ValueError("%d G1 points is not a multiple of k = %d" % (n_from, k))
+        elif s2:
+            n = cols(col_g1, 12) // s2
+        elif s1:
+            n = cols(col_g2, 24) // s1
+        else:
+            n = 0
+        want = {"g1": (g1, 12, n * k), "g2": (g2, 24, n * k), "col_g1": (col_g1, 12, n * s2), "col_g2": (col_g2, 24, n * s1)}
+        for name, (x, w, rows) in want.items():
+            if rows and cols(x, w) != rows:
+                raise ValueError("%s holds %d points, %d expected" % (name, cols(x, w), rows))
+        if (s2 and col_g1 is None) or (s1 and col_g2 is None):
+            raise ValueError("a fixed column without its per-check points")
+        if n == 0:
+            return (True, np.zeros(0, dtype=np.uint8)) if locate else True
+        if rand is None:
+            rand = self.rlc_random(n)
+        flags = _lib.RLC_POINTS_CHECKED if points_checked else 0
+        arrays = [("g1", g1, 12, n * k), ("g2", g2, 24, n * k), ("inf1", inf1, None, n * k), ("inf2", inf2, None, n * k),
+                  ("col_g1", col_g1, 12, n * s2), ("col_inf1", col_inf1, None, n * s2), ("fixed_g2", fixed_g2, 24, s2), ("fixed_inf2", fixed_inf2, None, s2),
+                  ("col_g2", col_g2, 24, n * s1), ("col_inf2", col_inf2, None, n * s1), ("fixed_g1", fixed_g1, 12, s1), ("fixed_inf1", fixed_inf1, None, s1)]
+        b = _lib.RlcBatch(n_checks=n, k=k, s2=s2, s1=s1)
+        keep = []
+        if torch_in:
+            import torch
+            dev = torch.device("cuda", self.device)
+            for name, x, w, rows in arrays:
+                if x is None or not rows:
+                    continue
+                if w is None:
+                    self._t_bytes(x, rows, name)
+                else:
+                    self._t_check(x, w, name, rows=rows)
+                setattr(b, name, x.data_ptr())
+            if not _is_torch(rand):
+                rand = torch.from_numpy(np.ascontiguousarray(rand, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
+            self._t_check(rand, 2, "rand", rows=n)
+            all_ok = torch.empty(1, dtype=torch.int32, device=dev)
+            self._chk(self._lib.zkp_pairing_check_batch_rlc_dev(self._h, ctypes.byref(b), self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            if not locate:
+                return all_ok
+            ok = bool(all_ok.item())
+            host = lambda x: None if x is None else (x.cpu().numpy() if _is_torch(x) else x)
+            g1, g2, inf1, inf2, col_g1, col_inf1, fixed_g2, fixed_inf2, col_g2, col_inf2, fixed_g1, fixed_inf1 = [host(a[1]) for a in arrays]
+        else:
+            for name, x, w, rows in arrays:
+                if x is None or not rows:
+                    continue
+                a = _flags(x, rows, name) if w is None else _np(x, w)
+                if w is not None and a.shape[0] != rows:
+                    raise ValueError("%s holds %d points, %d expected" % (name, a.shape[0], rows))
+                keep.append(a)
+                setattr(b, name, a.ctypes.data)
+            r = _np(rand, 2)
+            if r.shape[0] != n:
+                raise ValueError("rand holds %d pairs for %d checks" % (r.shape[0], n))
+            res = ctypes.c_int(0)
+            self._chk(self._lib.zkp_pairing_check_batch_rlc(self._h, ctypes.byref(b), _ptr(r), flags, ctypes.byref(res)))
+            ok = bool(res.value)
+            if not locate:
+                return ok
+        if ok:
+            return True, np.ones(n, dtype=np.uint8)
+        e1, e2, f1, f2, kk = self._rlc_expand(n, k, s1, s2, g1, g2, inf1, inf2, col_g1, col_inf1, fixed_g2, fixed_inf2, col_g2, col_inf2, fixed_g1,
+                                              fixed_inf1)
+        per, _ = self.pairing_check(e1, e2, kk, f1, f2)
+        if not points_checked:
+            bad = (self.g1_is_valid(e1, f1) | self.g2_is_valid(e2, f2)).reshape(n, kk).any(axis=1)
+            per[bad] = 0
+        return False, per
+
+    @staticmethod
+    def _rlc_expand(n, k, s1, s2, g1, g2, inf1, inf2, col_g1, col_inf1, fixed_g2, fixed_inf2, col_g2, col_inf2, fixed_g1, fixed_inf1):
+        """the checks of a pairing_check_rlc batch as k + s2 + s1 consecutive pairs each (host arrays)"""
+        kk = k + s2 + s1
+        e1, e2 = np.zeros((n, kk, 12), dtype=np.uint64), np.zeros((n, kk, 24), dtype=np.uint64)
+        f1, f2 = np.zeros((n, kk), dtype=np.uint8), np.zeros((n, kk), dtype=np.uint8)
+        fl = lambda x, shape: 0 if x is None else np.asarray(x, dtype=np.uint8).reshape(shape)
+        if k:
+            e1[:, :k], e2[:, :k] = _np(g1, 12).reshape(n, k, 12), _np(g2, 24).reshape(n, k, 24)
+            f1[:, :k], f2[:, :k] = fl(inf1, (n, k)), fl(inf2, (n, k))
+        if s2:
+            e1[:, k:k + s2], e2[:, k:k + s2] = _np(col_g1, 12).reshape(n, s2, 12), _np(fixed_g2, 24)[None]
+            f1[:, k:k + s2], f2[:, k:k + s2] = fl(col_inf1, (n, s2)), fl(fixed_inf2, (1, s2))
+        if s1:
+            e1[:, k + s2:], e2[:, k + s2:] = _np(fixed_g1, 12)[None], _np(col_g2, 24).reshape(n, s1, 24)
+            f1[:, k + s2:], f2[:, k + s2:] = fl(fixed_inf1, (1, s1)), fl(col_inf2, (n, s1))
+        return e1.reshape(-1, 12), e2.reshape(-1, 24), f1.reshape(-1), f2.reshape(-1), kk
+
     def msm_profile(self, which, points, scalars, n_msm=1, shared_bases=False):
         """measurement: one MSM on torch tensors with the milliseconds of its six phases (zkp_msm_profile_dev)"""
         import torch
