@@ -186,14 +186,13 @@ int main() {
                 k.n_pipes = pipes;
                 k.max_stream = (size_t)ms;
                 k = clamp(k);
-                k.c_single_min = k.chunk;
                 knobs.push_back(k);
                 Knobs k2 = k;
                 k2.c_split = 3; k2.split_min = 1; k2.super = (size_t)1 << 22; k2.inv_batch = 1; k2.inv_lanes = 1;
                 k2 = clamp(k2);
                 knobs.push_back(k2);
                 Knobs k3 = k;
-                k3.c_single = false; k3.split_min = (size_t)1 << 40; k3.super = 1; k3.inv_batch = 100000; k3.inv_lanes = (size_t)1 << 40;
+                k3.split_min = (size_t)1 << 40; k3.super = 1; k3.inv_batch = 100000; k3.inv_lanes = (size_t)1 << 40;
                 k3 = clamp(k3);
                 knobs.push_back(k3);
             }

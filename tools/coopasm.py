@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Hand-scheduled gfx950 code of the step interpreter's MULACC step (k_coop, zkp_coop.hip) -> csrc/zkp_coop_mulacc.inc.
 
-The C++ term loop of k_coop costs 201 VALU instructions per term for 147 multiply-adds (28 operand copies, address
-arithmetic, 14 Karatsuba half sums) and its per-step part 432 for 196 (80 accumulator clears, a column-serial reduction);
-every attempt to get a copy-free loop out of the compiler ended in spills or a lost wavefront.  This
-generator emits the step as ONE inline-asm block with pinned registers:
+A compiled C++ term loop cost 201 VALU instructions per term for 147 multiply-adds (28 operand copies, address arithmetic,
+14 Karatsuba half sums) and its per-step part 432 for 196 (80 accumulator clears, a column-serial reduction); every attempt
+to get a copy-free loop out of the compiler ended in spills or a lost wavefront.  This generator emits
+the step as ONE inline-asm block with pinned registers:
 
   * two operand register sets (terms alternate), loaded straight by ds_read_b128 - no copies;
   * LDS addresses come RESOLVED from a per-lane table (built by the host at start-up from the generated step tables:
@@ -16,8 +16,10 @@ generator emits the step as ONE inline-asm block with pinned registers:
     m-computation of row i + 1, so the dependent chain (mul_lo, and, mad, shift, add) never stalls the wavefront;
   * limb extraction is one v_bfe_i32 per limb + the 64-bit carry.
 
-The arithmetic is EXACTLY acc_mul_k / acc_fold / acc_reduce of zkp_fp28.hpp (the same columns mod 2^64, the same m_i, the
-same balanced limbs), so tools/coopgen.py's emulator stays the gate and `ZKP_COOP_ASM=0` builds the C++ loop as the A/B baseline.
+The arithmetic is one level of Karatsuba over the limb halves: a_lo b_lo and a_hi b_hi land in the schoolbook columns of acc_mul
+(zkp_fp28.hpp), the middle product in its subtractive form (a_hi - a_lo)(b_lo - b_hi) in 13 extra columns shared by every term,
+folded in by additions only (mod 2^64: the true column values fit), then acc_reduce.  The columns, the m_i and the balanced limbs
+are EXACTLY those of acc_mul + acc_reduce, so tools/coopgen.py's emulator stays the gate.
 
 Reference anchors (what the step computes): Fp12::mul_by_014 src/fp12.rs:99-111, Fp12::square :173-184, Fp12 Mul :193-210.
 """
@@ -266,15 +268,12 @@ def tail(g, out, fold=True):
             g.e("v_mov_b32 v%d, v%d" % (out + NL - 1, tmp))    # column 27 is empty: the last carry is the top limb
 
 
-SETPRIO = int(os.environ.get("ZKP_GEN_SETPRIO", "0"))
-
-
 def generate(vb=8):
     g = Asm(vb)
     out = g.A[0]
     # prologue: per-step flag words (row T of the resolved table), entry of term 0, operands of term 0, entry of term 1
     g.e("s_mov_b64 s[%d:%d], %%[rt]" % (g.sRT, g.sRT + 1))
-    g.e("s_mul_i32 s%d, %%[T], %%[row]" % g.sX)       # row: bytes per table row (64 lanes x 16 B x wavefronts per workgroup)
+    g.e("s_mul_i32 s%d, %%[T], %%[row]" % g.sX)       # row: bytes per table row (64 lanes x 16 B)
     g.e("s_add_u32 s%d, s%d, s%d" % (g.sX, g.sRT, g.sX))
     g.e("s_addc_u32 s%d, s%d, 0" % (g.sX + 1, g.sRT + 1))
     g.e("s_mov_b64 s[%d:%d], s[%d:%d]" % (g.sFR, g.sFR + 1, g.sX, g.sX + 1))
@@ -300,9 +299,6 @@ def generate(vb=8):
     g.e("s_cmp_lt_u32 s%d, %%[T]" % g.sT)
     g.e("s_cbranch_scc1 .Lmloop_%=")
     g.e(".Lmtail_%=:")
-    if SETPRIO:
-        # experiment (round 5): a wavefront in its reduction tail / store section issues ahead of wavefronts in their term loops
-        g.e("s_setprio %d" % SETPRIO)
     g.e("s_waitcnt vmcnt(0)")
     # the step's store words (z, w of the flag row; the flag words themselves are dead): LDS byte address of the result slot and of
     # its companion slot, -1 where the lane stores nothing - requested here, they arrive behind the reduction
@@ -346,8 +342,6 @@ def generate(vb=8):
     g.e("s_mov_b64 exec, s[%d:%d]" % (g.sEX, g.sEX + 1))
     g.e(".Lmdone_%=:")
     g.e("s_waitcnt lgkmcnt(0)")
-    if SETPRIO:
-        g.e("s_setprio 0")
     return g, out
 
 
@@ -473,7 +467,7 @@ def ksqr_k(g, A, P1, P2, first):
 #     per limb, interleaved; their results ARE the next product's X registers;
 #   * the new coefficient is parked from those registers (seven ds_write_b128: re0..re13, im0..im13 are 28 consecutive
 #     registers) and the pair partner's coefficient lands in the Y registers by DPP.
-# Same integers as sq_combine / the C++ combinations of zkp_coop.hip (tools/coopgen.py emu_ksq is the model).
+# Same integers as sq_combine and the lane-role combinations of tools/coopgen.py emu_ksq (the model).
 P_BLS = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 VRED_C, VRED_SHIFT_IN, VRED_SHIFT_OUT = 80647, 9, 24      # zkp_coop_prog.inc (asserted by write_inc)
 

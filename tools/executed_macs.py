@@ -22,7 +22,7 @@ import coopgen as cg  # noqa: E402
 import prepasm  # noqa: E402
 
 # lanes of an interpreter wavefront that execute: 5 checks x 12 lanes.  Lanes 60..63 own nothing; until round 4 they ran every instruction
-# on a neighbour's operands (64 lanes issued), since round 5 they leave the kernel at its start (zkp_coop.hip, ZKP_COOP_IDLE_LANES_OFF)
+# on a neighbour's operands (64 lanes issued), since round 5 they leave the kernel at its start (zkp_coop.hip k_coop)
 COOP_LANES = 60
 
 MAD = re.compile(r"^\s*v_mad_[iu]64_[iu]32\b")

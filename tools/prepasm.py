@@ -1,20 +1,19 @@
 #!/usr/bin/env python3
-"""The homogeneous-projective doubling step of k_prep_lines<true> (zkp_coop.hip dbl_step_cln) as ONE hand-allocated gfx950
-asm block -> csrc/zkp_prep_dbl.inc.
+"""The homogeneous-projective doubling step of k_prep_lines<true> as ONE hand-allocated gfx950 asm block -> csrc/zkp_prep_dbl.inc.
 
-Why: the compiled step calls eleven by-value field routines; per lane and step it issues 4,508 multiply-adds and ~3,100 other
+Why: the compiled step called eleven by-value field routines; per lane and step it issued 4,508 multiply-adds and ~3,100 other
 instructions (argument moves, operand forms through v_cndmask, a renormalisation per scaled product), and Karatsuba product
 blocks cost the callers their registers.  Here the whole step has ONE register allocation:
 
   * six 14-register value blocks (X, Y, W pinned in/out + three), three 16-register temporaries (the last two registers of
     each stay zero: a line record is stored from them as four dwordx4), the Karatsuba product set of tools/coopasm.py
     (kterm / tail: 80 accumulator registers + 14 differences) - 232 VGPRs, two waves per SIMD as before;
-  * lane parity c = Fp2 coefficient (two lanes per pair, as in the compiled kernel); the lane roles are EXEC parity masks and
+  * lane parity c = Fp2 coefficient (two lanes per pair, as in the rest of k_prep_lines); the lane roles are EXEC parity masks and
     v_cndmask on a parity VCC, the partner's coefficient comes by DPP quad_perm [1,0,3,2] (always under full EXEC);
   * every product is kterm (147 multiply-adds), every reduction tail(): 13 products + 10 reductions per step
     = 3,871 multiply-adds; scalings sit on operands, so only E = 3 xi C and the stored c2 coefficient are renormalised.
 
-Formulas (the same values as dbl_step_cln; Costello-Lange-Naehrig doubling on (X : Y : W = 2Z), scaled by 4, b' = 4 xi):
+Formulas (Costello-Lange-Naehrig doubling on (X : Y : W = 2Z), scaled by 4, b' = 4 xi):
     B = Y^2, C = W^2, H2 = (Y + W)^2 - B - C, E = 3 xi C, F = 3 E,
     X' = ((X + Y)^2 - X^2 - B)(B - F),  Y' = (B + F)^2 - 12 E^2,  W' = B (4 H2)
     line: c2 = 2 (B - E) [record 0 + c], c1 xP = (-6 X^2) xP [record 2 + c], c0 yP = H2 yP [record 4 + c]
@@ -294,7 +293,7 @@ def generate(vb=6):
 
 
 def generate_add(vb=6):
-    """the mixed addition T + Q on the same coordinates (zkp_coop.hip add_step_cln; Aranha et al. eq. (13), (14) with every quantity
+    """the mixed addition T + Q on the same coordinates (Aranha et al. eq. (13), (14) with every quantity
     doubled: W = 2 Z), Q = (qx, qy) parked in LDS (values 2, 3: this lane's coefficient):
         th = 2 Y - qy W, la = 2 X - qx W (renormalised), line: c2 = th qx - la qy, c1 xP = -th xP, c0 yP = la yP,
         C = th^2, D = la^2, E = la D, F = W C, G = 2 X D, H = E + F - 2 G, X' = la H, Y' = th (G - H) - 2 Y E, W' = 2 W E
@@ -359,7 +358,7 @@ def generate_add(vb=6):
 
 def generate_jac(vb=6):
     """The doubling step of k_prep_lines<false> - the lines zkp_multi_miller_loop_batch must return the value of - as one block:
-    the point in Jacobian coordinates as ePrint 2010/354 Alg. 26 walks it (zkp_coop.hip dbl_step; reference src/g2.rs:210-242 is the
+    the point in Jacobian coordinates as ePrint 2010/354 Alg. 26 walks it (reference src/g2.rs:210-242 is the
     same doubling) and the upstream-shaped line coefficients, every VALUE mod p the one Alg. 26 produces (the Miller value is
     compared bit for bit with the oracle's), the route to it the cheapest this machine has:
         B = Y^2, zz = Z^2, Z' = (Y + Z)^2 - B - zz,  M = 3 X^2 (straight out of the squaring's reduction),  S = (4X) B,
@@ -429,7 +428,7 @@ def generate_jac(vb=6):
 
 
 def generate_jac_add(vb=6):
-    """The mixed-addition step of k_prep_lines<false>: ePrint 2010/354 Alg. 27 in VALUES (zkp_coop.hip add_step), Q = (qx, qy) parked
+    """The mixed-addition step of k_prep_lines<false>: ePrint 2010/354 Alg. 27 in VALUES, Q = (qx, qy) parked
     in LDS values 2, 3:
         zz = Z^2, U2 = qx zz, S2' = (2 qy) Z zz, H = U2 - X, r = S2' - 2Y  [Alg. 27's t2, t6],  Z' = (2Z) H  [its nz],
         HH = H^2, t5 = (2H)(2HH) = 4 H^3, t7 = (2X)(2HH) = 4 X H^2,  X' = r^2 - t5 - 2 t7,  Y' = r (t7 - X') - (2Y) t5,

@@ -38,47 +38,22 @@
 
 #include "zkp_coop_prog.inc"
 #include "zkp_fp28.hpp"
-#ifndef ZKP_COOP_ASM
-#define ZKP_COOP_ASM 1   // the MULACC step of k_coop as one hand-scheduled inline-asm block (tools/coopasm.py -> zkp_coop_mulacc.inc);
-                         // 0 builds the C++ term loop below it, the A/B baseline
-#endif
-#if ZKP_COOP_ASM
-#include "zkp_coop_mulacc.inc"
-#endif
-#ifndef ZKP_PREP_ASM
-#define ZKP_PREP_ASM ZKP_COOP_ASM   // the doubling step of k_prep_lines<true> as one hand-allocated asm block (tools/prepasm.py ->
-                                    // zkp_prep_dbl.inc); 0: the compiled step (dbl_step_cln), the A/B baseline
-#endif
-#if ZKP_PREP_ASM
-#include "zkp_prep_dbl.inc"
-#endif
-#ifndef ZKP_VALID_ASM
-#define ZKP_VALID_ASM ZKP_COOP_ASM   // the Jacobian doubling / mixed addition of the subgroup checks as asm blocks (tools/validasm.py ->
-                                     // zkp_valid_steps.inc): k_g1_valid_fast / k_g2_valid_fast; 0: the compiled kernels only (round 3)
-#endif
-#if ZKP_VALID_ASM
-#include "zkp_valid_steps.inc"
-#endif
+#include "zkp_coop_mulacc.inc"   // the MULACC step of k_coop and the squaring of k_ksq as hand-scheduled asm blocks (tools/coopasm.py)
+#include "zkp_prep_dbl.inc"      // the doubling / addition steps of k_prep_lines as hand-allocated asm blocks (tools/prepasm.py)
+#include "zkp_valid_steps.inc"   // the Jacobian doubling / mixed addition of the subgroup checks as asm blocks (tools/validasm.py)
 
 using namespace zkp28;
 
 namespace {
 
-#ifndef ZKP_COOP_WG_WAVES
-#define ZKP_COOP_WG_WAVES 1   // wavefronts per k_coop workgroup: 1 = five checks per wavefront, lanes 60..63 idle; 3 = sixteen checks per
-                              // workgroup - lanes 60..63 of the three wavefronts together run the sixteenth check, and every step that
-                              // touches LDS is fenced by workgroup barriers (its operand reads before its in-place result store, its
-                              // stores before the next step's reads).  Bit-exact and measured: 6.25 % fewer
-                              // wavefronts, but they spend 21 % of their cycles at the barriers - the Miller program alone runs 12 %
-                              // slower, the 2^20-pair pass the same (256.8 against 256.0 ms).  Kept as a build knob.
-#endif
-constexpr int WGW = ZKP_COOP_WG_WAVES;
-static_assert(WGW == 1 || WGW == 3, "one wavefront (5 checks) or three (16 checks) per workgroup");
-constexpr int GROUPS = WGW == 3 ? 16 : 5;   // checks per workgroup
+// one wavefront per k_coop workgroup: five checks of twelve lanes, lanes 60..63 idle.  Sixteen checks on three wavefronts (workgroup
+// barriers around every step that touches LDS) were bit-exact and measured: 6.25 % fewer wavefronts, but they
+// spent 21 % of their cycles at the barriers - the Miller program alone ran 12 % slower, the 2^20-pair pass the same (256.8 / 256.0 ms)
+constexpr int GROUPS = 5;              // checks per workgroup
 constexpr int LIG = ZKP_COOP_G;        // 12 lanes per group
 constexpr int ST_SIZE = ZKP_COOP_ST_SIZE;
 constexpr int NLINES = ZKP_COOP_NLINES;
-static_assert(zkp::plan::NLINES == NLINES && zkp::plan::ST_SIZE == ST_SIZE && zkp::plan::GROUPS == (WGW == 3 ? 16 : 5),
+static_assert(zkp::plan::NLINES == NLINES && zkp::plan::ST_SIZE == ST_SIZE && zkp::plan::GROUPS == GROUPS,
               "zkp_plan.hpp (the host's planning arithmetic, checked under sanitizers on the CPU) follows the generated programs");
 
 enum { OP_END = 0, OP_MULACC = 1, OP_LIN = 2, OP_GLOAD = 3, OP_GSTORE = 4, OP_LOOP = 5, OP_ENDLOOP = 6,
@@ -173,35 +148,24 @@ __device__ __forceinline__ void canon28(uint32_t* f, const int32_t* x) {
 }
 
 __host__ __device__ constexpr int coop_group_stride(int S) { return S + ((4 - S % 8) + 8) % 8; }
-// (+ 16 bytes behind the image with three wavefronts: the identity flags of the check that straddles them)
 constexpr int coop_cfg_slots(uint32_t cfg) { return cfg == 2 ? ZKP_COOP_DEEP_NSLOT : cfg == 1 ? ZKP_COOP_WIDE_NSLOT : ZKP_COOP_NSLOT; }
 constexpr int coop_cfg_consts(uint32_t cfg) { return cfg == 2 ? ZKP_COOP_DEEP_NCONST : cfg == 1 ? ZKP_COOP_WIDE_NCONST : ZKP_COOP_NCONST; }
-constexpr size_t coop_lds_bytes(int S, int SC) { return (size_t)4 * (SC + GROUPS * coop_group_stride(S)) * 16 + (WGW > 1 ? 16 : 0); }
-#ifndef ZKP_COOP_KARATSUBA
-#define ZKP_COOP_KARATSUBA 1   // acc_mul_k: 147 multiply-adds per product block instead of 196 (zkp_fp28.hpp); measured on one box,
-                               // 2^20-pair pass: 296.5 ms -> 283.3 ms
-#endif
-#ifndef ZKP_COOP_WAVES
-#if ZKP_COOP_ASM
-#define ZKP_COOP_WAVES 3   // the asm block pins 156 VGPRs (80 Karatsuba accumulators, two operand sets); with the per-lane context
-                           // re-derived per step the kernel needs 166 = 3 waves per SIMD, no spills (12 x 11-12 KB of LDS per CU)
-#else
-#define ZKP_COOP_WAVES 2   // C++ term loop: register bound only - it allocates 168 VGPRs = 3 waves per SIMD under bound 2.  Measured
-                           // alternatives: bound 3 -> 4 spilled VGPRs, 290.7 ms; bound 4 (128 VGPRs, 86 spilled) -> 925 ms; without
-                           // Karatsuba 4 waves x 128 VGPRs: 296.5 ms
-#endif
-#endif
+constexpr size_t coop_lds_bytes(int S, int SC) { return (size_t)4 * (SC + GROUPS * coop_group_stride(S)) * 16; }
+// the asm block pins 156 VGPRs (80 Karatsuba accumulators - 147 multiply-adds per product block instead of 196, measured on the 2^20-pair
+// pass: 296.5 -> 283.3 ms - and two operand sets); with the per-lane context re-derived per step the kernel needs 166 = 3 waves per SIMD,
+// no spills (12 x 11-12 KB of LDS per CU)
+constexpr int COOP_WAVES = 3;
 // S slots per group and SC constants: two instantiations - <24, 34> for programs that need the whole constants table (11,136 B of
 // LDS per wavefront), <30, 4> for the Miller programs (30 slots, 4 constants; 11,776 B); twelve wavefronts per CU either way
 template <int S, int SC>
-__global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
+__global__ void __launch_bounds__(64, COOP_WAVES) k_coop(CoopArgs A) {
     extern __shared__ int4 lds[];
     const uint32_t n_checks = eff_n(A.n_checks, A.nd);     // wave-uniform; also the stride of the line buffer (k_prep_lines takes the same)
     if (blockIdx.x * GROUPS >= n_checks) return;          // the whole workgroup: nothing below is reached by part of it
-    const int lane = threadIdx.x;        // 0 .. 64 * WGW - 1: the lane number within the workgroup
-    // per-lane values, all functions of the lane number.  With the asm MULACC block (ZKP_COOP_ASM) they are re-derived at the top of
-    // every step and again behind the block from an opaque copy of `lane` (ZKP_LANE_CTX): kept in registers across the block they
-    // would cost the kernel its third wavefront per SIMD (the block owns 156 of the 168 VGPRs)
+    const int lane = threadIdx.x;
+    // per-lane values, all functions of the lane number.  They are re-derived at the top of every step and again behind the asm
+    // MULACC block from an opaque copy of `lane` (ZKP_LANE_CTX): kept in registers across the block they would cost the kernel its
+    // third wavefront per SIMD (the block owns 156 of the 168 VGPRs)
     int grp, lig, gbase;
     uint32_t check;
     bool lane_ok, active;
@@ -212,50 +176,27 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
     // (its group's base or 0) + its number.  SG = S rounded up to 4 mod 8: the lane groups of a ds_read_b128 (lanes of up to
     // three check groups) then fall on different bank quads for neighbouring slots.
     constexpr int SG = coop_group_stride(S), PS = SC + GROUPS * SG;
-#if ZKP_COOP_ASM
-#define ZKP_LANE_OPAQUE(l) asm volatile("" : "+v"(l))
-#else
-#define ZKP_LANE_OPAQUE(l) (void)0
-#endif
 #define ZKP_LANE_CTX()                                                                                  \
     do {                                                                                                \
         int l_ = lane;                                                                                  \
-        ZKP_LANE_OPAQUE(l_);                                                                            \
-        if (WGW == 1) {                                                                                 \
-            grp = (l_ * 43) >> 9;             /* lane / 12 for lane < 64 */                             \
-            lig = l_ - grp * LIG;             /* lanes 60..63: grp 5, lig 0..3 (never store) */         \
-            lane_ok = grp < GROUPS;                                                                     \
-        } else {                              /* wavefront w: checks 5w .. 5w+4; its lanes 60..63 are lanes 4w .. 4w+3 of check 15 */ \
-            const int wv_ = l_ >> 6, wl_ = l_ & 63, g0_ = (wl_ * 43) >> 9;                              \
-            grp = g0_ < 5 ? wv_ * 5 + g0_ : 15;                                                         \
-            lig = g0_ < 5 ? wl_ - g0_ * LIG : wv_ * 4 + (wl_ - 60);                                     \
-            lane_ok = true;                                                                             \
-        }                                                                                               \
+        asm volatile("" : "+v"(l_));                                                                    \
+        grp = (l_ * 43) >> 9;             /* lane / 12 for lane < 64 */                                 \
+        lig = l_ - grp * LIG;                                                                           \
+        lane_ok = grp < GROUPS;                                                                         \
         check = blockIdx.x * GROUPS + grp;                                                              \
         active = lane_ok && check < n_checks;                                                           \
         gbase = SC + (lane_ok ? grp : GROUPS - 1) * SG;                                                 \
     } while (0)
-    // with several wavefronts per workgroup one check's lanes sit in all of them: LDS reads and writes of a step are fenced
-// (LDS counter only: a global load in flight need not land before the barrier)
-#define ZKP_WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define ZKP_WG_FENCE() do { if (WGW > 1) ZKP_WG_BARRIER(); } while (0)
 
-    for (int i = lane; i < (int)A.nconst * 4; i += 64 * WGW) lds[(i & 3) * PS + (i >> 2)] = A.consts[i];
+    for (int i = lane; i < (int)A.nconst * 4; i += 64) lds[(i & 3) * PS + (i >> 2)] = A.consts[i];
     __syncthreads();
-#ifndef ZKP_COOP_IDLE_LANES_OFF
-#define ZKP_COOP_IDLE_LANES_OFF 1
-#endif
-#if ZKP_COOP_IDLE_LANES_OFF
-    // round 5: lanes 60..63 of a one-wavefront workgroup own nothing (five checks of twelve lanes) - they used to run every instruction
-    // on group 4's operands and store nothing.  They leave here: EXEC never holds them again (every asm block restores the EXEC it was
-    // entered with; no DPP or ballot of a live lane reads them: they are a quad of their own), and their multiply-adds stop drawing power.
-    if (WGW == 1 && lane >= GROUPS * LIG) return;
-#endif
-#if ZKP_COOP_ASM
+    // lanes 60..63 own nothing (five checks of twelve lanes): they leave here, so that their multiply-adds draw no power.  EXEC never
+    // holds them again (every asm block restores the EXEC it was entered with; no DPP or ballot of a live lane reads them: they are a
+    // quad of their own).
+    if (lane >= GROUPS * LIG) return;
     // the lanes that own a coefficient of a live check: wave-uniform (two SGPRs), the store mask of the asm MULACC block
     ZKP_LANE_CTX();
     const unsigned long long act_lanes = __ballot(active);
-#endif
 
     // the step headers are read-only and wave-uniform: through the constant address space they become scalar loads
     // (s_load_dwordx4 into SGPRs, scalar cache) instead of a vector load + readfirstlane per word
@@ -275,19 +216,14 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
         if (op == OP_END) break;
         ZKP_LANE_CTX();
         if (op == OP_MULACC) {
-            // software pipeline: table words two terms ahead, LDS operands one term ahead, so the
-            // 196 multiply-adds of term t cover the latency of everything term t+1 needs
             const uint32_t h3 = hdr[4 * pc + 3];
             const uint32_t T = arg;
-#if ZKP_COOP_ASM
             // one inline-asm block (tools/coopasm.py): term loop on two operand register sets with resolved per-lane LDS
-            // addresses, Karatsuba fold, row-pipelined Montgomery reduction, limb extraction; the same integers as
-            // acc_mul_k / acc_fold / acc_reduce of the C++ variant below
-            const uint4* rt = A.rtbl + (size_t)(off / LIG) * (64 * WGW);
+            // addresses, Karatsuba fold, row-pipelined Montgomery reduction, limb extraction
+            const uint4* rt = A.rtbl + (size_t)(off / LIG) * 64;
             // round 4: a step without epilogue stores its result and its companion form from inside the block (resolved
-            // addresses in the flag row of the table, the active lanes as a mask); with several wavefronts per workgroup the
-            // stores must wait for the workgroup's fence, so they stay behind the block
-            const uint32_t nost = (h1 & 1u) | (WGW > 1 ? 1u : 0u);
+            // addresses in the flag row of the table, the active lanes as a mask)
+            const uint32_t nost = h1 & 1u;
             int32_t r[NL];
             {
                 static_assert(NL == 14, "the generated block is for 14 limbs");
@@ -296,7 +232,7 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
                              : ZKP_MULACC_OUTS(r)
                              : [rt] "s"(rt), [T] "s"(T), [h1] "s"(h1), [h3] "s"(h3), [lane16] "v"(lane * 16),   // (rematerialised from the lane number: not a live value)
                                [act] "s"(act_lanes), [nost] "s"(nost),
-                               [ps1] "i"(PS * 16), [ps2] "i"(PS * 32), [ps3] "i"(PS * 48), [row] "i"(1024 * WGW),
+                               [ps1] "i"(PS * 16), [ps2] "i"(PS * 32), [ps3] "i"(PS * 48), [row] "i"(1024),
                                [p0] "s"(PL[0]), [p1] "s"(PL[1]), [p2] "s"(PL[2]), [p3] "s"(PL[3]), [p4] "s"(PL[4]), [p5] "s"(PL[5]), [p6] "s"(PL[6]),
                                [p7] "s"(PL[7]), [p8] "s"(PL[8]), [p9] "s"(PL[9]), [p10] "s"(PL[10]), [p11] "s"(PL[11]), [p12] "s"(PL[12]),
                                [p13] "s"(PL[13]), [pinv] "s"(ZKP28_PINV)
@@ -305,83 +241,9 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
             if (!nost) { pc++; continue; }
             ZKP_LANE_CTX();
             const uint32_t ew = tbl[off + T * LIG + lig];
-#else
-            Acc acc;
-            acc_zero(acc);
-#if ZKP_COOP_KARATSUBA
-            AccMid mid;
-            mid_zero(mid);
-#endif
-            // software pipeline: the table word of term t + 2 is requested at the top of term t and taken over at its
-            // end, behind the multiply-adds (the table is padded: the read past the last term is harmless); the LDS
-            // operands of term t + 1 are requested before the multiply-adds of term t
-            uint32_t w = tbl[off + lig];
-            uint32_t wn = tbl[off + LIG + lig];
-            const uint32_t ew = tbl[off + T * LIG + lig];
-            int32_t xa[NL], xb[NL];
-            ld(xa, w & 127);
-            ld(xb, (w >> 14) & 127);
-#pragma unroll 1
-            for (uint32_t t = 0; t < T; t++) {
-                const uint32_t w2 = tbl[off + (t + 2) * LIG + lig];
-                const bool no_a2 = (h3 >> t) & 1, no_b2 = (h3 >> (12 + t)) & 1;   // wave-uniform
-                const bool no_neg = (h1 >> (4 + t)) & 1;                          // no lane negates this term
-                const bool has_da = (h1 >> (16 + t)) & 1;                         // some lane doubles its A operand
-                const int32_t ma = -(int32_t)((w >> 28) & 1), mb = -(int32_t)((w >> 29) & 1), mn = -(int32_t)((w >> 30) & 1);
-                int32_t a[NL], b[NL];
-                if (no_a2 && no_neg) {
-#pragma unroll
-                    for (int i = 0; i < NL; i++) a[i] = xa[i];
-                } else if (no_a2) {
-#pragma unroll
-                    for (int i = 0; i < NL; i++) a[i] = (xa[i] ^ mn) - mn;
-                } else if (no_neg) {
-                    int32_t x2[NL];
-                    ld(x2, (w >> 7) & 127);
-#pragma unroll
-                    for (int i = 0; i < NL; i++) a[i] = xa[i] + ((x2[i] ^ ma) - ma);
-                } else {
-                    int32_t x2[NL];
-                    ld(x2, (w >> 7) & 127);
-#pragma unroll
-                    for (int i = 0; i < NL; i++) a[i] = ((xa[i] + ((x2[i] ^ ma) - ma)) ^ mn) - mn;
-                }
-                if (has_da) {
-                    const uint32_t sh = w >> 31;
-#pragma unroll
-                    for (int i = 0; i < NL; i++) a[i] = (int32_t)((uint32_t)a[i] << sh);
-                }
-                if (no_b2) {
-#pragma unroll
-                    for (int i = 0; i < NL; i++) b[i] = xb[i];
-                } else {
-                    int32_t x2[NL];
-                    ld(x2, (w >> 21) & 127);
-#pragma unroll
-                    for (int i = 0; i < NL; i++) b[i] = xb[i] + ((x2[i] ^ mb) - mb);
-                }
-                if (t + 1 < T) {
-                    ld(xa, wn & 127);
-                    ld(xb, (wn >> 14) & 127);
-                }
-#if ZKP_COOP_KARATSUBA
-                acc_mul_k(acc, mid, a, b);
-#else
-                acc_mul(acc, a, b);
-#endif
-                w = wn;
-                wn = w2;
-            }
-#if ZKP_COOP_KARATSUBA
-            acc_fold(acc, mid);
-#endif
-            int32_t r[NL];
-            acc_reduce(r, acc);
-#endif
             if (h1 & 1) {  // step-uniform: epilogue dst = alpha r + beta E, renormalised
                 int32_t e[NL];
                 ld(e, (ew >> 16) & 127);
-                ZKP_WG_FENCE();   // every operand of the step has been read
                 const int32_t al = sext4((ew >> 8) & 15), be = sext4((ew >> 12) & 15);
                 // value renormalisation folded in: q = round(value / p) from the top limb of the combination
                 // (the lower limbs are normalised: their carries cannot move q), then ONE weak normalisation
@@ -390,8 +252,6 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
 #pragma unroll
                 for (int i = 0; i < NL; i++) r[i] = al * r[i] + be * e[i] - q * K_PBAL[i];
                 weak_norm(r);
-            } else {
-                ZKP_WG_FENCE();
             }
             if (active && ((ew >> 7) & 1)) lds_st(lds, gbase + (int)(ew & 63), PS, r);
             if (h1 & 2) {  // step-uniform: companion store of a squaring run - the even lane of an Fp2 coefficient keeps
@@ -405,7 +265,6 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
                 }
                 if (active && ((ew >> 29) & 1)) lds_st(lds, gbase + (int)((ew >> 23) & 63), PS, c2);
             }
-            ZKP_WG_FENCE();
         } else if (op == OP_LIN) {
             int32_t r[NL];
 #pragma unroll
@@ -422,9 +281,7 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
             weak_norm(r);
             if (h1 & 1) vred(r);   // only where the generator's static value bound asks for it
             const uint32_t ew = tbl[off + arg * LIG + lig];
-            ZKP_WG_FENCE();
             if (active && ((ew >> 7) & 1)) lds_st(lds, gbase + (int)(ew & 63), PS, r);
-            ZKP_WG_FENCE();
         } else if (op == OP_GLOAD) {
             const uint32_t w = tbl[off + lig];
             const uint32_t idx = w >> 8;
@@ -444,11 +301,7 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
                     }
                 } else {
                     size_t rec;
-#ifdef ZKP_EXP_TRAFFIC4L   // timing-only experiment (wrong results): four checks read one line record
-                    if (arg == K_LINE) rec = ((size_t)cursor * A.k * 6 + pair6 + idx) * n_checks + (check & ~3u);
-#else
                     if (arg == K_LINE) rec = ((size_t)cursor * A.k * 6 + pair6 + idx) * n_checks + check;   // line buffer: this launch's checks only
-#endif
                     else rec = (size_t)(idx + A.st_off) * A.nc + check;
                     const int4* src = (arg == K_LINE ? A.lines : (const int4*)A.state) + rec * 4;
                     int4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3];
@@ -457,7 +310,6 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
                 }
                 lds_st(lds, gbase + (int)(w & 63), PS, x);
             }
-            ZKP_WG_FENCE();
             cursor += h1;
         } else if (op == OP_GSTORE) {
             const uint32_t w = tbl[off + lig];
@@ -493,16 +345,7 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
 #pragma unroll
                     for (int i = 1; i < NL; i++) d |= f[i];
                     const unsigned long long good = __ballot((d == 0) || !part);
-                    unsigned gm;
-                    if (WGW == 1) {
-                        gm = (unsigned)((good >> (grp * LIG)) & 0xfffu);
-                    } else {   // check 15: four lanes in each wavefront, their flags meet behind the LDS image
-                        uint32_t* tailf = (uint32_t*)(lds + 4 * PS);
-                        const int wv = lane >> 6, g0 = ((lane & 63) * 43) >> 9;
-                        if ((lane & 63) == 60) tailf[wv] = (uint32_t)(good >> 60) & 0xfu;
-                        __syncthreads();
-                        gm = g0 < 5 ? (unsigned)((good >> (g0 * LIG)) & 0xfffu) : (tailf[0] | tailf[1] << 4 | tailf[2] << 8);
-                    }
+                    const unsigned gm = (unsigned)((good >> (grp * LIG)) & 0xfffu);
                     if (active && lig == 0) {
                         const bool is_one = gm == 0xfffu;
                         if (A.ok) A.ok[check] = is_one ? 1 : 0;
@@ -510,7 +353,6 @@ __global__ void __launch_bounds__(64 * WGW, ZKP_COOP_WAVES) k_coop(CoopArgs A) {
                     }
                 }
             }
-            ZKP_WG_FENCE();   // a GLOAD step behind this one stores without a fence of its own
         } else if (op == OP_LOOP) {
             loop_pc = pc + 1;
             loop_left = (int)h1;
@@ -579,19 +421,10 @@ __device__ __forceinline__ void rec_load(Fp28& x, const int4* src) {
 // snapshots (one shared batched inversion), and the step program squares on uncompressed through bits 60, 62, 63 and
 // multiplies the six powers.  tools/coopgen.py emu_ksq / emu_kdec are the limb-exact models of these kernels.
 constexpr int KS_CHECKS = 16;
-#ifndef ZKP_KSQ_ASM
-#define ZKP_KSQ_ASM ZKP_COOP_ASM   // a squaring of k_ksq behind its operand forms as ONE asm block (tools/coopasm.py generate_ksq): the Fp2 product
-                                   // as Karatsuba terms + tail on register operands (980 multiply-adds instead of the 1,204 of two
-                                   // product-scanning multiplies), DPP combinations, both carry chains, parking; 0: the compiled loop
-                                   // around mont_mul_ps, the A/B baseline
-#endif
-#ifndef ZKP_KSQ_WAVES
-#if ZKP_KSQ_ASM
-#define ZKP_KSQ_WAVES 3            // the block pins 162 VGPRs (four operands, both results' homes, 78 accumulator registers)
-#else
-#define ZKP_KSQ_WAVES 4
-#endif
-#endif
+// a squaring of k_ksq behind its operand forms is ONE asm block (tools/coopasm.py generate_ksq): the Fp2 product as Karatsuba terms
+// + tail on register operands (980 multiply-adds instead of the 1,204 of two product-scanning multiplies), DPP combinations, both
+// carry chains, parking.  The block pins 162 VGPRs (four operands, both results' homes, 78 accumulator registers): three waves per SIMD
+constexpr int KSQ_WAVES = 3;
 
 __device__ __forceinline__ void park_st(int4* xch, int lane, const int32_t* re, const int32_t* im) {
     xch[0 * 64 + lane] = make_int4(re[0], re[1], re[2], re[3]);
@@ -602,47 +435,10 @@ __device__ __forceinline__ void park_st(int4* xch, int lane, const int32_t* re, 
     xch[5 * 64 + lane] = make_int4(im[6], im[7], im[8], im[9]);
     xch[6 * 64 + lane] = make_int4(im[10], im[11], im[12], im[13]);
 }
-#if !ZKP_KSQ_ASM
-__device__ __forceinline__ void park_ld(int32_t* re, int32_t* im, const int4* xch, int lane) {
-    const int4 r0 = xch[0 * 64 + lane], r1 = xch[1 * 64 + lane], r2 = xch[2 * 64 + lane], r3 = xch[3 * 64 + lane];
-    const int4 i0 = xch[4 * 64 + lane], i1 = xch[5 * 64 + lane], i2 = xch[6 * 64 + lane];
-    re[0] = r0.x; re[1] = r0.y; re[2] = r0.z; re[3] = r0.w; re[4] = r1.x; re[5] = r1.y; re[6] = r1.z; re[7] = r1.w;
-    re[8] = r2.x; re[9] = r2.y; re[10] = r2.z; re[11] = r2.w; re[12] = r3.x; re[13] = r3.y; im[0] = r3.z; im[1] = r3.w;
-    im[2] = i0.x; im[3] = i0.y; im[4] = i0.z; im[5] = i0.w; im[6] = i1.x; im[7] = i1.y; im[8] = i1.z; im[9] = i1.w;
-    im[10] = i2.x; im[11] = i2.y; im[12] = i2.z; im[13] = i2.w;
-}
-// out = 3 t + 2 sgn x - q p (sgn = -1 where neg is all ones) with q = round(value / p) taken from the top limbs, as ONE
-// exact carry chain (balanced limbs, the top limb keeps the rest); |result| < 0.51 p.  (The chain stays in 64 bits: t is a
-// combination of three products, |limb| <= 4 * 2^27, so 3 t + 2 x - q p reaches 20 * 2^27 - a 32-bit chain was measured 1.5 %
-// faster on the pass and WRONG, round 3.)
-__device__ __forceinline__ void sq_combine(int32_t* out, const int32_t* t, const int32_t* x, int32_t neg) {
-    int32_t sx[NL];
-#pragma unroll
-    for (int i = 0; i < NL; i++) sx[i] = (x[i] ^ neg) - neg;
-    const int32_t top = 3 * t[NL - 1] + 2 * sx[NL - 1];
-    const int32_t q = ((top >> ZKP_COOP_VRED_SHIFT_IN) * ZKP_COOP_VRED_C + (1 << (ZKP_COOP_VRED_SHIFT_OUT - 1))) >> ZKP_COOP_VRED_SHIFT_OUT;
-    int64_t v = 0;
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        v += (int64_t)t[i] * 3;
-        v += (int64_t)sx[i] * 2;
-        v -= (int64_t)q * (int64_t)K_PBAL[i];
-        if (i < NL - 1) {
-            const int64_t u = v + (1ll << (W - 1));
-            out[i] = (int32_t)((uint32_t)u & (uint32_t)MASK) - (1 << (W - 1));
-            v = u >> W;
-        } else {
-            out[i] = (int32_t)v;
-        }
-    }
-}
-#define ZKP_QUAD(x, ctrl) __builtin_amdgcn_update_dpp(0, (x), (ctrl), 0xf, 0xf, false)
-#endif
 
 // operand forms of a lane's next product, in place: in (x, y) = (the lane's coefficient, its pair partner's).  B lanes: u v =
 // mine * partner as they stand.  A lanes: X = u + v and MINUS Y = -(u + xi v), u + xi v = (u0 + v0 - v1) + (u1 + v1 + v0) u with
 // v = mine on lane 0, the partner on lane 2 - the asm body wants the A product negated, and here the sign is one operand swap
-#if ZKP_KSQ_ASM
 __device__ __forceinline__ void ksq_forms(int32_t* xr, int32_t* xi, int32_t* yr, int32_t* yi, bool a_lane, bool v_mine) {
     if (a_lane) {
 #pragma unroll
@@ -656,11 +452,10 @@ __device__ __forceinline__ void ksq_forms(int32_t* xr, int32_t* xi, int32_t* yr,
         }
     }
 }
-#endif
 // nsq compressed squarings of the Fp12 value in state elements [elem_in, elem_in + 12) (only z2..z5 are read); after
 // squaring number it + 1 where bit it of snap_mask is set, (z2..z5) go to the next snapshot area: 12 elements each from
 // elem_snap on, laid out like an Fp12 value whose z0, z1 positions are left for k_kdec_b to fill.
-__global__ void __launch_bounds__(64, ZKP_KSQ_WAVES) k_ksq(int4* state, uint32_t n_checks_in, uint32_t nc, uint32_t elem_in, uint32_t elem_snap,
+__global__ void __launch_bounds__(64, KSQ_WAVES) k_ksq(int4* state, uint32_t n_checks_in, uint32_t nc, uint32_t elem_in, uint32_t elem_snap,
                                                            uint32_t nsq, uint64_t snap_mask, NDev nd) {
     extern __shared__ int4 parked[];               // 7 x 64 quads, at LDS address 0 (the asm body addresses it by lane number)
     const uint32_t n_checks = eff_n(n_checks_in, nd);
@@ -679,41 +474,19 @@ __global__ void __launch_bounds__(64, ZKP_KSQ_WAVES) k_ksq(int4* state, uint32_t
     // X, Y: the two factors of the lane's product.  `mine` is the lane's own coefficient of its pair (u, v) - v on lanes 0
     // and 3, u on lanes 1 and 2 - and `other` the pair partner's.  B lanes: u v = mine * other.  A lanes: (u + v)(u + xi v).
     int32_t xr[NL], xi[NL], yr[NL], yi[NL];
-#if !ZKP_KSQ_ASM
-    auto advance = [&](const int32_t* mr, const int32_t* mi, const int32_t* o_r, const int32_t* oi) {
-        park_st(parked, lane, mr, mi);            // the "2 z" term of the lane's next combination
-        if (b_lane) {
-#pragma unroll
-            for (int i = 0; i < NL; i++) { xr[i] = mr[i]; xi[i] = mi[i]; yr[i] = o_r[i]; yi[i] = oi[i]; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NL; i++) {
-                xr[i] = mr[i] + o_r[i];
-                xi[i] = mi[i] + oi[i];
-                yr[i] = xr[i] - (mine_is_v ? mi[i] : oi[i]);      // u + xi v = (u0 + v0 - v1) + (u1 + v0 + v1) u
-                yi[i] = xi[i] + (mine_is_v ? mr[i] : o_r[i]);
-            }
-        }
-    };
-#endif
     {
         Fp28 u0, u1, v0, v1;
         rec_load(u0, rec(elem_in + 2 * tu));
         rec_load(u1, rec(elem_in + 2 * tu + 1));
         rec_load(v0, rec(elem_in + 2 * tv));
         rec_load(v1, rec(elem_in + 2 * tv + 1));
-#if ZKP_KSQ_ASM
         const Fp28 &m0 = mine_is_v ? v0 : u0, &m1 = mine_is_v ? v1 : u1, &o0 = mine_is_v ? u0 : v0, &o1 = mine_is_v ? u1 : v1;
         park_st(parked, lane, m0.l, m1.l);
 #pragma unroll
         for (int i = 0; i < NL; i++) { xr[i] = m0.l[i]; xi[i] = m1.l[i]; yr[i] = o0.l[i]; yi[i] = o1.l[i]; }
         ksq_forms(xr, xi, yr, yi, !b_lane, r == 0);
-#else
-        if (mine_is_v) advance(v0.l, v1.l, u0.l, u1.l); else advance(u0.l, u1.l, v0.l, v1.l);
-#endif
     }
     uint32_t snap = elem_snap;
-#if ZKP_KSQ_ASM
     // One inline-asm block per squaring (tools/coopasm.py generate_ksq): the Fp2 product, the other pair's products by DPP, the
     // lane-role combinations, both carry chains, the parking of the new coefficient and the pair partner's coefficient by DPP.
     // In: X = xr + xi u, Y = yr + yi u.  Out: the lane's new coefficient in (xr, xi), its partner's in (yr, yi) - the
@@ -746,11 +519,7 @@ __global__ void __launch_bounds__(64, ZKP_KSQ_WAVES) k_ksq(int4* state, uint32_t
             int4* const st_ = state + (size_t)(chk_ < n_checks ? chk_ : n_checks - 1) * 4;
             auto rec_ = [&](uint32_t e) -> int4* { return st_ + (size_t)e * nc * 4; };
             const int tu_ = (l_ & 2) ? 1 : 3, tv_ = (l_ & 2) ? 5 : 2;
-#if defined(ZKP_EXP_TRAFFIC4) && (ZKP_EXP_TRAFFIC4 & 1)     // timing-only experiment (wrong results): a quarter of the snapshot records is written
-            if (chk_ < n_checks && a_lane && (chk_ & 3) == 0) {
-#else
             if (chk_ < n_checks && a_lane) {
-#endif
                 Fp28 o;
 #pragma unroll
                 for (int i = 0; i < NL; i++) o.l[i] = xr[i];
@@ -769,68 +538,6 @@ __global__ void __launch_bounds__(64, ZKP_KSQ_WAVES) k_ksq(int4* state, uint32_t
         }
         ksq_forms(xr, xi, yr, yi, a_lane, v_mine);
     }
-#else
-#pragma unroll 1
-    for (uint32_t it = 0; it < nsq; it++) {
-        int32_t sre[NL], sim[NL];
-        // X Y = (X0 Y0 - X1 Y1) + (X0 Y1 + X1 Y0) u, one reduction per coefficient
-        mont_mul_ps<true>(sim, xr, yi, xi, yr);
-#pragma unroll
-        for (int i = 0; i < NL; i++) xi[i] = -xi[i];
-        mont_mul_ps<true>(sre, xr, yr, xi, yi);
-        // the other pair's products: A from its even lane, B from its odd lane.  The DPP reads stay outside the lane-role
-        // branches: a DPP read from a lane that the branch has switched off returns nothing.
-        int32_t tr[NL], ti[NL];
-        {
-            int32_t ar[NL], ai[NL], br[NL], bi[NL];
-#pragma unroll
-            for (int i = 0; i < NL; i++) {
-                ar[i] = ZKP_QUAD(sre[i], 0x0A);   // quad_perm [2,2,0,0]
-                ai[i] = ZKP_QUAD(sim[i], 0x0A);
-                br[i] = ZKP_QUAD(sre[i], 0x5F);   // quad_perm [3,3,1,1]
-                bi[i] = ZKP_QUAD(sim[i], 0x5F);
-            }
-            if (!b_lane) {         // 3 (A - (1 + xi) B) - 2 old,  (1 + xi) = 2 + u
-#pragma unroll
-                for (int i = 0; i < NL; i++) { tr[i] = ar[i] - 2 * br[i] + bi[i]; ti[i] = ai[i] - br[i] - 2 * bi[i]; }
-            } else if (r == 1) {   // 3 xi (2 B) + 2 old
-#pragma unroll
-                for (int i = 0; i < NL; i++) { tr[i] = 2 * (br[i] - bi[i]); ti[i] = 2 * (br[i] + bi[i]); }
-            } else {               // 3 (2 B) + 2 old
-#pragma unroll
-                for (int i = 0; i < NL; i++) { tr[i] = 2 * br[i]; ti[i] = 2 * bi[i]; }
-            }
-        }
-        int32_t or_[NL], oi[NL];
-        park_ld(or_, oi, parked, lane);
-        const int32_t neg = b_lane ? 0 : -1;
-        sq_combine(sre, tr, or_, neg);
-        sq_combine(sim, ti, oi, neg);
-        // the pair partner's new coefficient completes (u', v')
-        int32_t pr[NL], pi[NL];
-#pragma unroll
-        for (int i = 0; i < NL; i++) { pr[i] = ZKP_QUAD(sre[i], 0xB1); pi[i] = ZKP_QUAD(sim[i], 0xB1); }   // quad_perm [1,0,3,2]
-        if (it < 64 && ((snap_mask >> it) & 1)) {      // wave-uniform (a 64-bit shift by 64 or more is undefined)
-            if (active && !b_lane) {      // lane 0 holds (v, u) = (mine, partner), lane 2 (u, v)
-                Fp28 o;
-#pragma unroll
-                for (int i = 0; i < NL; i++) o.l[i] = sre[i];
-                rec_store(rec(snap + 2 * (mine_is_v ? tv : tu)), o);
-#pragma unroll
-                for (int i = 0; i < NL; i++) o.l[i] = sim[i];
-                rec_store(rec(snap + 2 * (mine_is_v ? tv : tu) + 1), o);
-#pragma unroll
-                for (int i = 0; i < NL; i++) o.l[i] = pr[i];
-                rec_store(rec(snap + 2 * (mine_is_v ? tu : tv)), o);
-#pragma unroll
-                for (int i = 0; i < NL; i++) o.l[i] = pi[i];
-                rec_store(rec(snap + 2 * (mine_is_v ? tu : tv) + 1), o);
-            }
-            snap += 12;
-        }
-        advance(sre, sim, pr, pi);
-    }
-#endif
 }
 
 // ---- two lanes per pair: lane parity c selects the Fp2 coefficient a value's lane holds ------------------
@@ -840,15 +547,9 @@ __device__ __forceinline__ void swap_pair(Fp28& o, const Fp28& x) {
 #pragma unroll
     for (int i = 0; i < NL; i++) o.l[i] = __builtin_amdgcn_update_dpp(0, x.l[i], 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
 }
-#ifndef ZKP_PREP_KARATSUBA
-#define ZKP_PREP_KARATSUBA 0   // Karatsuba product blocks (147 multiply-adds instead of 196) in the by-value routines: bit-exact, measured
-                               // round 3: k_prep_lines<true> 8.03-8.16 against 8.08-8.09 ms per 2^18 pairs - the 13 extra columns cost
-                               // the callers 29 spilled registers (0 without) and k_kdec_a/b their third wavefront; not the default
-#endif
-#ifndef ZKP_PREP_PS
-#define ZKP_PREP_PS 0   // product-scanning multiply in the by-value routines: measured +0.3 % time on the 2^20 pass (at two waves
-                        // per SIMD the one-column dependency chains are not covered); the accumulator form stays
-#endif
+// The by-value routines multiply in the schoolbook accumulator form (acc_mul).  Measured in round 3: Karatsuba product blocks (147
+// multiply-adds instead of 196) cost their callers 29 spilled registers and k_kdec_a / k_kdec_b their third wavefront for no gain; the
+// product-scanning multiply cost +0.3 % on the 2^20 pass (at two waves per SIMD its one-column dependency chains are not covered).
 // r = coefficient c of (a0 + a1 u)^2 :  c=0: (a0 + a1)(a0 - a1) ;  c=1: (2 a0) a1
 // Operands and results travel BY VALUE (VGPRs): with pointers every temporary lives in scratch memory and
 // the kernel becomes HBM-bound on its own stack traffic (measured: 50 GB per 2^17 pairs).
@@ -861,22 +562,10 @@ __device__ __attribute__((noinline)) Fp28 c_sqr(Fp28 mine, int c) {
         x[i] = o.l[i] + (c ? o.l[i] : mine.l[i]);
         y[i] = mine.l[i] - (c ? 0 : o.l[i]);
     }
-#if ZKP_PREP_PS
-    mont_mul_ps<false>(r.l, x, y, x, y);
-#elif ZKP_PREP_KARATSUBA
-    Acc acc;
-    AccMid mid;
-    acc_zero(acc);
-    mid_zero(mid);
-    acc_mul_k(acc, mid, x, y);
-    acc_fold(acc, mid);
-    acc_reduce(r.l, acc);
-#else
     Acc acc;
     acc_zero(acc);
     acc_mul(acc, x, y);
     acc_reduce(r.l, acc);
-#endif
     return r;
 }
 // r = coefficient c of (a0 + a1 u)(b0 + b1 u) :  c=0: a0 b0 - a1 b1 ;  c=1: a0 b1 + a1 b0  (one reduction)
@@ -901,69 +590,18 @@ __device__ __attribute__((noinline)) Fp28 c_mul_q(Fp28 ma, int4 q0, int4 q1, int
         x1[i] = c ? ao.l[i] : ma.l[i];
         x2[i] = c ? ma.l[i] : -ao.l[i];
     }
-#if ZKP_PREP_PS
-    mont_mul_ps<true>(r.l, x1, mb.l, x2, bo.l);
-#elif ZKP_PREP_KARATSUBA
-    Acc acc;
-    AccMid mid;
-    acc_zero(acc);
-    mid_zero(mid);
-    acc_mul_k(acc, mid, x1, mb.l);
-    acc_mul_k(acc, mid, x2, bo.l);
-    acc_fold(acc, mid);
-    acc_reduce(r.l, acc);
-#else
     Acc acc;
     acc_zero(acc);
     acc_mul(acc, x1, mb.l);
     acc_mul(acc, x2, bo.l);
     acc_reduce(r.l, acc);
-#endif
     return r;
 }
 __device__ __forceinline__ Fp28 c_mul(const Fp28& ma, const Fp28& mb, int c) { return c_mul_q(ma, FP28_AS_QUADS(mb), c); }
-// r = coefficient c of s^2 - 12 e^2 with ONE reduction (the Y' = (B + F)^2 - 3 (2 E)^2 of the homogeneous doubling step): both
-// squarings' operand forms as in c_sqr, the second product's first factor normalised (one pass) and scaled by -12.
-// Column budget (units of 2^54 per product of limbs): s normalised, e renormalised: 2 * 2 + 12 * 2 = 28 <= 30.
-[[maybe_unused]] __device__ __attribute__((noinline)) Fp28 c_sqr_sub12sqr_q(Fp28 s, int4 q0, int4 q1, int4 q2, int4 q3, int c) {
-    Fp28 e, os, oe, r;
-    fp28_unpack(e, q0, q1, q2, q3);
-    swap_pair(os, s);
-    swap_pair(oe, e);
-    int32_t xs[NL], ys[NL], xe[NL], ye[NL];
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        xs[i] = os.l[i] + (c ? os.l[i] : s.l[i]);
-        ys[i] = s.l[i] - (c ? 0 : os.l[i]);
-        xe[i] = oe.l[i] + (c ? oe.l[i] : e.l[i]);
-        ye[i] = e.l[i] - (c ? 0 : oe.l[i]);
-    }
-    weak_norm(xe);
-#pragma unroll
-    for (int i = 0; i < NL; i++) xe[i] *= -12;
-    Acc acc;
-    acc_zero(acc);
-    acc_mul(acc, xs, ys);
-    acc_mul(acc, xe, ye);
-    acc_reduce(r.l, acc);
-    return r;
-}
 __device__ __attribute__((noinline)) Fp28 f_mul_q(Fp28 a, int4 q0, int4 q1, int4 q2, int4 q3) {
     Fp28 b, r;
     fp28_unpack(b, q0, q1, q2, q3);
-#if ZKP_PREP_PS
-    mont_mul_ps<false>(r.l, a.l, b.l, a.l, b.l);
-#elif ZKP_PREP_KARATSUBA
-    Acc acc;
-    AccMid mid;
-    acc_zero(acc);
-    mid_zero(mid);
-    acc_mul_k(acc, mid, a.l, b.l);
-    acc_fold(acc, mid);
-    acc_reduce(r.l, acc);
-#else
     fp28_mul(r, a, b);
-#endif
     return r;
 }
 __device__ __forceinline__ Fp28 f_mul_v(const Fp28& a, const Fp28& b) { return f_mul_q(a, FP28_AS_QUADS(b)); }
@@ -979,249 +617,15 @@ __device__ __forceinline__ Fp28 c_neg(const Fp28& a) {
 
 struct G2C { Fp28 x, y, z; };   // this lane's coefficient of the three Jacobian coordinates
 
-// ---- lazily normalised arithmetic of the doubling step, with its bounds carried in the TYPE: Bd<L, LO, HI> is a value whose
-// limbs are at most L (2^27 + 16) in magnitude and whose value lies in [LO, HI] units of p / 64.  Additions, subtractions and
-// doublings are plain limb-wise operations (no carry pass); every consumer states what it can take as a static_assert, so a
-// formula that would overflow an int32 limb, a 64-bit product column or the value renormalisation does not compile:
-//   * a product column holds 14 * sum(La Lb) * 2^54 < 2^63  =>  sum(La Lb) <= 30 (zkp_fp28.hpp); the operand forms of the
-//     Fp2 squaring double the limb bound (x0 + x1, x0 - x1, 2 x0);
-//   * a Montgomery reduction returns (-0.05 p, 1.05 p) while sum(|a| |b|) <= 100 p^2 (R = 2^392 = 2521 p);
-//   * the one-pass normalisation adds 2^27 to a limb: L <= 14;  the value renormalisation subtracts q p first, q <= |v| / p + 1/2,
-//     p's balanced limbs are at most 2^27: L + q + 1 <= 15.
-template <int L, int LO, int HI> struct Bd { Fp28 v; };
-[[maybe_unused]] constexpr int bd_k(int lo, int hi) { return -lo > hi ? -lo : hi; }
-typedef Bd<1, -4, 68> BdRed;     // a reduced product
-typedef Bd<1, -33, 33> BdVred;   // after the value renormalisation (|v| <= 0.51 p)
-template <int L1, int A1, int B1, int L2, int A2, int B2>
-__device__ __forceinline__ Bd<L1 + L2, A1 + A2, B1 + B2> bd_add(const Bd<L1, A1, B1>& a, const Bd<L2, A2, B2>& b) {
-    Bd<L1 + L2, A1 + A2, B1 + B2> r;
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.v.l[i] = a.v.l[i] + b.v.l[i];
-    return r;
-}
-template <int L1, int A1, int B1, int L2, int A2, int B2>
-__device__ __forceinline__ Bd<L1 + L2, A1 - B2, B1 - A2> bd_sub(const Bd<L1, A1, B1>& a, const Bd<L2, A2, B2>& b) {
-    Bd<L1 + L2, A1 - B2, B1 - A2> r;
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.v.l[i] = a.v.l[i] - b.v.l[i];
-    return r;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ Bd<2 * L, 2 * A, 2 * B> bd_dbl(const Bd<L, A, B>& a) {
-    Bd<2 * L, 2 * A, 2 * B> r;
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.v.l[i] = a.v.l[i] + a.v.l[i];
-    return r;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ Bd<L, -B, -A> bd_neg(const Bd<L, A, B>& a) {
-    Bd<L, -B, -A> r;
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.v.l[i] = -a.v.l[i];
-    return r;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ Bd<1, A, B> bd_norm(const Bd<L, A, B>& a) {
-    static_assert(L <= 14, "one-pass normalisation: |limb| + 2^27 must stay below 2^31");
-    Bd<1, A, B> r;
-    r.v = a.v;
-    weak_norm(r.v.l);
-    return r;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ BdVred bd_vred(const Bd<L, A, B>& a) {
-    static_assert(L + (bd_k(A, B) + 32 + 63) / 64 + 1 <= 15, "value renormalisation: |limb| + q 2^27 + 2^27 must stay below 2^31");
-    BdVred r;
-    r.v = a.v;
-    vred(r.v.l);
-    return r;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ BdRed bd_sqr(const Bd<L, A, B>& a, int c) {
-    static_assert(4 * L * L <= 30, "column budget of the Fp2 squaring (its operand forms double the limbs)");
-    static_assert(4 * bd_k(A, B) * bd_k(A, B) <= 100 * 64 * 64, "value budget of the reduction");
-    BdRed r;
-    r.v = c_sqr(a.v, c);
-    return r;
-}
-template <int L1, int A1, int B1, int L2, int A2, int B2>
-__device__ __forceinline__ BdRed bd_mul(const Bd<L1, A1, B1>& a, const Bd<L2, A2, B2>& b, int c) {
-    static_assert(2 * L1 * L2 <= 30, "column budget of the Fp2 product (two products per coefficient)");
-    static_assert(2 * bd_k(A1, B1) * bd_k(A2, B2) <= 100 * 64 * 64, "value budget of the reduction");
-    BdRed r;
-    r.v = c_mul(a.v, b.v, c);
-    return r;
-}
-// a^2 - 12 e^2, one reduction (c_sqr_sub12sqr_q): a normalised, e renormalised
-template <int A, int B>
-__device__ __forceinline__ BdRed bd_sqr_sub12sqr(const Bd<1, A, B>& a, const BdVred& e, int c) {
-    static_assert(4 * bd_k(A, B) * bd_k(A, B) + 12 * 4 * 33 * 33 <= 100 * 64 * 64, "value budget of the reduction");
-    BdRed r;
-    r.v = c_sqr_sub12sqr_q(a.v, FP28_AS_QUADS(e.v), c);
-    return r;
-}
-// static checks for values that leave the typed code as plain Fp28
-template <int L, int A, int B>
-__device__ __forceinline__ const Fp28& bd_for_vred(const Bd<L, A, B>& a) {
-    static_assert(L + (bd_k(A, B) + 32 + 63) / 64 + 1 <= 15, "value renormalisation: |limb| + q 2^27 + 2^27 must stay below 2^31");
-    return a.v;
-}
-template <int L, int A, int B>
-__device__ __forceinline__ const Fp28& bd_for_fmul(const Bd<L, A, B>& a) {   // multiplied by a reduced Fp value (limbs <= 2^27, |v| <= 1.05 p)
-    static_assert(L <= 30 && bd_k(A, B) * 68 <= 100 * 64 * 64, "budgets of the Fp product");
-    return a.v;
-}
-
-// ePrint 2010/354 Alg. 26; hands this lane's coefficient of the line (c0, c1, c2) to the three sinks and advances r.
-// The operations are ordered so that few values are live at any call: a by-value call keeps the caller's values in
-// the ~108 callee-saved VGPRs only, everything beyond that is spilled around EVERY call (that was 100 GB of scratch
-// traffic per 2^20 pairs); the line coefficients leave through the sinks as soon as they exist.  Three one-pass
-// normalisations per step are left (24 when every addition normalised its result): the types prove the rest unnecessary.
-// sink_l2 renormalises its argument; sink_l0 / sink_l1 multiply theirs by a reduced Fp value.
-template <class S0, class S1, class S2>
-__device__ __forceinline__ void dbl_step(G2C& r, int c, S0&& sink_l0, S1&& sink_l1, S2&& sink_l2) {
-    Bd<1, -33, 68> x, y, z;    // renormalised by the previous step, or a reduced input coordinate (the first step)
-    x.v = r.x; y.v = r.y; z.v = r.z;
-    auto zsq = bd_sqr(z, c);
-    auto tmp1 = bd_sqr(y, c);
-    auto nz = bd_sub(bd_sub(bd_sqr(bd_add(z, y), c), tmp1), zsq);
-    sink_l0(bd_for_fmul(bd_dbl(bd_mul(nz, zsq, c))));
-    auto tmp0 = bd_sqr(x, c);
-    auto tmp4 = bd_norm(bd_add(bd_add(tmp0, tmp0), tmp0));
-    sink_l1(bd_for_fmul(bd_neg(bd_dbl(bd_mul(tmp4, zsq, c)))));
-    auto tmp5 = bd_sqr(tmp4, c);
-    {
-        auto tmp6 = bd_sub(bd_sub(bd_sqr(bd_add(x, tmp4), c), tmp0), tmp5);
-        sink_l2(bd_for_vred(bd_sub(tmp6, bd_dbl(bd_dbl(tmp1)))));
-    }
-    auto tmp3s = bd_sqr(bd_add(tmp1, x), c);
-    auto tmp2 = bd_sqr(tmp1, c);
-    auto tmp3 = bd_norm(bd_dbl(bd_sub(bd_sub(tmp3s, tmp0), tmp2)));
-    auto nx = bd_sub(bd_sub(tmp5, tmp3), tmp3);
-    auto ny = bd_sub(bd_mul(bd_sub(tmp3, nx), tmp4, c), bd_norm(bd_dbl(bd_dbl(bd_dbl(tmp2)))));
-    r.x = bd_vred(nx).v;
-    r.y = bd_vred(ny).v;
-    r.z = bd_vred(nz).v;
-}
-// ePrint 2010/354 Alg. 27
-[[maybe_unused]] __device__ __forceinline__ void add_step(Fp28& l0, Fp28& l1, Fp28& l2, G2C& r, const Fp28& qx, const Fp28& qy, int c) {
-    Fp28 zsq = c_sqr(r.z, c);
-    Fp28 ysq = c_sqr(qy, c);
-    Fp28 t0 = c_mul(zsq, qx, c);
-    Fp28 t1 = c_sqr(c_add(qy, r.z), c);
-    t1 = c_mul(c_sub(c_sub(t1, ysq), zsq), zsq, c);
-    Fp28 t2 = c_sub(t0, r.x);
-    Fp28 t3 = c_sqr(t2, c);
-    Fp28 t4 = c_dbl(c_dbl(t3));
-    Fp28 t5 = c_mul(t4, t2, c);
-    Fp28 t6 = c_sub(c_sub(t1, r.y), r.y);
-    Fp28 t9 = c_mul(t6, qx, c);
-    Fp28 t7 = c_mul(t4, r.x, c);
-    Fp28 nx = c_sqr(t6, c);
-    nx = c_sub(c_sub(c_sub(nx, t5), t7), t7);
-    Fp28 nz = c_sqr(c_add(r.z, t2), c);
-    nz = c_sub(c_sub(nz, zsq), t3);
-    Fp28 t10 = c_add(qy, nz);
-    Fp28 t8 = c_mul(c_sub(t7, nx), t6, c);
-    t0 = c_dbl(c_mul(r.y, t5, c));
-    Fp28 ny = c_sub(t8, t0);
-    t10 = c_sub(c_sqr(t10, c), ysq);
-    t10 = c_sub(t10, c_sqr(nz, c));
-    t9 = c_sub(c_dbl(t9), t10);
-    t10 = c_dbl(nz);
-    t6 = c_neg(t6);
-    t1 = c_dbl(t6);
-    vred(nx.l); vred(ny.l); vred(nz.l);
-    r.x = nx; r.y = ny; r.z = nz;
-    l0 = t10; l1 = t1; l2 = t9;
-}
-
-// ---- the same two steps in homogeneous projective coordinates, for the FUSED paths only (zkp_pairing_* / zkp_pairing_check_*):
-// those expose Gt and flags, and any factor of the Miller value that lies in Fp2 dies in the final exponentiation's
-// f^(p^6 - 1), so the lines may be scaled freely and the point may live in whatever coordinates are cheapest.
-// zkp_multi_miller_loop_batch keeps the upstream-shaped value (Alg. 26 / 27 above).
-// Costello-Lange-Naehrig doubling (ePrint 2009/615; Aranha et al. ePrint 2010/526 eq. (10)) on (X : Y : W), W = 2 Z, scaled
-// by 4 so that no halving is left; b' = 4 xi (src/common.rs:69-71: B2 = (4, 4)), so 3 b' Z^2 = 3 xi W^2:
-//   B = Y^2, C = W^2, H2 = (Y + W)^2 - B - C = 2 Y W, E = 3 xi C, F = 3 E,
-//   X' = ((X + Y)^2 - X^2 - B) (B - F) = 2 X Y (B - F),   Y' = (B + F)^2 - 3 (2 E)^2,   W' = 4 B H2
-//   line (times 2 / Z): 2 (B - E)  -  6 X^2 xP  +  H2 yP        [the (c0, c1, c4) operands of mul_by_014]
-// Seven Fp2 squarings and two products: 13 products and 10 reductions per lane (the two squarings of Y' share one) against
-// 16 and 13 of Alg. 26.
-template <int L, int A, int B>
-__device__ __forceinline__ Bd<2 * L, (A - B), (A + B) < 2 * B ? 2 * B : (A + B)> bd_xi(const Bd<L, A, B>& a, int c) {
-    // (1 + u) (a0 + a1 u) = (a0 - a1) + (a0 + a1) u : this lane's coefficient, the partner's by DPP
-    Bd<2 * L, (A - B), (A + B) < 2 * B ? 2 * B : (A + B)> r;
-    Fp28 o;
-    swap_pair(o, a.v);
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.v.l[i] = c ? o.l[i] + a.v.l[i] : a.v.l[i] - o.l[i];
-    return r;
-}
-template <class S0, class S1, class S2>
-__device__ __forceinline__ void dbl_step_cln(G2C& r, int c, S0&& sink_l0, S1&& sink_l1, S2&& sink_l2) {
-    Bd<1, -33, 68> x, y, w;    // renormalised by the previous step, or a reduced input coordinate / the constant 2 (the first step)
-    x.v = r.x; y.v = r.y; w.v = r.z;
-    // ordered for few live values: at most six 14-register values across any by-value call (they live in the ~108 callee-saved
-    // VGPRs; what does not fit is spilled around every call)
-    auto B = bd_sqr(y, c);
-    auto C = bd_sqr(w, c);
-    auto H2 = bd_sub(bd_sub(bd_sqr(bd_add(y, w), c), B), C);
-    sink_l0(bd_for_fmul(H2));
-    auto nw = bd_mul(B, bd_dbl(bd_dbl(H2)), c);      // 4 B H2 with the factor on the operand: a reduced product, no renormalisation
-    auto xiC = bd_xi(C, c);
-    auto E = bd_vred(bd_add(bd_add(xiC, xiC), xiC));
-    sink_l2(bd_for_vred(bd_dbl(bd_sub(B, E))));
-    auto X2 = bd_sqr(x, c);
-    {
-        auto X6 = bd_dbl(bd_add(bd_add(X2, X2), X2));
-        sink_l1(bd_for_fmul(bd_neg(X6)));
-    }
-    auto XY2 = bd_sub(bd_sub(bd_sqr(bd_add(x, y), c), X2), B);
-    auto F = bd_add(bd_add(E, E), E);
-    auto nx = bd_mul(XY2, bd_sub(B, F), c);
-    auto ny = bd_sqr_sub12sqr(bd_norm(bd_add(B, F)), E, c);      // (B + F)^2 - 3 (2 E)^2 under one reduction
-    r.x = nx.v;                 // a reduced product is a valid input as it stands
-    r.y = ny.v;
-    r.z = nw.v;
-}
-// mixed addition T + Q on the same coordinates (Aranha et al. eq. (13), (14) with every quantity doubled: W = 2 Z):
-//   th = 2 Y - y2 W, la = 2 X - x2 W, C = th^2, D = la^2, E = la D, F = W C, G = 2 X D, H = E + F - 2 G,
-//   X' = la H, Y' = th (G - H) - 2 Y E, W' = 2 W E        line (times 2): la yP - th xP + (th x2 - la y2)
-// Five of the 68 steps: written with normalising additions, no bound bookkeeping beyond |v| < 8 p at every product.
-[[maybe_unused]] __device__ __forceinline__ void add_step_cln(Fp28& l0, Fp28& l1, Fp28& l2, G2C& r, const Fp28& qx, const Fp28& qy, int c) {
-    Fp28 th = c_sub(c_dbl(r.y), c_mul(qy, r.z, c));
-    Fp28 la = c_sub(c_dbl(r.x), c_mul(qx, r.z, c));
-    vred(th.l); vred(la.l);
-    l2 = c_sub(c_mul(th, qx, c), c_mul(la, qy, c));
-    l1 = c_neg(th);
-    l0 = la;
-    Fp28 C = c_sqr(th, c), D = c_sqr(la, c);
-    Fp28 E = c_mul(la, D, c), F = c_mul(r.z, C, c), G = c_mul(c_dbl(r.x), D, c);
-    Fp28 H = c_sub(c_add(E, F), c_dbl(G));
-    vred(H.l);
-    Fp28 GH = c_sub(G, H);
-    vred(GH.l);
-    Fp28 nx = c_mul(la, H, c);
-    Fp28 ny = c_sub(c_mul(th, GH, c), c_mul(c_dbl(r.y), E, c));
-    Fp28 nw = c_dbl(c_mul(r.z, E, c));
-    vred(ny.l); vred(nw.l);
-    r.x = nx; r.y = ny; r.z = nw;
-}
-
 // two lanes per pair: write the 68-step line stream of pair `pid` (check = pid / k, j = pid % k);
 // lane c writes the records of Fp2 coefficient c.  The k pairs are pairs j0 .. j0+k-1 of the check's k_in
 // input pairs (k_in > k when a check is processed in groups of at most eight pairs).
-#ifndef ZKP_PREP_WAVES
-#define ZKP_PREP_WAVES 2   // measured: 256 VGPRs (2 waves/SIMD) 6.6 ms, 168 -> 9.3 ms, 128 -> 11.4 ms per 2^17 pairs (spill traffic)
-#endif
-// CLN: homogeneous projective steps with freely scaled lines (fused pairing paths); otherwise the upstream-shaped Alg. 26 / 27.
-#ifdef ZKP_EXP_TRAFFIC4L
-#define ZKP_EXP_LINE_KEEP(check) (((check) & 3u) == 0)     // timing-only experiment: a quarter of the line records is written
-#else
-#define ZKP_EXP_LINE_KEEP(check) true
-#endif
+constexpr int PREP_WAVES = 2;   // measured: 256 VGPRs (2 waves/SIMD) 6.6 ms, 168 -> 9.3 ms, 128 -> 11.4 ms per 2^17 pairs (spill traffic)
+// CLN: Costello-Lange-Naehrig steps in homogeneous projective coordinates with freely scaled lines (tools/prepasm.py), for the fused
+// pairing paths only - any factor of the Miller value that lies in Fp2 dies in the final exponentiation; otherwise the upstream-shaped
+// Jacobian steps of ePrint 2010/354 Alg. 26 / 27 (zkp_multi_miller_loop_batch exposes that Miller value).
 template <bool CLN>
-__global__ void __launch_bounds__(64, ZKP_PREP_WAVES) k_prep_lines(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2,
+__global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2,
                                                        uint32_t n_pairs_in, uint32_t k, uint32_t k_in, uint32_t j0, uint32_t nc_in, int4* lines, NDev nd) {
     // nc_in checks of k pairs each (n_pairs_in = nc_in * k); with a device-resident count the launch covers the checks that exist, and
     // their number is the stride of the line records (k_coop computes the same)
@@ -1248,15 +652,6 @@ __global__ void __launch_bounds__(64, ZKP_PREP_WAVES) k_prep_lines(const uint64_
         park[(v * 4 + 2) * 64 + lane] = make_int4(x.l[8], x.l[9], x.l[10], x.l[11]);
         park[(v * 4 + 3) * 64 + lane] = make_int4(x.l[12], x.l[13], 0, 0);
     };
-    [[maybe_unused]] auto park_ld = [&](int v) -> Fp28 {
-        asm volatile("" ::: "memory");   // keep the load at its use (no hoisting out of the step loop)
-        const int4 v0 = park[(v * 4 + 0) * 64 + lane], v1 = park[(v * 4 + 1) * 64 + lane], v2 = park[(v * 4 + 2) * 64 + lane],
-                   v3 = park[(v * 4 + 3) * 64 + lane];
-        Fp28 x;
-        x.l[0] = v0.x; x.l[1] = v0.y; x.l[2] = v0.z; x.l[3] = v0.w; x.l[4] = v1.x; x.l[5] = v1.y; x.l[6] = v1.z; x.l[7] = v1.w;
-        x.l[8] = v2.x; x.l[9] = v2.y; x.l[10] = v2.z; x.l[11] = v2.w; x.l[12] = v3.x; x.l[13] = v3.y;
-        return x;
-    };
     G2C r;
     {
         Fp28 t;
@@ -1274,22 +669,6 @@ __global__ void __launch_bounds__(64, ZKP_PREP_WAVES) k_prep_lines(const uint64_
     uint32_t step = 0;
     // stream order (c2, c1 * xP, c0 * yP) = the (c0, c1, c4) operands of mul_by_014; a pair with an infinity streams
     // the neutral line (1, 0, 0)
-#if !ZKP_PREP_ASM
-    auto put = [&](uint32_t e, const Fp28& v) {
-        if (!live_lane) return;
-        if (dead) {      // a branch, not selects: as selects the limbs of ONE stay in (spilled) registers for the whole kernel
-            Fp28 o;
-            if (e == 0 && c == 0) f_set(o, K28_ONE); else f_zero(o);
-            asm volatile("" ::: "memory");
-            rec_store(rec(step, e + c), o);
-        } else {
-            rec_store(rec(step, e + c), v);
-        }
-    };
-    auto sink_l0 = [&](const Fp28& l0) { put(4, f_mul_v(l0, park_ld(PY))); };
-    auto sink_l1 = [&](const Fp28& l1) { put(2, f_mul_v(l1, park_ld(PX))); };
-    auto sink_l2 = [&](Fp28 l2) { vred(l2.l); put(0, l2); };
-#else
     // the asm steps store the lines of live pairs without an infinity only; a pair with an infinity streams the neutral line
     // (1, 0, 0) at every step - written here, ahead of the loop, so that none of this is alive across the blocks
     if (live_lane && dead) {
@@ -1301,19 +680,17 @@ __global__ void __launch_bounds__(64, ZKP_PREP_WAVES) k_prep_lines(const uint64_
             }
         }
     }
-#endif
     // bits of |x| below its leading one: a doubling step each, an addition step after it where the bit is set
     // (the lowest bit is clear: the loop ends with the final doubling) -> 63 + 5 = 68 line records
     const uint64_t xs = 0xd201000000010000ULL;
 #pragma unroll 1
     for (int b = 62; b >= 0; b--) {
-#if ZKP_PREP_ASM
         // the step's three line records leave from inside the block (lanes of live pairs without an infinity); a pair with an
-        // infinity gets the neutral line from put() behind it
+        // infinity got the neutral lines ahead of the loop
 #define ZKP_PREP_STEP_ASM(BLOCK)                                                                                                          \
         do {                                                                                                                              \
             constexpr uint32_t PL[NL] = {ZKP28_P_LIMBS};                                                                                  \
-            const unsigned long long smask = __ballot(live_lane && !dead && ZKP_EXP_LINE_KEEP(check));                                    \
+            const unsigned long long smask = __ballot(live_lane && !dead);                                                                 \
             const uint64_t sb_ = (uint64_t)(uintptr_t)lines + (uint64_t)step * k * 6 * nc * 64;   /* wave-uniform: made scalar by hand */ \
             const char* const sbase = (const char*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(sb_ >> 32)) << 32) |  \
                                                     (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)sb_));                  \
@@ -1329,22 +706,9 @@ __global__ void __launch_bounds__(64, ZKP_PREP_WAVES) k_prep_lines(const uint64_
         static_assert(NL == 14, "the generated blocks are for 14 limbs");
         // <false>: the Jacobian doubling with the upstream-shaped lines (round 4: generate_jac, 18 Karatsuba blocks + 12 reductions)
         if (CLN) ZKP_PREP_STEP_ASM(ZKP_PREP_DBL_ASM); else ZKP_PREP_STEP_ASM(ZKP_PREP_JAC_DBL_ASM);
-#else
-        if (CLN) dbl_step_cln(r, c, sink_l0, sink_l1, sink_l2); else dbl_step(r, c, sink_l0, sink_l1, sink_l2);
-#endif
         step++;
         if ((xs >> b) & 1) {
-#if ZKP_PREP_ASM
             if (CLN) ZKP_PREP_STEP_ASM(ZKP_PREP_ADD_ASM); else ZKP_PREP_STEP_ASM(ZKP_PREP_JAC_ADD_ASM);
-#else
-            {
-                Fp28 l0, l1, l2;
-                if (CLN) add_step_cln(l0, l1, l2, r, park_ld(QX), park_ld(QY), c); else add_step(l0, l1, l2, r, park_ld(QX), park_ld(QY), c);
-                sink_l2(l2);
-                sink_l1(l1);
-                sink_l0(l0);
-            }
-#endif
             step++;
         }
     }
@@ -1539,7 +903,6 @@ __global__ void __launch_bounds__(64, 2) k_g2_valid28(const uint64_t* g2, const 
     if (live && c == 0 && !keep) status[i] = is_inf ? 0 : st;
 }
 
-#if ZKP_VALID_ASM
 // ---- the same two checks with the chain's steps as asm blocks (tools/validasm.py).  No exceptional case of the group law is
 // handled in the steps: each of them sends Z to 0, Z = 0 is absorbing, and a chain that ends with Z = 0 mod p is handed to
 // the generic kernel above (status VALID_REDO; launched behind this one with redo_only).  A point of the prime-order subgroup
@@ -1767,7 +1130,6 @@ __global__ void __launch_bounds__(64, 3) k_g2_valid_fast3(const uint64_t* g2, co
     }
     if (live_ && c_ == 0) status[i_] = (flags & 2) ? 0 : ((flags & 1) ? st : 1);
 }
-#endif
 
 // a^(p-2) (Fermat; reference src/fp.rs:307-319); a == 0 gives 0.  Kept as the cross-check of f_inv (ZKP_INV_FERMAT).
 __device__ __forceinline__ Fp28 f_inv_fermat(const Fp28& a) {
@@ -1800,28 +1162,10 @@ __device__ __constant__ const int32_t PL[N] = {ZKP30_P_LIMBS};
 // Round 6: the transition matrix is tracked in PACKED 16-bit halves - (u, v) in one register, (q, r) in another - over three runs of ten steps
 // (entries <= 2^10), and the three 2 x 2 matrices are multiplied together afterwards (24-bit multiplies; the products wrap mod 2^32 and
 // the true entries are <= 2^30).  A conditional negation / masked addition / doubling of BOTH entries of a row is one v_pk_* instruction:
-// 19 instead of 24 instructions per step.  The same matrix as the plain 30-step loop (ZKP_SG_PLAIN_DIVSTEPS=1 builds that one: the A/B
-// baseline), hence the same inverse: tests/test_gpu_parity.py::test_divstep_inversion_equals_fermat.
-#ifndef ZKP_SG_PLAIN_DIVSTEPS
-#define ZKP_SG_PLAIN_DIVSTEPS 0
-#endif
+// 19 instead of 24 instructions per step.  The same matrix as thirty plain division steps, hence the same inverse:
+// tests/test_gpu_parity.py::test_divstep_inversion_equals_fermat.
 typedef short zkp_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void divsteps30(int32_t& eta, uint32_t f, uint32_t g, int32_t& u_, int32_t& v_, int32_t& q_, int32_t& r_) {
-#if ZKP_SG_PLAIN_DIVSTEPS
-    uint32_t u = 1, v = 0, q = 0, r = 1, e = (uint32_t)eta;
-#pragma unroll 6      // five trips instead of thirty - a taken branch costs a lone wavefront about three of the step's 24 instructions
-    for (int i = 0; i < 30; i++) {
-        uint32_t c1 = (uint32_t)((int32_t)e >> 31);          // eta < 0  <=>  delta > 0
-        const uint32_t c2 = 0u - (g & 1u);
-        const uint32_t x = (f ^ c1) - c1, y = (u ^ c1) - c1, z = (v ^ c1) - c1;
-        g += x & c2; q += y & c2; r += z & c2;
-        c1 &= c2;                                              // delta > 0 and g odd: swap roles
-        e = (e ^ c1) - (c1 + 1u);
-        f += g & c1; u += q & c1; v += r & c1;
-        g >>= 1; u <<= 1; v <<= 1;
-    }
-    eta = (int32_t)e; u_ = (int32_t)u; v_ = (int32_t)v; q_ = (int32_t)q; r_ = (int32_t)r;
-#else
     uint32_t e = (uint32_t)eta;
     int32_t U = 1, V = 0, Q = 0, R = 1;                        // the product of the runs so far
 #pragma unroll
@@ -1853,7 +1197,6 @@ __device__ __forceinline__ void divsteps30(int32_t& eta, uint32_t f, uint32_t g,
         }
     }
     eta = (int32_t)e; u_ = U; v_ = V; q_ = Q; r_ = R;
-#endif
 }
 // Round 6: the limbs and matrix entries are pinned to 32-bit registers (an empty asm the optimiser cannot see through).  Without it
 // LLVM carries a limb as the masked 64-bit carry word it came from and expands every (int64) u * limb into the 64 x 64-bit pattern
@@ -2116,12 +1459,7 @@ __global__ void __launch_bounds__(64, 2) k_kdec_a(int4* state, uint32_t n_checks
     bool live = e < n_checks * count;
     if (!live) e = n_checks * count - 1;
     const uint32_t sn = e / n_checks, check = e - sn * n_checks;
-#if defined(ZKP_EXP_TRAFFIC4) && (ZKP_EXP_TRAFFIC4 & 2)
-    int4* const st = state + (size_t)(check & ~3u) * 4;
-    if (check & 3) live = false;
-#else
     int4* const st = state + (size_t)check * 4;
-#endif
     const uint32_t base = elem_snap + 12 * sn;
     auto rec = [&](uint32_t el) -> int4* { return st + (size_t)el * nc * 4; };
     F2 f{c};
@@ -2156,9 +1494,6 @@ __global__ void __launch_bounds__(64, 2) k_kdec_a(int4* state, uint32_t n_checks
         if (c == 0) rec_store(rec(elem_n + sn), n);
     }
 }
-#ifndef ZKP_KDEC_MERGED
-#define ZKP_KDEC_MERGED 1
-#endif
 __global__ void __launch_bounds__(64, 3) k_kdec_b(int4* state, uint32_t n_checks_in, uint32_t nc, uint32_t elem_snap, uint32_t count, uint32_t elem_ninv,
                                                   NDev nd) {
     const uint32_t n_checks = eff_n(n_checks_in, nd);
@@ -2169,12 +1504,7 @@ __global__ void __launch_bounds__(64, 3) k_kdec_b(int4* state, uint32_t n_checks
     bool live = e < n_checks * count;
     if (!live) e = n_checks * count - 1;
     const uint32_t sn = e / n_checks, check = e - sn * n_checks;
-#if defined(ZKP_EXP_TRAFFIC4) && (ZKP_EXP_TRAFFIC4 & 2)
-    int4* const st = state + (size_t)(check & ~3u) * 4;
-    if (check & 3) live = false;
-#else
     int4* const st = state + (size_t)check * 4;
-#endif
     const uint32_t base = elem_snap + 12 * sn;
     auto rec = [&](uint32_t el) -> int4* { return st + (size_t)el * nc * 4; };
     F2 f{c};
@@ -2198,7 +1528,6 @@ __global__ void __launch_bounds__(64, 3) k_kdec_b(int4* state, uint32_t n_checks
     }
     Fp28 dinv = f_mul_v(c ? c_neg(D) : D, ninv);               // conj(D) / |D|^2
     Fp28 z1 = f.mul(N, dinv);
-#if ZKP_KDEC_MERGED
     // t = 2 z1^2 + z2 z5 - 3 z3 z4 under ONE reduction (five products; column budget 2 * 2 * 2 + 2 + 3 * 2 = 16 <= 30; a reduced
     // value, no renormalisation): coefficient c of a b is x1 b + x2 b' with (x1, x2) = (a, -a') or (a', a), ' = the partner's
     Fp28 t;
@@ -2244,17 +1573,6 @@ __global__ void __launch_bounds__(64, 3) k_kdec_b(int4* state, uint32_t n_checks
     }
     Fp28 o;
     swap_pair(o, t);
-#else
-    Fp28 z4, z5;
-    rec_load(z5, rec(base + 10 + c));
-    Fp28 t = c_add(c_dbl(f.sqr(z1)), f.mul(z2, z5));
-    rec_load(z3, rec(base + 4 + c));
-    rec_load(z4, rec(base + 2 + c));
-    Fp28 m34 = f.mul(z3, z4);
-    t = f_vred(c_sub(t, c_add(c_dbl(m34), m34)));
-    Fp28 o;
-    swap_pair(o, t);
-#endif
     Fp28 z0 = c ? c_add(o, t) : c_add(c_sub(t, o), f_const(K28_ONE));   // xi t + 1
     z0 = f_vred(z0);
     if (live) {
@@ -2667,15 +1985,6 @@ __global__ void __launch_bounds__(64, 2) k_msm_final(const int4* wsums, uint32_t
 // the primer of prime(): a grid of one-wavefront workgroups that leave at once
 __global__ void __launch_bounds__(64) k_primer() {}
 
-// measurement only (ZKP_TIME_FILL=256): pseudo-random balanced 28-bit limbs as the timing hook's synthetic state - what real operands look like
-__global__ void k_fill_rand(int32_t* p, size_t n_words) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_words) return;
-    uint64_t x = (i + 1) * 0x9E3779B97F4A7C15ull;
-    x ^= x >> 29; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 32;
-    p[i] = (int32_t)((uint32_t)x >> 4) - (1 << 27);
-}
-
 }  // namespace
 
 // =============================================================================== host side
@@ -2701,7 +2010,6 @@ struct CoopDev {
     plan::Knobs kn;          // chunking / splitting knobs, clamped (zkp_plan.hpp: the arithmetic the CPU test walks under sanitizers)
     bool inv_fermat;         // a^(p-2) instead of the division-step inversion (cross-check)
     int cus;                 // compute units of the device
-    int prime_mask;          // ZKP_COOP_PRIME_MASK (experiments): which kernel classes are primed
     bool prime_now;          // set per super-chunk by two_phase: batches of at most one chunk only (a larger one keeps the GPU full: nothing to place)
     int prime;               // ZKP_COOP_PRIME: small grids in the dispatcher's bad bands are preceded by an empty grid of the same size (prime())
     int4* big_state;         // per-check state of a whole super-chunk (7.9 KB per check)
@@ -2716,7 +2024,7 @@ struct CoopDev {
     const uint32_t* n_dev;         // for the duration of one coop_pairing call: the device-resident check count (or null)
 };
 
-enum { PRIME_COOP = 1, PRIME_PREP = 2, PRIME_KSQ = 4, PRIME_INV = 8, PRIME_KDEC = 16 };      // kernel classes of prime()
+enum { PRIME_PREP, PRIME_KSQ, PRIME_INV };      // kernel classes of prime()
 // kernel classes of coop_profile_pairing (include/zkp_pairings.h ZKP_PROFILE_*)
 enum { PROF_PREP = 0, PROF_MILLER, PROF_FEXP_A, PROF_INV, PROF_KSQ, PROF_KDEC_A, PROF_KDEC_B, PROF_C_DEEP, PROF_C_PLAIN, PROF_CLASSES };
 struct ProfScope {
@@ -2742,7 +2050,7 @@ static void coop_resolve_table(const ZkpProgDesc& p, std::vector<uint4>& rt) {
     const int S = coop_cfg_slots(p.wide), SC = coop_cfg_consts(p.wide);
     const int SG = coop_group_stride(S);
     const size_t rows = p.n_tbl / LIG + 2;
-    constexpr int RL = 64 * WGW;   // lanes per row
+    constexpr int RL = 64;   // lanes per row
     rt.assign(rows * RL, make_uint4(0, 0, 0, 0));
     auto addr = [&](uint32_t slot, int grp) -> uint32_t { return 16u * (((slot & 64) ? 0 : SC + grp * SG) + (slot & 63)); };
     for (uint32_t pc = 0; pc * 4 + 3 < p.n_hdr; pc++) {
@@ -2750,13 +2058,7 @@ static void coop_resolve_table(const ZkpProgDesc& p, std::vector<uint4>& rt) {
         if ((h0 & 0xff) != OP_MULACC) continue;
         const uint32_t T = (h0 >> 8) & 0xff;
         for (int lane = 0; lane < RL; lane++) {
-            int g0 = lane / LIG, lig = lane - g0 * LIG, grp = g0 < GROUPS ? g0 : GROUPS - 1;
-            if (WGW > 1) {
-                const int wv = lane >> 6, wl = lane & 63;
-                g0 = wl / LIG;
-                grp = g0 < 5 ? wv * 5 + g0 : 15;
-                lig = g0 < 5 ? wl - g0 * LIG : wv * 4 + (wl - 60);
-            }
+            const int g0 = lane / LIG, lig = lane - g0 * LIG, grp = g0 < GROUPS ? g0 : GROUPS - 1;
             uint32_t f1 = 0, f2 = 0;
             for (uint32_t t = 0; t < T; t++) {
                 const uint32_t w = p.tbl[off + t * LIG + lig];
@@ -2768,7 +2070,7 @@ static void coop_resolve_table(const ZkpProgDesc& p, std::vector<uint4>& rt) {
             // z, w: LDS byte address of the step's result slot / companion slot for this lane, -1 where it stores nothing
             // (a padding lane of the step, lanes 60..63 of a wavefront)
             const uint32_t ew = p.tbl[off + T * LIG + lig];
-            const bool owner = WGW > 1 || g0 < GROUPS;
+            const bool owner = g0 < GROUPS;
             const uint32_t dst = (owner && ((ew >> 7) & 1)) ? addr(ew & 63, grp) : 0xffffffffu;
             const uint32_t sd = (owner && ((ew >> 29) & 1)) ? addr((ew >> 23) & 63, grp) : 0xffffffffu;
             rt[(off / LIG + T) * RL + lane] = make_uint4(f1, f2, dst, sd);
@@ -2812,7 +2114,6 @@ hipError_t coop_init(CoopState* st, const hipDeviceProp_t& prop) {
     kn.n_pipes = (int)env_l("ZKP_COOP_STREAMS", kn.n_pipes);
     kn.chunk = (size_t)env_l("ZKP_COOP_CHUNK", (long)kn.chunk);
     kn.super = (size_t)env_l("ZKP_COOP_SUPER", (long)kn.super);
-    kn.c_single = env_l("ZKP_COOP_C_SINGLE", 1) != 0;
     kn.inv_batch = (uint32_t)env_l("ZKP_COOP_INV_BATCH", (long)kn.inv_batch);
     kn.inv_lanes = (size_t)env_l("ZKP_COOP_INV_LANES", (long)kn.inv_lanes);
     // ZKP_COOP_NO_STREAM=1: groups of eight pairs joined by f12mul, the flow of rounds 1-4 (A/B baseline, cross-check);
@@ -2823,13 +2124,10 @@ hipError_t coop_init(CoopState* st, const hipDeviceProp_t& prop) {
     kn.c_split = (int)env_l("ZKP_COOP_C_SPLIT", 0);
     kn.c_split_min = (size_t)env_l("ZKP_COOP_C_SPLIT_MIN", (long)kn.c_split_min);
     kn.split_min = (size_t)env_l("ZKP_COOP_SPLIT_MIN", (long)kn.split_min);
-    kn = plan::clamp(kn);
-    kn.c_single_min = (size_t)env_l("ZKP_COOP_C_SINGLE_MIN", (long)kn.chunk);
-    d->kn = kn;
+    d->kn = plan::clamp(kn);
     d->inv_fermat = env_l("ZKP_COOP_INV_FERMAT", 0) != 0;
     d->cus = prop.multiProcessorCount;
     d->prime = (int)env_l("ZKP_COOP_PRIME", 1);
-    d->prime_mask = (int)env_l("ZKP_COOP_PRIME_MASK", PRIME_PREP | PRIME_KSQ | PRIME_INV);
     for (int i = 0; i < MAX_PIPES; i++) d->pipe[i].owner = d;
     for (int i = 0; i < d->kn.n_pipes; i++) {
         if ((e = hipStreamCreateWithFlags(&d->pipe[i].stream, hipStreamNonBlocking)) != hipSuccess) return e;
@@ -2884,9 +2182,9 @@ static hipError_t ensure_buf(int4** p, size_t* cap, size_t bytes) {
 // 24,576 pairs: 7.5 -> 6.8 / 8.3 -> 7.5 ms); the interpreter's and the decompression's launches gain nothing and are not primed.  Only
 // batches of at most one chunk are primed (a larger one keeps the GPU full).  LDS padding to cap the workgroups per
 // compute unit does nothing here (the imbalance is between the SIMDs of a compute unit).  ZKP_COOP_PRIME: 0 off, 1 the bands (default),
-// 2 every grid of 1 .. 12 workgroups per compute unit; ZKP_COOP_PRIME_MASK: the kernel classes (A/B).
+// 2 every grid of 1 .. 12 workgroups per compute unit of the primed classes.
 static hipError_t prime(const CoopDev* d, hipStream_t s, size_t blocks, int cls) {
-    if (!d || !d->prime || d->cus <= 0 || !blocks || !(d->prime_mask & cls) || !d->prime_now) return hipSuccess;
+    if (!d || !d->prime || d->cus <= 0 || !blocks || !d->prime_now) return hipSuccess;
     const size_t c = (size_t)d->cus;
     const bool band = cls == PRIME_KSQ ? (blocks > 3 * c && blocks <= 4 * c) || (blocks > 6 * c && blocks <= 8 * c)      // three wavefronts per SIMD
                                        : (blocks > 2 * c && blocks <= 3 * c);
@@ -2921,23 +2219,19 @@ static hipError_t run_prog(CoopDev* d, CoopPipe* pp, int prog, uint32_t n_checks
     a.chk_off = chk_off;
     a.nd = pp->nd;
 
-    static_assert(12 / WGW * coop_lds_bytes(ZKP_COOP_NSLOT, ZKP_COOP_NCONST) <= 160 * 1024 &&
-                      12 / WGW * coop_lds_bytes(ZKP_COOP_WIDE_NSLOT, ZKP_COOP_WIDE_NCONST) <= 160 * 1024 &&
-                      12 / WGW * coop_lds_bytes(ZKP_COOP_DEEP_NSLOT, ZKP_COOP_DEEP_NCONST) <= 160 * 1024,
+    static_assert(12 * coop_lds_bytes(ZKP_COOP_NSLOT, ZKP_COOP_NCONST) <= 160 * 1024 &&
+                      12 * coop_lds_bytes(ZKP_COOP_WIDE_NSLOT, ZKP_COOP_WIDE_NCONST) <= 160 * 1024 &&
+                      12 * coop_lds_bytes(ZKP_COOP_DEEP_NSLOT, ZKP_COOP_DEEP_NCONST) <= 160 * 1024,
                   "twelve wavefronts (three per SIMD, the register bound) must fit the 160 KB of LDS of a CU");
-    size_t lds_bytes = coop_lds_bytes(coop_cfg_slots(cfg), coop_cfg_consts(cfg));
-    // occupancy experiments only (the VALUE is cached, not the pointer getenv returned: a later setenv may move the environment)
-    static const long lds_pad = getenv("ZKP_COOP_LDS_PAD") ? atol(getenv("ZKP_COOP_LDS_PAD")) : 0;
-    if (lds_pad > 0) lds_bytes += (size_t)lds_pad;
+    const size_t lds_bytes = coop_lds_bytes(coop_cfg_slots(cfg), coop_cfg_consts(cfg));
     unsigned blocks = (n_checks + GROUPS - 1) / GROUPS;
-    { hipError_t ep = prime(d, s, blocks, PRIME_COOP); if (ep != hipSuccess) return ep; }
     ProfScope prof(d, s, cfg == 1 ? PROF_MILLER : cfg == 2 ? PROF_C_DEEP : d->prof_phase_c ? PROF_C_PLAIN : PROF_FEXP_A);
     if (cfg == 2)
-        hipLaunchKernelGGL((k_coop<ZKP_COOP_DEEP_NSLOT, ZKP_COOP_DEEP_NCONST>), dim3(blocks), dim3(64 * WGW), lds_bytes, s, a);
+        hipLaunchKernelGGL((k_coop<ZKP_COOP_DEEP_NSLOT, ZKP_COOP_DEEP_NCONST>), dim3(blocks), dim3(64), lds_bytes, s, a);
     else if (cfg == 1)
-        hipLaunchKernelGGL((k_coop<ZKP_COOP_WIDE_NSLOT, ZKP_COOP_WIDE_NCONST>), dim3(blocks), dim3(64 * WGW), lds_bytes, s, a);
+        hipLaunchKernelGGL((k_coop<ZKP_COOP_WIDE_NSLOT, ZKP_COOP_WIDE_NCONST>), dim3(blocks), dim3(64), lds_bytes, s, a);
     else
-        hipLaunchKernelGGL((k_coop<ZKP_COOP_NSLOT, ZKP_COOP_NCONST>), dim3(blocks), dim3(64 * WGW), lds_bytes, s, a);
+        hipLaunchKernelGGL((k_coop<ZKP_COOP_NSLOT, ZKP_COOP_NCONST>), dim3(blocks), dim3(64), lds_bytes, s, a);
     return hipGetLastError();
 }
 
@@ -2974,8 +2268,7 @@ static hipError_t prep(CoopPipe* pp, const uint64_t* g1, const uint64_t* g2, con
     const size_t prep_lds = 4 * 4 * 64 * sizeof(int4);
     { hipError_t ep = prime(pp->owner, s, (2 * (size_t)n_pairs + 63) / 64, PRIME_PREP); if (ep != hipSuccess) return ep; }
     ProfScope prof(pp->owner, s, PROF_PREP);
-    static const bool no_cln = getenv("ZKP_PREP_NO_CLN") && atoi(getenv("ZKP_PREP_NO_CLN"));   // A/B knob (value cached, not the pointer)
-    if (fused && !no_cln)
+    if (fused)
         hipLaunchKernelGGL(k_prep_lines<true>, dim3((2 * n_pairs + 63) / 64), dim3(64), prep_lds, s, g1 + 12 * p0, g2 + 24 * p0, i1 ? i1 + p0 : nullptr,
                            i2 ? i2 + p0 : nullptr, n_pairs, g, k_in, j0, n, pp->lines, pp->nd);
     else
@@ -3100,7 +2393,6 @@ static hipError_t run_fexp_c(CoopDev* d, CoopPipe* pp, uint32_t n, uint32_t nc, 
                 e = run_ksq(pp->stream, pp->state, n, nc, ps.a, ps.b, ps.c, ps.mask, d, pp->nd);
                 break;
             case ZKP_PLAN_KDEC_A: {
-                { hipError_t ep = prime(d, pp->stream, (2 * (size_t)n * ps.b + 63) / 64, PRIME_KDEC); if (ep != hipSuccess) return ep; }
             ProfScope prof(d, pp->stream, PROF_KDEC_A);
                 hipLaunchKernelGGL(k_kdec_a, dim3((unsigned)((2 * (size_t)n * ps.b + 63) / 64)), dim3(64), 0, pp->stream, pp->state, n, nc, ps.a, ps.b, ps.c, pp->nd);
                 e = hipGetLastError();
@@ -3110,7 +2402,6 @@ static hipError_t run_fexp_c(CoopDev* d, CoopPipe* pp, uint32_t n, uint32_t nc, 
                 e = run_inv(d, pp->stream, pp->state, n, nc, ps.a, ps.b, ps.c, pp->nd);
                 break;
             case ZKP_PLAN_KDEC_B: {
-                { hipError_t ep = prime(d, pp->stream, (2 * (size_t)n * ps.b + 63) / 64, PRIME_KDEC); if (ep != hipSuccess) return ep; }
             ProfScope prof(d, pp->stream, PROF_KDEC_B);
                 hipLaunchKernelGGL(k_kdec_b, dim3((unsigned)((2 * (size_t)n * ps.b + 63) / 64)), dim3(64), 0, pp->stream, pp->state, n, nc, ps.a, ps.b, ps.c, pp->nd);
                 e = hipGetLastError();
@@ -3164,19 +2455,12 @@ static hipError_t two_phase(CoopDev* d, size_t n_total, size_t k, bool need_line
                 v.nd = NDev{d->n_dev, (uint32_t)(sb + base)};
                 return run_fexp_c(d, &v, n, (uint32_t)ns, out ? out + 72 * (sb + base) : nullptr, ok ? ok + sb + base : nullptr, all_ok);
             }, part);
-        } else if (pcc.mode == plan::C_SINGLE) {
+        } else {
             CoopPipe v = d->pipe[0];
             v.state = d->big_state;
             v.stream = s;
             v.nd = NDev{d->n_dev, (uint32_t)sb};
             e = run_fexp_c(d, &v, (uint32_t)ns, (uint32_t)ns, out ? out + 72 * sb : nullptr, ok ? ok + sb : nullptr, all_ok);
-        } else {
-            e = for_chunks(d, ns, 1, false, false, s, [&](CoopPipe* pp, size_t base, uint32_t n) -> hipError_t {
-                CoopPipe v = *pp;
-                v.state = d->big_state + 4 * base;
-                v.nd = NDev{d->n_dev, (uint32_t)(sb + base)};
-                return run_fexp_c(d, &v, n, (uint32_t)ns, out ? out + 72 * (sb + base) : nullptr, ok ? ok + sb + base : nullptr, all_ok);
-            });
         }
         if (e != hipSuccess) return e;
     }
@@ -3335,11 +2619,6 @@ hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hip
             if (!timed) {
                 timed = true;
                 if (which == 17) return hipStreamSynchronize(s);
-                static const bool empty_primer = getenv("ZKP_PRIMER_EMPTY") && atoi(getenv("ZKP_PRIMER_EMPTY")) != 0;
-                if (which == 18 && empty_primer) {
-                    hipLaunchKernelGGL(k_primer, dim3((unsigned)((n + KS_CHECKS - 1) / KS_CHECKS)), dim3(64), 0, s);
-                    return hipGetLastError();
-                }
                 if (which == 18) return run_ksq(s, v.state, (uint32_t)n, (uint32_t)n, 0, 12, 1, 0);
                 hipError_t e1 = run_prog(d, &v, ZKP_PROG_TIME_T1, (uint32_t)n, (uint32_t)n, 1, nullptr, nullptr, nullptr, nullptr);
                 if (e1 != hipSuccess || which == 16) return e1;
@@ -3355,15 +2634,7 @@ hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hip
         if (which == 11) return run_prog(d, &v, ZKP_PROG_MILLER1_STATE, (uint32_t)n, (uint32_t)n, 1, nullptr, nullptr, nullptr, nullptr);
         return run_prog(d, &v, ids[which], (uint32_t)n, (uint32_t)n, 1, nullptr, nullptr, nullptr, nullptr);
     };
-    // ZKP_TIME_FILL=<byte> (measurement only): the synthetic inputs are this byte repeated instead of zeros - the clock a kernel gets depends
-    // on the operand data (DESIGN_HISTORY section 4, round 5), so zeros flatter a multiply-add-dense kernel
-    static const int fill = getenv("ZKP_TIME_FILL") ? atoi(getenv("ZKP_TIME_FILL")) : 0;
-    if (which != 11 && fill < 256 && (e = hipMemsetAsync(v.state, fill & 0xff, (size_t)ST_SIZE * n * 64, s)) != hipSuccess) return e;
-    if (which != 11 && fill >= 256) {
-        const size_t words = (size_t)ST_SIZE * n * 16;
-        hipLaunchKernelGGL(k_fill_rand, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, (int32_t*)v.state, words);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if (which != 11 && (e = hipMemsetAsync(v.state, 0, (size_t)ST_SIZE * n * 64, s)) != hipSuccess) return e;
     if ((e = once()) != hipSuccess) return e;
     if ((e = hipEventRecord(e0, s)) != hipSuccess) return e;
     if ((e = once()) != hipSuccess) return e;
@@ -3373,13 +2644,12 @@ hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hip
 }
 
 // ZKP_VALID_GENERIC=1 (environment, read once): the compiled kernels alone, the round-3 path - the A/B baseline and the cross-check
-[[maybe_unused]] static bool valid_generic_only() {
+static bool valid_generic_only() {
     static const bool v = getenv("ZKP_VALID_GENERIC") && atoi(getenv("ZKP_VALID_GENERIC")) != 0;
     return v;
 }
 hipError_t coop_g1_valid(const uint64_t* g1, const uint8_t* inf, size_t n, uint8_t* status, hipStream_t s) {
     if (!n) return hipSuccess;
-#if ZKP_VALID_ASM
     if (!valid_generic_only()) {
         hipLaunchKernelGGL(k_g1_valid_fast, dim3((unsigned)((n + 63) / 64)), dim3(64), 3 * 4 * 64 * sizeof(int4), s, g1, inf, (uint32_t)n, status);
         hipError_t e = hipGetLastError();
@@ -3387,13 +2657,11 @@ hipError_t coop_g1_valid(const uint64_t* g1, const uint8_t* inf, size_t n, uint8
         hipLaunchKernelGGL(k_g1_valid28, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g1, inf, (uint32_t)n, status, 1);
         return hipGetLastError();
     }
-#endif
     hipLaunchKernelGGL(k_g1_valid28, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g1, inf, (uint32_t)n, status, 0);
     return hipGetLastError();
 }
 hipError_t coop_g2_valid(CoopState* st, const uint64_t* g2, const uint8_t* inf, size_t n, uint8_t* status, hipStream_t s) {
     if (!n) return hipSuccess;
-#if ZKP_VALID_ASM
     if (!valid_generic_only()) {
         // ZKP_G2_VALID_WAVES=2 (environment, read once): the two-wave kernel (no scratch buffer), the A/B baseline of the three-wave one
         static const bool two_waves = getenv("ZKP_G2_VALID_WAVES") && atoi(getenv("ZKP_G2_VALID_WAVES")) == 2;
@@ -3420,8 +2688,6 @@ hipError_t coop_g2_valid(CoopState* st, const uint64_t* g2, const uint8_t* inf, 
         hipLaunchKernelGGL(k_g2_valid28, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, s, g2, inf, (uint32_t)n, status, 1);
         return hipGetLastError();
     }
-#endif
-    (void)st;
     hipLaunchKernelGGL(k_g2_valid28, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, s, g2, inf, (uint32_t)n, status, 0);
     return hipGetLastError();
 }

@@ -31,8 +31,6 @@ struct Knobs {
     int n_pipes = 2;                          // ZKP_COOP_STREAMS
     size_t chunk = (size_t)1 << 16;           // ZKP_COOP_CHUNK: checks per pipeline pass (bounds the line buffer: 26 KB per pair)
     size_t super = (size_t)1 << 20;           // ZKP_COOP_SUPER: checks per two-phase final exponentiation
-    bool c_single = true;                     // ZKP_COOP_C_SINGLE
-    size_t c_single_min = (size_t)1 << 16;    // ZKP_COOP_C_SINGLE_MIN (default: chunk)
     uint32_t inv_batch = 32;                  // ZKP_COOP_INV_BATCH
     size_t inv_lanes = (size_t)1 << 15;       // ZKP_COOP_INV_LANES
     size_t max_stream = MAX_STREAM;           // ZKP_COOP_MAX_STREAM / ZKP_COOP_NO_STREAM
@@ -112,13 +110,12 @@ inline Chunks plan_chunks(const Knobs& kn, size_t n_total, size_t k, bool need_l
 }
 
 // ---- phase C of a super-chunk of ns checks (two_phase)
-enum PhaseCMode { C_PARTS = 0, C_SINGLE = 1, C_CHUNKS = 2 };
+enum PhaseCMode { C_PARTS = 0, C_SINGLE = 1 };
 struct PhaseC { PhaseCMode mode; size_t part; };     // C_PARTS: parts of `part` checks alternate over the pipelines
 inline PhaseC plan_phase_c(const Knobs& kn, size_t ns, bool profiling) {
     const int parts = profiling ? 0 : (kn.c_split > 0 ? kn.c_split : (ns >= kn.c_split_min && kn.n_pipes >= 2 ? 2 : 0));
     if (parts > 1 && ns >= (size_t)16 * parts) return {C_PARTS, ((ns + parts - 1) / parts + 15) / 16 * 16};
-    if (kn.c_single || ns <= kn.c_single_min) return {C_SINGLE, ns};     // one launch sequence on the caller's stream
-    return {C_CHUNKS, 0};                                                // ZKP_COOP_C_SINGLE=0: per chunk on the pipelines (rounds 1-2)
+    return {C_SINGLE, ns};     // one launch sequence on the caller's stream
 }
 
 // ---- batched inversion of `count` planes of n values: few lanes with long batches (the kernel is bound by one lane's chain)
