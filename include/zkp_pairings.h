@@ -43,6 +43,9 @@
  * aborts and never unwinds across this boundary (the reference's panics F7 become status bytes).
  * Inputs must be canonical (< p): non-canonical limbs give ZKP_ERR_NONCANONICAL when validation is on
  * (zkp_set_validate), unspecified field values otherwise.
+ * Points: ONLY the infinity flag marks the identity - coordinates (0, 0) with the flag clear are a point like any other (EIP-197-style
+ * callers must set the flag).  The pairing entry points do not validate points (zkp_points_check_batch and the RLC path do): on any
+ * canonical input, on or off the curve, in or out of the prime-order subgroups, they compute exactly what is written below.
  * Threading: a zkp_ctx is bound to one GPU and is not thread-safe; use one ctx per thread / rank.  The *_dev calls
  * of one ctx may be issued on different streams: each call first makes its stream wait (an event, no host wait) for the
  * previous call's use of the context's workspace, so they never overlap on it.
@@ -135,12 +138,17 @@ int zkp_device_info(const zkp_ctx* ctx, int* cus, int* clock_khz, char* name, si
 const uint64_t* zkp_gt_identity(void);
 
 /* ---- host-pointer entry points (H2D copy, kernels, D2H copy, synchronous) ---------------------- */
-/* out_gt[i] = pairing(g1[i], g2[i]); inf1/inf2 may be NULL (= no infinities). */
+/* out_gt[i] = pairing(g1[i], g2[i]); inf1/inf2 may be NULL (= no infinities).  Every pairing-shaped entry point (pairing, check, product
+ * check, their _dev and _multi flavours, both kernel families) returns exactly final_exponentiation(multi_miller_loop(..)) of the
+ * upstream-shaped Miller loop (ePrint 2010/354 Alg. 26 / 27) for ANY canonical input; a pair with an infinity flag contributes one. */
 int zkp_pairing_batch(zkp_ctx* ctx, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2,
                       size_t n, uint64_t* out_gt);
 /* n_checks groups of k consecutive pairs; out_ml[c] = multi_miller_loop(group c) (72 u64 each). */
 int zkp_multi_miller_loop_batch(zkp_ctx* ctx, const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1,
                                 const uint8_t* inf2, size_t n_checks, size_t k, uint64_t* out_ml);
+/* f^(3 (p^12 - 1) / r); f = 0 (a Miller loop on points off the curves can give it, e.g. an unflagged (0, 0) G2 point) gives the ZERO
+ * record, never Gt::identity(), so a check or product check whose Miller value is zero fails (ok = 0, all_ok = 0, is_one = 0) where the
+ * reference panics in Fp12::invert().unwrap() (F7). */
 int zkp_final_exponentiation_batch(zkp_ctx* ctx, const uint64_t* f, size_t n, uint64_t* out_gt);
 /* ok[c] = (final_exponentiation(multi_miller_loop(group c)) == Gt::identity()); ok may be NULL.
  * *all_ok = AND over this call's checks (the cross-GPU AND is the caller's single RCCL all-reduce). */

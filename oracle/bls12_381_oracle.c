@@ -839,7 +839,9 @@ static fp12 final_exponentiation(const fp12* fin) {
     fp12 f = *fin;
     fp12 t0 = f, t1, t2, t3, t4, t5, t6;
     for (int i = 0; i < 6; i++) t0 = fp12_frob(&t0);
-    if (!fp12_inv(&f, &t1)) return fp12_one(); /* f == 0 cannot come out of a Miller loop */
+    /* f == 0 comes out of a Miller loop on points outside the curves (an unflagged (0, 0) G2 point, for one): its
+     * final exponentiation is the zero record, so a check on it fails (the reference panics in Fp12::invert().unwrap()) */
+    if (!fp12_inv(&f, &t1)) { memset(&t1, 0, sizeof t1); return t1; }
     t2 = fp12_mul(&t0, &t1);
     t1 = t2;
     t2 = fp12_frob(&t2);

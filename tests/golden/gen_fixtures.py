@@ -185,6 +185,112 @@ def main():
     with open(os.path.join(HERE, "model_vectors.json"), "w") as f:
         json.dump(out, f, indent=0)
     print("wrote model_vectors.json", os.path.getsize(os.path.join(HERE, "model_vectors.json")), "bytes")
+    with open(os.path.join(HERE, "outside_groups.json"), "w") as f:
+        json.dump(outside_groups(), f, indent=0)
+    print("wrote outside_groups.json", os.path.getsize(os.path.join(HERE, "outside_groups.json")), "bytes")
+
+
+# ---- points outside G1 / G2 and off the curves (outside_groups.json)
+X_SIGNED = -m.BLS_X
+H1 = (X_SIGNED - 1) ** 2 // 3                 # G1 cofactor = 3 11^2 10177^2 859267^2 52437899^2
+H2 = (X_SIGNED ** 8 - 4 * X_SIGNED ** 7 + 5 * X_SIGNED ** 6 - 4 * X_SIGNED ** 4 + 6 * X_SIGNED ** 3 - 4 * X_SIGNED ** 2
+      - 4 * X_SIGNED + 13) // 9             # G2 cofactor = 13^2 23^2 2713 11953 262069 ...
+B2 = (4, 4)                                   # b' = 4 xi of the twist
+
+
+def _small_order(mul, rnd_point, n_group, ell):
+    """a point of order exactly ell: [N / ell^v] R (v the full multiplicity of ell in N), then [ell] while that is not infinity"""
+    v, t = 0, n_group
+    while t % ell == 0:
+        t //= ell
+        v += 1
+    assert v >= 1
+    while True:
+        q = mul(rnd_point(), n_group // ell ** v)
+        if q is None:
+            continue
+        while mul(q, ell) is not None:
+            q = mul(q, ell)
+        return q
+
+
+def outside_groups():
+    """Inputs the pairing entry points accept without validation (they ask only for canonical limbs): on-curve points of small
+    order and random points outside the prime-order subgroups, and points off the curves.  Every pairing-shaped entry point must
+    return exactly final_exponentiation(multi_miller_loop(..)) of the Alg. 26 / 27 model on them; the final exponentiation of zero
+    is zero."""
+    assert H1 == 0x396C8C005555E1568C00AAAB0000AAAB and H1 % 11 ** 2 == 0 and H1 % 10177 ** 2 == 0
+    assert all(H2 % d == 0 for d in (13 ** 2, 23 ** 2, 2713, 11953))
+    g = m.SplitMix64(0x0FFC0DE)
+
+    def g1_rnd():
+        while True:
+            x = g.below(P)
+            y = m.fp_sqrt((x * x * x + 4) % P)
+            if y is not None:
+                return (x, y)
+
+    def g2_rnd():
+        while True:
+            x = rnd_f2(g)
+            y = f2_sqrt(m.f2_add(m.f2_mul(m.f2_sqr(x), x), B2))
+            if y is not None:
+                return (x, y)
+
+    g1, g2 = {}, {}
+    g1["order3"] = (0, 2)
+    g1["order3_neg"] = (0, P - 2)
+    for ell in (11, 10177):
+        g1["order%d" % ell] = _small_order(m.g1_mul, g1_rnd, H1 * m.R_ORDER, ell)
+    g1["cofactor"] = g1_rnd()
+    g1["off_zero"] = (0, 0)
+    x = g.below(P)
+    g1["off_x0"] = (x, 0)
+    g1["off_random"] = (g.below(P), g.below(P))
+    for ell in (13, 23, 2713, 11953):
+        g2["order%d" % ell] = _small_order(m.g2_mul, g2_rnd, H2 * m.R_ORDER, ell)
+    g2["cofactor"] = g2_rnd()
+    g2["off_zero"] = (m.F2_ZERO, m.F2_ZERO)
+    g2["off_x0"] = (rnd_f2(g), m.F2_ZERO)
+    g2["off_0y"] = (m.F2_ZERO, rnd_f2(g))
+    g2["off_gen_y1"] = (m.G2_GEN[0], m.f2_add(m.G2_GEN[1], m.F2_ONE))
+    while True:   # y^2 = 3 x^3 / 2: the first Alg. 26 line has c2 = 6 x^3 - 4 y^2 = 0
+        x = rnd_f2(g)
+        y = f2_sqrt(m.f2_muls(m.f2_mul(m.f2_sqr(x), x), 3 * m.fp_inv(2) % P))
+        if y is not None:
+            g2["off_c2_zero"] = (x, y)
+            break
+    orders1 = {"order3": 3, "order3_neg": 3, "order11": 11, "order10177": 10177}
+    orders2 = {"order13": 13, "order23": 23, "order2713": 2713, "order11953": 11953}
+    for name, pt in g1.items():
+        on = m.g1_on_curve(pt)
+        assert on == (not name.startswith("off_"))
+        if name in orders1:
+            assert m.g1_mul(pt, orders1[name]) is None and pt is not None
+        if on:
+            assert not m.g1_torsion_free(pt)
+    for name, pt in g2.items():
+        on = m.g2_on_curve(pt)
+        assert on == (not name.startswith("off_"))
+        if name in orders2:
+            assert m.g2_mul(pt, orders2[name]) is None and pt is not None
+        if on:
+            assert not m.g2_torsion_free(pt)
+    # the pair whose Alg. 26 Miller value is zero
+    x, y = g2["off_c2_zero"]
+    _, (_, _, c2) = m.doubling_step((x, y, m.F2_ONE))
+    assert c2 == m.F2_ZERO and m.multi_miller_loop([(g1["off_zero"], g2["off_c2_zero"])]) == [m.F2_ZERO] * 6
+    out = {"g1": {k: {"p": g1hex(v), "on_curve": m.g1_on_curve(v), "order": orders1.get(k)} for k, v in g1.items()},
+           "g2": {k: {"p": g2hex(v), "on_curve": m.g2_on_curve(v), "order": orders2.get(k)} for k, v in g2.items()}}
+    # a handful of pairs with the model's Miller value and Gt ("gen" = the generator of G1 / G2)
+    pts1, pts2 = dict(g1, gen=m.G1_GEN), dict(g2, gen=m.G2_GEN)
+    pairs = []
+    for a, b in (("gen", "order13"), ("gen", "order11953"), ("order11", "gen"), ("order3", "order23"), ("cofactor", "cofactor"),
+                 ("gen", "off_gen_y1"), ("off_random", "gen"), ("gen", "off_zero"), ("off_zero", "off_c2_zero")):
+        ml = m.multi_miller_loop([(pts1[a], pts2[b])])
+        pairs.append({"g1": a, "g2": b, "miller": flat12(ml), "gt": flat12(m.final_exponentiation(ml))})
+    out["pairs"] = pairs
+    return out
 
 
 if __name__ == "__main__":

@@ -39,6 +39,8 @@ def test_hot_kernels_keep_their_registers():
     assert ksq["vgpr"] <= 168 and ksq["spill"] == 0 and ksq["scratch"] == 0, ksq
     (prep,) = find("k_prep_linesILb1E")                                                                               # the fused paths' line steps
     assert prep["vgpr"] <= 256 and prep["spill"] == 0 and prep["scratch"] == 0, prep
+    (prepo,) = find("k_prep_lines_off_twist")                                                       # their Jacobian steps off the twist
+    assert prepo["vgpr"] <= 256 and prepo["spill"] == 0 and prepo["scratch"] == 0, prepo
     for name in ("k_kdec_a", "k_kdec_b"):
         (v,) = find(name)
         # round 5: k_kdec_b keeps z2 across its two by-value products (the denominator is no longer stored a second time): 170 registers

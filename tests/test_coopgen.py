@@ -310,3 +310,14 @@ def test_run_time_k_miller_program_matches_the_model():
     hdr, tbl = cg.encode(prog)
     ops = [hdr[i] & 0xff for i in range(0, len(hdr), 4)]
     assert ops.count(cg.OP_PLOOP) == ops.count(cg.OP_PENDLOOP) and all(hdr[i + 1] == 1 for i in range(0, len(hdr), 4) if (hdr[i] & 0xff) == cg.OP_PENDLOOP)
+
+
+def test_emulated_final_exponentiation_of_zero_is_the_zero_record():
+    """final_exponentiation(0) = 0 (a Miller value off the curves can be 0; the reference panics in Fp12::invert().unwrap()): fexp_a
+    from the wire, the batched inversion's 0 for 0, the phase C plan - zero record out, and the identity test says no"""
+    ea = cg.Emu(wire_in=[0] * 12).run(cg.prog_fexp_a(True).steps)
+    assert cg.from_mont(ea.state[cg.ST_N]) == 0
+    ea.state[cg.ST_NINV] = cg.mont(0)                  # k_batch_inv: a zero element gets 0
+    ec = cg.run_plan(cg.fexp_c_plan(), ea.state)
+    assert ec.wire_out == [0] * 12 and ec.is_identity is False
+    assert m.f12_flat_ints(m.final_exponentiation([m.F2_ZERO] * 6)) == [0] * 12

@@ -352,3 +352,108 @@ def test_group_law_reference_style():
     ng = g.copy()
     ng[12:] = o.fp2_neg(g[12:])
     assert o.g2_add(g, 0, ng, 0)[1] == 1
+
+
+# ------------------------------------------------------------------ points outside G1 / G2 and off the curves
+# The pairing entry points do not validate (include/zkp_pairings.h): on every canonical input the oracle must compute what the model's
+# Alg. 26 / 27 Miller loop and final exponentiation give, and the final exponentiation of zero is zero (the reference would panic in
+# Fp12::invert().unwrap(); a failing verdict is the status-code form of that).
+import outside_groups as og  # noqa: E402
+
+
+def _ml_gt(pairs):
+    """oracle Miller value and Gt of ONE check over `pairs` (model points; None = a flagged infinity over garbage coordinates)"""
+    g1 = np.concatenate([og.g1_wire(p if p is not None else (5, 7)) for p, _ in pairs])
+    g2 = np.concatenate([og.g2_wire(q if q is not None else ((1, 2), (3, 4))) for _, q in pairs])
+    i1 = np.array([p is None for p, _ in pairs], dtype=np.uint8)
+    i2 = np.array([q is None for _, q in pairs], dtype=np.uint8)
+    ml = o.multi_miller_loop_batch(g1, g2, 1, len(pairs), i1, i2)[0]
+    ok = o.pairing_check_batch(g1, g2, 1, len(pairs), i1, i2)[0]
+    return ml, o.final_exponentiation_batch(ml)[0], int(ok)
+
+
+def _model_flat(f):
+    return og.f12_wire(m.f12_flat_ints(f))
+
+
+def test_outside_groups_fixture_is_what_it_says():
+    g1, g2 = og.g1_points(), og.g2_points()
+    for name, v in og.data()["g1"].items():
+        assert o.g1_is_valid(og.g1_wire(g1[name])) == (2 if v["on_curve"] else 1), name
+    for name, v in og.data()["g2"].items():
+        assert o.g2_is_valid(og.g2_wire(g2[name])) == (2 if v["on_curve"] else 1), name
+        if v["order"]:
+            q, inf = o.g2_mul(og.g2_wire(g2[name]), v["order"])
+            assert inf == 1, name
+    assert {v["order"] for v in og.data()["g1"].values()} >= {3, 11, 10177}
+    assert {v["order"] for v in og.data()["g2"].values()} >= {13, 23, 2713, 11953}
+
+
+def test_oracle_matches_the_stored_model_values_outside_the_groups():
+    g1, g2 = og.g1_all(), og.g2_all()
+    for c in og.data()["pairs"]:
+        pair = [(g1[c["g1"]], g2[c["g2"]])]
+        ml, gt, _ = _ml_gt(pair)
+        assert ints(ml) == [H(x) for x in c["miller"]], (c["g1"], c["g2"])
+        assert ints(gt) == [H(x) for x in c["gt"]], (c["g1"], c["g2"])
+        p = o.pairing_batch(og.g1_wire(pair[0][0]), og.g2_wire(pair[0][1]))[0]
+        assert np.array_equal(p, gt), (c["g1"], c["g2"])
+
+
+@pytest.mark.parametrize("side", ["g1", "g2"])
+def test_oracle_pairing_equals_the_model_on_every_class(side):
+    """each G1 class against the G2 generator and each G2 class against the G1 generator: Miller value, final exponentiation and
+    pairing() of the oracle equal the model's"""
+    classes = og.g1_points() if side == "g1" else og.g2_points()
+    for name, pt in classes.items():
+        pair = (pt, m.G2_GEN) if side == "g1" else (m.G1_GEN, pt)
+        ml_m = m.multi_miller_loop([pair])
+        gt_m = m.final_exponentiation(ml_m)
+        ml, gt, ok = _ml_gt([pair])
+        assert np.array_equal(ml, _model_flat(ml_m)), name
+        assert np.array_equal(gt, _model_flat(gt_m)), name
+        assert np.array_equal(o.pairing_batch(og.g1_wire(pair[0]), og.g2_wire(pair[1]))[0], gt), name
+        assert ok == int(gt_m == m.f12_one()), name
+
+
+def test_oracle_multi_pair_check_over_every_class():
+    """one check over every class at once (k = 19) and with one flagged infinity over garbage: the shared-squaring Miller value equals
+    the model's"""
+    g1, g2 = list(og.g1_all().values()), list(og.g2_all().values())
+    pairs = [(g1[i % len(g1)], g2[i % len(g2)]) for i in range(max(len(g1), len(g2)) + 1)]
+    pairs[3] = (None, pairs[3][1])
+    ml, gt, _ = _ml_gt(pairs)
+    ml_m = m.multi_miller_loop([p for p in pairs if p[0] is not None])
+    assert np.array_equal(ml, _model_flat(ml_m))
+    assert np.array_equal(gt, _model_flat(m.final_exponentiation(ml_m)))
+
+
+def test_final_exponentiation_of_zero_is_zero():
+    z = np.zeros(72, dtype=np.uint64)
+    assert m.final_exponentiation([m.F2_ZERO] * 6) == [m.F2_ZERO] * 6
+    one = o.fp12_one()
+    out = o.final_exponentiation_batch(np.concatenate([one, z, one]))
+    assert not out[1].any()
+    assert np.array_equal(out[0], one) and np.array_equal(out[2], one)
+
+
+def test_a_zero_miller_value_fails_the_check():
+    """an unflagged (0, 0) G2 point makes the first Alg. 26 line vanish: the Miller value is 0 and so is its Gt, and a check that fails
+    alone must still fail with that pair added (the oracle used to return Gt::identity() for it, so ANY check passed).  The flag, not
+    the coordinates, marks the identity."""
+    g1, g2 = og.g1_all(), og.g2_all()
+    P, Q, Z2 = m.G1_GEN, m.G2_GEN, g2["off_zero"]
+    assert _ml_gt([(P, Q)])[2] == 0
+    ml, gt, ok = _ml_gt([(P, Q), (P, Z2)])
+    assert not ml.any() and not gt.any() and ok == 0
+    # a passing check stays passing with a FLAGGED infinity over (0, 0) and fails with the same coordinates unflagged
+    passing = [(P, Q), (m.g1_neg(P), Q)]
+    assert _ml_gt(passing)[2] == 1
+    assert _ml_gt(passing + [(P, None)])[2] == 1
+    assert _ml_gt(passing + [(P, Z2)])[2] == 0
+    # Groth16 shape: proof point B sent as an unflagged (0, 0)
+    ok = o.pairing_check_batch(np.concatenate([og.g1_wire(P), og.g1_wire(P)]), np.concatenate([og.g2_wire(Z2), og.g2_wire(Q)]), 1, 2)
+    assert ok[0] == 0
+    # the pair whose first Alg. 26 line has c2 = 0 meets an unflagged G1 (0, 0): zero, not the identity
+    ml, gt, ok = _ml_gt([(g1["off_zero"], g2["off_c2_zero"])])
+    assert not ml.any() and not gt.any() and ok == 0

@@ -394,3 +394,43 @@ def test_doubling_step_on_half_a_wavefront_leaves_the_other_half_alone():
         if r in two.v:
             assert vals[:2] == two.v[r][:2], r
     assert four.mem == two.mem and len(two.mem) > 0
+
+
+def _cln_miller_loop(p1, q):
+    """the Miller value of k_prep_lines<true>'s line stream: the CLN steps of doubling_model / addition_model (the formulas the asm
+    blocks are held to above) from (X : Y : W) = (x, y, 2), in the model's loop shape"""
+    import bls12_381_model as m
+    X, Y, W = q[0], q[1], (2, 0)
+    f = m.f12_one()
+    bits = bin(m.BLS_X >> 1)[2:]
+    for bit in bits[1:]:
+        X, Y, W, ln = doubling_model(X, Y, W, p1[0], p1[1])
+        f = m.f12_mul(f, m._sparse_014(*ln))
+        if bit == "1":
+            X, Y, W, ln = addition_model(X, Y, W, q[0], q[1], p1[0], p1[1])
+            f = m.f12_mul(f, m._sparse_014(*ln))
+        f = m.f12_sqr(f)
+    X, Y, W, ln = doubling_model(X, Y, W, p1[0], p1[1])
+    return m.f12_conj(m.f12_mul(f, m._sparse_014(*ln)))
+
+
+def test_cln_lines_give_the_alg26_pairing_exactly_on_the_twist():
+    """the routing rule of k_prep_lines<true>: after the final exponentiation the CLN Miller loop (b' = 4 xi built into its doubling)
+    equals the Alg. 26 / 27 one of the model on G2, on a twist point outside G2 and on twist points of order 13 (whose loop meets
+    T = +-Q and infinity), 23, 2713 and 11953 - and differs off the twist, where the kernel must run the Jacobian steps instead"""
+    import bls12_381_model as m
+    import outside_groups as og
+    g2 = og.g2_all()
+    for name, v in list(og.data()["g2"].items()) + [("gen", {"on_curve": True})]:
+        q = g2[name]
+        want = m.pairing(m.G1_GEN, q)
+        got = m.final_exponentiation(_cln_miller_loop(m.G1_GEN, q))
+        if v["on_curve"]:
+            assert got == want, name
+        elif name == "off_gen_y1":
+            assert got != want, name
+    # y^2 = 3 x^3 / 2 against an unflagged G1 (0, 0): the first Alg. 26 line vanishes (Miller value 0, Gt 0) where the CLN line
+    # c2 = 2 (y^2 - 12 xi) does not (its Gt is the identity) - the pair only a wavefront on the Jacobian steps gets right
+    p0, q = og.g1_points()["off_zero"], g2["off_c2_zero"]
+    assert m.pairing(p0, q) == [m.F2_ZERO] * 6
+    assert m.final_exponentiation(_cln_miller_loop(p0, q)) == m.f12_one()

@@ -621,12 +621,56 @@ struct G2C { Fp28 x, y, z; };   // this lane's coefficient of the three Jacobian
 // lane c writes the records of Fp2 coefficient c.  The k pairs are pairs j0 .. j0+k-1 of the check's k_in
 // input pairs (k_in > k when a check is processed in groups of at most eight pairs).
 constexpr int PREP_WAVES = 2;   // measured: 256 VGPRs (2 waves/SIMD) 6.6 ms, 168 -> 9.3 ms, 128 -> 11.4 ms per 2^17 pairs (spill traffic)
-// CLN: Costello-Lange-Naehrig steps in homogeneous projective coordinates with freely scaled lines (tools/prepasm.py), for the fused
-// pairing paths only - any factor of the Miller value that lies in Fp2 dies in the final exponentiation; otherwise the upstream-shaped
-// Jacobian steps of ePrint 2010/354 Alg. 26 / 27 (zkp_multi_miller_loop_batch exposes that Miller value).
-template <bool CLN>
-__global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2,
-                                                       uint32_t n_pairs_in, uint32_t k, uint32_t k_in, uint32_t j0, uint32_t nc_in, int4* lines, NDev nd) {
+// y^2 == x^3 + 4 xi for the lane pair's Fp2 point (x, y)?  Inline products (c_mul's arithmetic): a call ahead of the asm loop of
+// k_prep_lines costs the loop its registers (compiled that way: 192 B of scratch per lane).  Under full EXEC (DPP partner exchange).
+__device__ __forceinline__ Fp28 pair_mul_inline(const Fp28& a, const Fp28& b, int c) {
+    Fp28 ao, bo, r;
+    swap_pair(ao, a);
+    swap_pair(bo, b);
+    int32_t x1[NL], x2[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        x1[i] = c ? ao.l[i] : a.l[i];
+        x2[i] = c ? a.l[i] : -ao.l[i];
+    }
+    Acc acc;
+    acc_zero(acc);
+    acc_mul(acc, x1, b.l);
+    acc_mul(acc, x2, bo.l);
+    acc_reduce(r.l, acc);
+    return r;
+}
+__device__ __forceinline__ bool on_twist_pair(const Fp28& x, const Fp28& y, int c) {
+    Fp28 b4;
+    f_set(b4, K28_ONE);
+    b4 = c_dbl(c_dbl(b4));                     // 4 xi = 4 + 4 u: 4 in both coefficients
+    const Fp28 d = c_sub(c_sub(pair_mul_inline(y, y, c), pair_mul_inline(pair_mul_inline(x, x, c), x, c)), b4);
+    Acc acc;
+    acc_zero(acc);
+#pragma unroll
+    for (int i = 0; i < NL; i++) acc.c[i] = d.l[i];
+    int32_t t[NL];
+    acc_reduce(t, acc);
+    uint32_t f[NL];
+    canon28(f, t);
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) o |= f[i];
+    const int z = o == 0 ? 1 : 0;
+    return z && __builtin_amdgcn_update_dpp(0, z, 0xB1, 0xf, 0xf, false);
+}
+
+// PREP_CLN: Costello-Lange-Naehrig steps in homogeneous projective coordinates with freely scaled lines (tools/prepasm.py), for the
+// fused pairing paths only - any factor of the Miller value that lies in Fp2 dies in the final exponentiation; PREP_JAC: the
+// upstream-shaped Jacobian steps of ePrint 2010/354 Alg. 26 / 27 (zkp_multi_miller_loop_batch exposes that Miller value).
+// The CLN doubling has b' = 4 xi built in, so on a G2 point off the twist it computes another function: a PREP_CLN wavefront with a
+// live pair (no infinity) off the twist stores nothing, and PREP_JAC_OFF_TWIST - launched after it on the same grid - runs exactly
+// those wavefronts on the Jacobian steps (same records, same order; on the twist the two line shapes differ by Fp2 factors only).
+// Valid inputs never leave the CLN steps; the test costs three Fp2 products per pair.  One body, three kernels (below).
+enum { PREP_JAC = 0, PREP_CLN = 1, PREP_JAC_OFF_TWIST = 2 };
+template <int MODE>
+__device__ __forceinline__ void prep_lines(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2, uint32_t n_pairs_in,
+                                           uint32_t k, uint32_t k_in, uint32_t j0, uint32_t nc_in, int4* lines, NDev nd) {
     // nc_in checks of k pairs each (n_pairs_in = nc_in * k); with a device-resident count the launch covers the checks that exist, and
     // their number is the stride of the line records (k_coop computes the same)
     const uint32_t nc = eff_n(nc_in, nd);
@@ -663,6 +707,11 @@ __global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines(const uint64_t* g
         park_st(QX, r.x);
         fp28_from_wire(r.y, g2 + 24 * src + 12 + 6 * c);
         park_st(QY, r.y);
+    }
+    constexpr bool CLN = MODE == PREP_CLN;
+    if (MODE != PREP_JAC) {        // wave-uniform: each wavefront is run by exactly one of the two fused launches
+        const bool off_wave = __ballot(live_lane && !dead && !on_twist_pair(r.x, r.y, c)) != 0;
+        if (off_wave != (MODE == PREP_JAC_OFF_TWIST)) return;
     }
     if (c == 0) f_set(r.z, K28_ONE); else f_zero(r.z);
     if (CLN) r.z = c_dbl(r.z);    // W = 2 Z
@@ -712,6 +761,18 @@ __global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines(const uint64_t* g
             step++;
         }
     }
+}
+// k_prep_lines<true>: the fused paths' CLN steps; k_prep_lines<false>: the Jacobian steps of zkp_multi_miller_loop_batch;
+// k_prep_lines_off_twist: the fused paths' wavefronts with a G2 point off the twist, on the Jacobian steps
+template <bool CLN>
+__global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1, const uint8_t* inf2,
+                                                       uint32_t n_pairs_in, uint32_t k, uint32_t k_in, uint32_t j0, uint32_t nc_in, int4* lines, NDev nd) {
+    prep_lines<CLN ? PREP_CLN : PREP_JAC>(g1, g2, inf1, inf2, n_pairs_in, k, k_in, j0, nc_in, lines, nd);
+}
+__global__ void __launch_bounds__(64, PREP_WAVES) k_prep_lines_off_twist(const uint64_t* g1, const uint64_t* g2, const uint8_t* inf1,
+                                                                 const uint8_t* inf2, uint32_t n_pairs_in, uint32_t k, uint32_t k_in, uint32_t j0,
+                                                                 uint32_t nc_in, int4* lines, NDev nd) {
+    prep_lines<PREP_JAC_OFF_TWIST>(g1, g2, inf1, inf2, n_pairs_in, k, k_in, j0, nc_in, lines, nd);
 }
 
 // =============================================================================== validity checks on the 28-bit core
@@ -2268,10 +2329,12 @@ static hipError_t prep(CoopPipe* pp, const uint64_t* g1, const uint64_t* g2, con
     const size_t prep_lds = 4 * 4 * 64 * sizeof(int4);
     { hipError_t ep = prime(pp->owner, s, (2 * (size_t)n_pairs + 63) / 64, PRIME_PREP); if (ep != hipSuccess) return ep; }
     ProfScope prof(pp->owner, s, PROF_PREP);
-    if (fused)
-        hipLaunchKernelGGL(k_prep_lines<true>, dim3((2 * n_pairs + 63) / 64), dim3(64), prep_lds, s, g1 + 12 * p0, g2 + 24 * p0, i1 ? i1 + p0 : nullptr,
-                           i2 ? i2 + p0 : nullptr, n_pairs, g, k_in, j0, n, pp->lines, pp->nd);
-    else
+    if (fused) {   // the CLN steps, then the Jacobian steps for the wavefronts with a G2 point off the twist (normally none: they return)
+        hipLaunchKernelGGL(k_prep_lines<true>, dim3((2 * n_pairs + 63) / 64), dim3(64), prep_lds, s, g1 + 12 * p0, g2 + 24 * p0,
+                           i1 ? i1 + p0 : nullptr, i2 ? i2 + p0 : nullptr, n_pairs, g, k_in, j0, n, pp->lines, pp->nd);
+        hipLaunchKernelGGL(k_prep_lines_off_twist, dim3((2 * n_pairs + 63) / 64), dim3(64), prep_lds, s, g1 + 12 * p0, g2 + 24 * p0,
+                           i1 ? i1 + p0 : nullptr, i2 ? i2 + p0 : nullptr, n_pairs, g, k_in, j0, n, pp->lines, pp->nd);
+    } else
         hipLaunchKernelGGL(k_prep_lines<false>, dim3((2 * n_pairs + 63) / 64), dim3(64), prep_lds, s, g1 + 12 * p0, g2 + 24 * p0, i1 ? i1 + p0 : nullptr,
                            i2 ? i2 + p0 : nullptr, n_pairs, g, k_in, j0, n, pp->lines, pp->nd);
     return hipGetLastError();
@@ -2629,6 +2692,7 @@ hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hip
         if (which >= 12 && which <= 14) return run_prog(d, &v, ids2[which - 12], (uint32_t)n, (uint32_t)n, 1, nullptr, nullptr, nullptr, nullptr);
         if (which == 10 || which == 15) {                          // 15: the upstream-shaped lines (k_prep_lines<false>)
             const uint64_t* zero = (const uint64_t*)v.state;      // 36 u64 of zeros per pair: the state buffer is far larger
+            // (0, 0) is off the twist: 10 times the fused path's twist test and its Jacobian launch, not the CLN steps
             return prep(&v, zero, zero + 12 * n, nullptr, nullptr, 0, (uint32_t)n, 1, 0, 1, which == 10);
         }
         if (which == 11) return run_prog(d, &v, ZKP_PROG_MILLER1_STATE, (uint32_t)n, (uint32_t)n, 1, nullptr, nullptr, nullptr, nullptr);

@@ -596,7 +596,8 @@ ZKP_DEV ZKP_NOINLINE void final_exponentiation(Fp12* out, const Fp12* fin) {
     Fp12 t0, t1, t2, t3, t4, t5, t6;
     t0 = *fin;
     for (int i = 0; i < 6; i++) fp12_frob(&t0, &t0);
-    if (!fp12_inv(&t1, fin)) { fp12_one(out); return; }
+    // f == 0 (a Miller loop on points off the curves) is not invertible: the zero record, so a check on it fails
+    if (!fp12_inv(&t1, fin)) { fp6_zero(&out->c0); fp6_zero(&out->c1); return; }
     fp12_mul(&t2, &t0, &t1);
     t1 = t2;
     fp12_frob(&t2, &t2);
