@@ -1073,6 +1073,18 @@ def from_mont(l):
     return limbs_value(l) * RINV % P
 
 
+# what a search over operands reads (tests/golden/gen_adversarial.py): while STATS is a dict, the models below record the extremes
+# of their internal quantities in it.  COL_LIMIT_BITS is the emulator's own margin for an accumulation column: the kernels' hard
+# limit is the int64 (2^63); a canonical input that lands between the two is to be reported, not a kernel bug.
+STATS = None
+COL_LIMIT_BITS = 62
+
+
+def _stat(key, v):
+    if STATS is not None and v > STATS.get(key, 0):
+        STATS[key] = v
+
+
 def lo28s(v):
     x = v & ((1 << W) - 1)
     return x - (1 << W) if x >= (1 << (W - 1)) else x
@@ -1086,6 +1098,7 @@ def acc_reduce(col):
         for j in range(NL):
             col[i + j] += m * P_LIMBS[j]
             assert abs(col[i + j]) < (1 << 63), "column overflow in reduction"
+            _stat("red_col", abs(col[i + j]))
         assert col[i] & ((1 << W) - 1) == 0
         col[i + 1] += col[i] >> W
     # carry-propagate the signed 64-bit columns c[14..26] into balanced 28-bit limbs (the top limb keeps the rest)
@@ -1107,6 +1120,7 @@ def weak_norm(x):
     c = []
     for i in range(NL - 1):
         assert abs(x[i]) < (1 << 31) - (1 << 27), "limb overflow before weak_norm"
+        _stat("wn_limb", abs(x[i]))
         ci = (x[i] + (1 << (W - 1))) >> W
         c.append(ci)
         x[i] -= ci << W
@@ -1122,9 +1136,11 @@ def vred(x):
     t = x[NL - 1]
     q = ((t >> VRED_SHIFT_IN) * VRED_C + (1 << (VRED_SHIFT_OUT - 1))) >> VRED_SHIFT_OUT
     assert abs(q) <= 14, "value too large for vred (q = %d)" % q
+    _stat("q_vred", abs(q))
     y = [a - q * b for a, b in zip(x, P_BAL)]
     y = weak_norm(y)
     assert abs(limbs_value(y)) < 0.51 * P
+    _stat("reduced", abs(limbs_value(y)) / P)
     return y
 
 
@@ -1134,14 +1150,18 @@ def epilogue(r, e, alpha, beta):
     t = alpha * r[NL - 1] + beta * e[NL - 1]
     q = ((t >> VRED_SHIFT_IN) * VRED_C + (1 << (VRED_SHIFT_OUT - 1))) >> VRED_SHIFT_OUT
     assert abs(q) <= 14, "value too large for the epilogue (q = %d)" % q
+    _stat("q_epi", abs(q))
     y = weak_norm([alpha * a + beta * b - q * c for a, b, c in zip(r, e, P_BAL)])
     assert abs(limbs_value(y)) < 0.51 * P
+    _stat("reduced", abs(limbs_value(y)) / P)
     return y
 
 
 def canonical_from_reduced(l):
     v = limbs_value(l)
     assert -P < v < 2 * P, "value out of canonicalisation range"
+    _stat("canon_hi", v / P)
+    _stat("canon_lo", -v / P)
     return v % P
 
 
@@ -1220,7 +1240,8 @@ class Emu:
                         self.counts["products"] += 1
                     mx = max(abs(c) for c in col)
                     self.max_col = max(self.max_col, mx)
-                    assert mx < (1 << 62), "column overflow in accumulation (%d bits)" % mx.bit_length()
+                    _stat("max_col", mx)
+                    assert mx < (1 << COL_LIMIT_BITS), "column overflow in accumulation (%d bits)" % mx.bit_length()
                     r = acc_reduce(col)
                     e = self.slot[ln["e"]]
                     if st["epi"]:
@@ -1283,7 +1304,8 @@ def mont_mul(pairs):
             if a[i]:
                 for j in range(NL):
                     col[i + j] += a[i] * b[j]
-    assert max(abs(c) for c in col) < (1 << 62), "column overflow in accumulation"
+    _stat("max_col", max(abs(c) for c in col))
+    assert max(abs(c) for c in col) < (1 << COL_LIMIT_BITS), "column overflow in accumulation"
     return acc_reduce(col)
 
 
@@ -1294,6 +1316,7 @@ def sq_combine(t, x, neg):
     assert abs(top) < (1 << 31)
     q = ((top >> VRED_SHIFT_IN) * VRED_C + (1 << (VRED_SHIFT_OUT - 1))) >> VRED_SHIFT_OUT
     assert abs(q) <= 14
+    _stat("q_sq", abs(q))
     out, v = [], 0
     for i in range(NL):
         assert abs(t[i]) < (1 << 31) and abs(sx[i]) < (1 << 31)
@@ -1307,6 +1330,7 @@ def sq_combine(t, x, neg):
             assert abs(v) < (1 << 31)
             out.append(v)
     assert abs(limbs_value(out)) < 0.51 * P
+    _stat("reduced", abs(limbs_value(out)) / P)
     return out
 
 
