@@ -19,6 +19,10 @@
  *   zkp_g1_msm_batch / g2           sum_i [k_i] P_i (no upstream counterpart: Add and Mul composed)
  *   zkp_fp_op_batch                 bls12381_sys_bigint(out, op, a, b)       src/fp.rs:376,443 (op 0 = mul, 1 = add); also
  *                                   Fp::sub / neg / square / invert          src/fp.rs:307-319, 383-411, 453-455
+ *   zkp_fr_op_batch                 Fr add / sub / neg / mul / square / invert src/fr.rs:402-411, 384-398, 415-431, 365-381, 225-227, 266-362
+ *   zkp_fr_from_wide_batch          Fr::from_bytes_wide / from_u512           src/fr.rs:192-217
+ *   zkp_fr_fold_batch,              sum_c w_c x_{c,i} in Fr and the batched Groth16 verifier built on it (no upstream counterpart:
+ *   zkp_groth16_verify_batch        Fr Mul / Add and pairing() composed)
  *   zkp_tower_op_batch              Fp2 / Fp6 / Fp12 mul, square, mul_by_014, src/fp2.rs:171-209, src/fp6.rs:188-288,
  *                                   conjugate, frobenius_map (the TRUE map),  src/fp12.rs:99-210 (:143-170 is wrong)
  *                                   invert, mul_by_nonresidue, mul_by_1 / 01  src/fp2.rs:95-102,161-168,278-296, src/fp6.rs:102-141,291-309
@@ -231,6 +235,72 @@ int zkp_g1_mul_endo_batch_dev(zkp_ctx* ctx, const void* d_base, const void* d_in
 int zkp_pairing_check_batch_rlc(zkp_ctx* ctx, const zkp_rlc_batch* b, const uint64_t* rand /* 2 u64 per check */, int flags, int* all_ok);
 /* device flavour: the batch's pointers, d_rand and d_all_ok are device pointers (the descriptor itself is a host struct) */
 int zkp_pairing_check_batch_rlc_dev(zkp_ctx* ctx, const zkp_rlc_batch* b, const void* d_rand, int flags, void* d_all_ok, void* stream);
+
+/* ---- the scalar field Fr, the Fr fold and the batched Groth16 verifier (symbols added under ABI version 4) -----------------------------
+ * Fr elements are 4 u64, little-endian, canonical (< r, the order of G1 / G2 / Gt), as the MSM and scalar-multiplication scalars.
+ * zkp_fr_op_batch: out[i] = a[i] op b[i] (op: zkp_fr_op; unary operations ignore b, which may be NULL); 0 inverts to 0 where the
+ * reference returns None (src/fr.rs:266-362).  Validation mode (zkp_set_validate): an element >= r gives ZKP_ERR_NONCANONICAL on the
+ * host flavour; the _dev flavour ORs into the context's validation word (zkp_take_validation_status_dev) like every other _dev call.
+ * zkp_fr_from_wide_batch: out[i] = the 512-bit little-endian integer bytes[64 i .. 64 i + 63] mod r (Fr::from_bytes_wide,
+ * src/fr.rs:192-217); any input is legal.
+ * zkp_fr_fold_batch: out[i] = sum_c w[c] x[c][i] mod r for i < l, and *sum_w = sum_c w[c] mod r (sum_w may be NULL); w holds n elements,
+ * x n rows of l.  Inputs are canonical (validation mode as above); n <= 2^24, l <= 65535, n l <= 2^31 - 1, else ZKP_ERR_ARG; n == 0
+ * gives zeros.  The sums are accumulated as exact integers (a product is below 2^512, 2^24 of them below 2^544 = 17 words) and
+ * reduced once per output.  Workspace (grow-only, layout zkvm_pairings_amd/csrc/zkp_groth16_plan.hpp): 68 B per output and workgroup,
+ * at most 1024 workgroups per tile of 64 outputs - 4.5 MB at worst.  The _dev flavours are asynchronous and capturable into a hipGraph
+ * once that workspace has reached the call's size.
+ * zkp_groth16_verify_batch: n Groth16 proofs (A_c, B_c, C_c) with n_inputs public inputs x_{c,i} each, against ONE verifying key.
+ * Proof c is valid iff e(A_c, B_c) == e(alpha, beta) e(vk_x_c, gamma) e(C_c, delta), vk_x_c = IC_0 + sum_i x_{c,i} IC_{i+1}.  The call
+ * tests, with r_c = a_c + b_c z^2 from rand[2c], rand[2c + 1] exactly as zkp_pairing_check_batch_rlc forms them (draw them uniformly at
+ * random, per call, from a cryptographic source), s_0 = sum_c r_c and s_{i+1} = sum_c r_c x_{c,i} (mod r):
+ *     prod_c e([r_c] A_c, B_c) * e(-sum_c [r_c] C_c, delta) * e(-sum_i [s_i] IC_i, gamma) * e(-[s_0] alpha, beta) == 1
+ * *all_ok = that test AND every point valid AND every public input < r AND no (a_c, b_c) = (0, 0): 1 implies, with probability at
+ * least 1 - 2^-128, that every proof is valid, and a batch of valid proofs always gives 1.  Points are in wire format; key points are
+ * finite (a key has no infinity flags); the inf_* arrays of the batch may be NULL.  An invalid point, a public input >= r (x + r is
+ * not x to a verifier) and a zero (a, b) are RESULTS (*all_ok = 0), not errors, in either validation mode; coordinates >= p keep the
+ * rule above (ZKP_ERR_NONCANONICAL / the validation word when validation is on).  Unless flags says otherwise every proof point
+ * (ZKP_GROTH16_POINTS_CHECKED) and every key point (ZKP_GROTH16_VK_CHECKED) goes through is_valid first.  n == 0 gives 1; n_inputs == 0
+ * is legal (vk_x = IC_0).  ZKP_ERR_ARG: null pointers with non-zero counts, n > 2^24, n_inputs > 65535, n n_inputs > 2^31 - 1, unknown
+ * flags.  Cost: n endomorphism scalings and one Miller product over the n free pairs, one G1 MSM of n terms (the C column), the fold, one
+ * MSM call of two sums of n_inputs + 1 terms (the IC sum and [s_0] alpha), one Miller product over three pairs, ONE final exponentiation.
+ * The signs are handled on the device (the three G2 key points are negated): there is no host-side "prepare" step.  The _dev flavour
+ * is asynchronous (no read-back) and capturable into a hipGraph once the context's workspaces have reached the call's size; d_all_ok
+ * (one int32) is required.  Workspace (grow-only, zkp_groth16_plan.hpp) per proof: 32 B of scalar, 97 B of scaled point, 3 B of status
+ * without ZKP_GROTH16_POINTS_CHECKED; per public input 257 B; the fold's partial sums (above); plus the MSM workspace of n terms (about
+ * 1.0 KB per term) and the Miller loop's own workspace. */
+typedef enum {
+    ZKP_FR_MUL = 0,
+    ZKP_FR_ADD = 1,
+    ZKP_FR_SUB = 2,
+    ZKP_FR_NEG = 3,
+    ZKP_FR_SQUARE = 4,
+    ZKP_FR_INVERT = 5       /* 0 gives 0 (the reference returns None, src/fr.rs:266-362) */
+} zkp_fr_op;
+typedef struct {
+    const void *alpha_g1, *beta_g2, *gamma_g2, *delta_g2;   /* one point each */
+    size_t n_inputs;
+    const void* ic;                                         /* n_inputs + 1 G1 points */
+} zkp_groth16_vk;
+typedef struct {
+    size_t n;
+    const void *a, *inf_a, *b, *inf_b, *c, *inf_c;          /* n G1, n G2, n G1 (+ optional infinity bytes) */
+    const void* inputs;                                     /* n x n_inputs x 4 u64, one row per proof */
+} zkp_groth16_batch;
+#define ZKP_GROTH16_POINTS_CHECKED 1   /* flags: the proof points are known valid */
+#define ZKP_GROTH16_VK_CHECKED     2   /* flags: the key points are known valid */
+int zkp_fr_op_batch(zkp_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+int zkp_fr_op_batch_dev(zkp_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, void* d_out, void* stream);
+int zkp_fr_from_wide_batch(zkp_ctx* ctx, const uint8_t* bytes /* 64 B little-endian each */, size_t n, uint64_t* out);
+int zkp_fr_from_wide_batch_dev(zkp_ctx* ctx, const void* d_bytes, size_t n, void* d_out, void* stream);
+int zkp_fr_fold_batch(zkp_ctx* ctx, const uint64_t* w /* n x 4 */, const uint64_t* x /* n x l x 4, row per w */, size_t n, size_t l,
+                      uint64_t* out /* l x 4 */, uint64_t* sum_w /* 4 u64, may be NULL */);
+int zkp_fr_fold_batch_dev(zkp_ctx* ctx, const void* d_w, const void* d_x, size_t n, size_t l, void* d_out, void* d_sum_w, void* stream);
+/* host flavour: the key's and the batch's pointers are host arrays */
+int zkp_groth16_verify_batch(zkp_ctx* ctx, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const uint64_t* rand /* 2 u64 per proof */,
+                             int flags, int* all_ok);
+/* device flavour: the key's and the batch's pointers, d_rand and d_all_ok are device pointers (the descriptors are host structs) */
+int zkp_groth16_verify_batch_dev(zkp_ctx* ctx, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const void* d_rand, int flags,
+                                 void* d_all_ok, void* stream);
 
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).

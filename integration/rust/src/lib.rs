@@ -54,6 +54,42 @@ pub struct zkp_rlc_batch {
 /// flags of `zkp_pairing_check_batch_rlc`: skip the subgroup checks (the caller guarantees every point is valid)
 pub const ZKP_RLC_POINTS_CHECKED: c_int = 1;
 
+/// a Groth16 verifying key for `zkp_groth16_verify_batch[_dev]` (include/zkp_pairings.h `zkp_groth16_vk`, same field order): one point each,
+/// then n_inputs + 1 G1 points; key points are finite
+#[repr(C)]
+#[allow(non_camel_case_types)]
+pub struct zkp_groth16_vk {
+    pub alpha_g1: *const c_void,
+    pub beta_g2: *const c_void,
+    pub gamma_g2: *const c_void,
+    pub delta_g2: *const c_void,
+    pub n_inputs: usize,
+    pub ic: *const c_void,
+}
+/// n proofs (A, B, C with optional infinity bytes) and their public inputs (n x n_inputs x 4 u64), `zkp_groth16_batch`
+#[repr(C)]
+#[allow(non_camel_case_types)]
+pub struct zkp_groth16_batch {
+    pub n: usize,
+    pub a: *const c_void,
+    pub inf_a: *const c_void,
+    pub b: *const c_void,
+    pub inf_b: *const c_void,
+    pub c: *const c_void,
+    pub inf_c: *const c_void,
+    pub inputs: *const c_void,
+}
+/// flags of `zkp_groth16_verify_batch`: the proof points / the key points are known valid
+pub const ZKP_GROTH16_POINTS_CHECKED: c_int = 1;
+pub const ZKP_GROTH16_VK_CHECKED: c_int = 2;
+/// zkp_fr_op (Fr elements: 4 u64, canonical)
+pub const ZKP_FR_MUL: c_int = 0;
+pub const ZKP_FR_ADD: c_int = 1;
+pub const ZKP_FR_SUB: c_int = 2;
+pub const ZKP_FR_NEG: c_int = 3;
+pub const ZKP_FR_SQUARE: c_int = 4;
+pub const ZKP_FR_INVERT: c_int = 5;
+
 /// zkp_fp_op: 0 and 1 are the zkVM precompile's op numbers (reference src/fp.rs:376,443)
 pub const ZKP_FP_MUL: c_int = 0;
 pub const ZKP_FP_ADD: c_int = 1;
@@ -181,6 +217,19 @@ extern "C" {
     pub fn zkp_pairing_check_batch_rlc(ctx: *mut ZkpCtx, b: *const zkp_rlc_batch, rand: *const u64, flags: c_int, all_ok: *mut c_int) -> c_int;
     pub fn zkp_pairing_check_batch_rlc_dev(ctx: *mut ZkpCtx, b: *const zkp_rlc_batch, d_rand: *const c_void, flags: c_int, d_all_ok: *mut c_void,
                                            stream: *mut c_void) -> c_int;
+    // the scalar field, the Fr fold and the batched Groth16 verifier (added under ABI version 4)
+    pub fn zkp_fr_op_batch(ctx: *mut ZkpCtx, op: c_int, a: *const u64, b: *const u64, n: usize, out: *mut u64) -> c_int;
+    pub fn zkp_fr_op_batch_dev(ctx: *mut ZkpCtx, op: c_int, d_a: *const c_void, d_b: *const c_void, n: usize, d_out: *mut c_void,
+                               stream: *mut c_void) -> c_int;
+    pub fn zkp_fr_from_wide_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out: *mut u64) -> c_int;
+    pub fn zkp_fr_from_wide_batch_dev(ctx: *mut ZkpCtx, d_bytes: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_fr_fold_batch(ctx: *mut ZkpCtx, w: *const u64, x: *const u64, n: usize, l: usize, out: *mut u64, sum_w: *mut u64) -> c_int;
+    pub fn zkp_fr_fold_batch_dev(ctx: *mut ZkpCtx, d_w: *const c_void, d_x: *const c_void, n: usize, l: usize, d_out: *mut c_void,
+                                 d_sum_w: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_groth16_verify_batch(ctx: *mut ZkpCtx, vk: *const zkp_groth16_vk, b: *const zkp_groth16_batch, rand: *const u64, flags: c_int,
+                                    all_ok: *mut c_int) -> c_int;
+    pub fn zkp_groth16_verify_batch_dev(ctx: *mut ZkpCtx, vk: *const zkp_groth16_vk, b: *const zkp_groth16_batch, d_rand: *const c_void,
+                                        flags: c_int, d_all_ok: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn zkp_g1_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g1: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g2_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g2: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g1_compress_batch(ctx: *mut ZkpCtx, g1: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;

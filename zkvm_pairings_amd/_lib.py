@@ -26,6 +26,20 @@ class RlcBatch(ctypes.Structure):
                 ("s1", c_sz), ("col_g2", c_vp), ("col_inf2", c_vp), ("fixed_g1", c_vp), ("fixed_inf1", c_vp)]
 
 
+GROTH16_POINTS_CHECKED = 1   # ZKP_GROTH16_POINTS_CHECKED
+GROTH16_VK_CHECKED = 2       # ZKP_GROTH16_VK_CHECKED
+
+
+class Groth16Vk(ctypes.Structure):
+    """zkp_groth16_vk: a verifying key for zkp_groth16_verify_batch[_dev] (field order of include/zkp_pairings.h)"""
+    _fields_ = [("alpha_g1", c_vp), ("beta_g2", c_vp), ("gamma_g2", c_vp), ("delta_g2", c_vp), ("n_inputs", c_sz), ("ic", c_vp)]
+
+
+class Groth16Batch(ctypes.Structure):
+    """zkp_groth16_batch: n proofs and their public inputs"""
+    _fields_ = [("n", c_sz), ("a", c_vp), ("inf_a", c_vp), ("b", c_vp), ("inf_b", c_vp), ("c", c_vp), ("inf_c", c_vp), ("inputs", c_vp)]
+
+
 # name -> (restype, argtypes); MUST list every symbol include/zkp_pairings.h declares
 SIGNATURES = {
     "zkp_abi_version": (c_int, []),
@@ -87,6 +101,14 @@ SIGNATURES = {
     "zkp_g1_mul_endo_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_pairing_check_batch_rlc": (c_int, [c_vp, ctypes.POINTER(RlcBatch), c_vp, c_int, ctypes.POINTER(c_int)]),
     "zkp_pairing_check_batch_rlc_dev": (c_int, [c_vp, ctypes.POINTER(RlcBatch), c_vp, c_int, c_vp, c_vp]),
+    "zkp_fr_op_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "zkp_fr_op_batch_dev": (c_int, [c_vp, c_int, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_fr_from_wide_batch": (c_int, [c_vp, c_vp, c_sz, c_vp]),
+    "zkp_fr_from_wide_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_fr_fold_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "zkp_fr_fold_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_groth16_verify_batch": (c_int, [c_vp, ctypes.POINTER(Groth16Vk), ctypes.POINTER(Groth16Batch), c_vp, c_int, ctypes.POINTER(c_int)]),
+    "zkp_groth16_verify_batch_dev": (c_int, [c_vp, ctypes.POINTER(Groth16Vk), ctypes.POINTER(Groth16Batch), c_vp, c_int, c_vp, c_vp]),
     "zkp_g1_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g2_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g1_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),

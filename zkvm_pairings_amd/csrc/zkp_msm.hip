@@ -28,6 +28,22 @@ size_t sort_temp_bytes(uint32_t keys) {
     return bytes;
 }
 
+// The bucket and window sums are zeroed by a kernel, where msm_run used to call hipMemsetAsync.  Observed on an MI355X: an MSM captured
+// into a hipGraph with the two memset nodes gave the right sums on the first replay and wrong ones on every later replay (G1, 1 to 127
+// terms and two sums of 1 to 65 terms, twelve replays each; eager calls and first replays were always right - DESIGN section 3.2).  With
+// the fill kernel every replay is right.  The earlier graph tests replay once, so they never saw it; the Groth16 verifier's test
+// replays twice.  bytes is a multiple of 16 (whole records), p 16-byte aligned.
+__global__ void k_zero_fill(uint4* p, size_t n16) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(0, 0, 0, 0);
+}
+inline hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {
+    const size_t n16 = bytes / 16;
+    if (!n16) return hipSuccess;
+    const size_t want = (n16 + 255) / 256;
+    hipLaunchKernelGGL(k_zero_fill, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, (uint4*)p, n16);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t msm_workspace_bytes(int which, size_t m, size_t n_msm, int shared) {
@@ -72,7 +88,7 @@ hipError_t msm_run(int which, void* ws, const uint64_t* points, const uint8_t* i
         MSM_CHK(hipcub::DeviceRadixSort::SortPairs(b + L.sort_temp, temp, k_in, k_out, v_in, v_out, (int)keys, 0, (int)p.key_bits, s));
         mark(3);
         const uint32_t n_buckets = segs * p.windows * p.nb, n_sums = segs * p.windows;
-        MSM_CHK(hipMemsetAsync(b + L.buckets, 0, (size_t)n_buckets * jr, s));
+        MSM_CHK(zero_fill(b + L.buckets, (size_t)n_buckets * jr, s));
         // level 0 from the sorted digits, then the partial sums ping-pong until one run is left
         uint32_t n = keys;
         const uint32_t* kin = k_out;
@@ -86,7 +102,7 @@ hipError_t msm_run(int which, void* ws, const uint64_t* points, const uint8_t* i
         }
         mark(4);
         MSM_CHK(msm_reduce(which, b + L.buckets, n_sums, p.split, p.chunk, (uint32_t*)(b + L.chunk_k), b + L.chunk_j, s));
-        MSM_CHK(hipMemsetAsync(b + L.wsums, 0, (size_t)n_sums * jr, s));
+        MSM_CHK(zero_fill(b + L.wsums, (size_t)n_sums * jr, s));
         n = n_sums * p.split;
         kin = (const uint32_t*)(b + L.chunk_k);
         jin = b + L.chunk_j;

@@ -22,6 +22,8 @@
 #include "zkp_msm_plan.hpp"
 #include "zkp_rlc.hpp"
 #include "zkp_rlc_plan.hpp"
+#include "zkp_groth16.hpp"
+#include "zkp_groth16_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -454,6 +456,8 @@ struct zkp_ctx {
     size_t msm_cap = 0;
     void* rlc_ws = nullptr;     // grow-only workspace of the RLC batch check (zkp_rlc_plan.hpp layout)
     size_t rlc_cap = 0;
+    void* g16_ws = nullptr;     // grow-only workspace of the Fr fold and the Groth16 verifier (zkp_groth16_plan.hpp layout)
+    size_t g16_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -875,6 +879,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->prod) (void)hipFree(c->prod);
     if (c->msm_ws) (void)hipFree(c->msm_ws);
     if (c->rlc_ws) (void)hipFree(c->rlc_ws);
+    if (c->g16_ws) (void)hipFree(c->g16_ws);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1535,6 +1540,16 @@ int grow_rlc(zkp_ctx* c, size_t bytes, void** ws) {
     *ws = c->rlc_ws;
     return ZKP_OK;
 }
+int grow_g16(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->g16_cap) {
+        if (c->g16_ws) { HIPCHK(c, hipFree(c->g16_ws)); c->g16_ws = nullptr; c->g16_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->g16_ws, bytes));
+        zkp_dbg_alloc("ctx.g16", c->g16_ws, bytes);
+        c->g16_cap = bytes;
+    }
+    *ws = c->g16_ws;
+    return ZKP_OK;
+}
 int grow_msm(zkp_ctx* c, size_t bytes) { return msm_grow(c, bytes); }
 int msm(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, void* out, void* out_inf, hipStream_t s) {
     return msm_dev(c, which, pts, inf, sc, m, n_msm, 0, out, out_inf, s, nullptr);
@@ -2074,6 +2089,164 @@ int zkp_profile_pairing_dev(zkp_ctx* c, const void* g1, const void* g2, size_t n
     HostIO io(c);
     if (int rc = io.status()) return rc;
     return coop_rc(c, "coop_profile_pairing", zkp::coop_profile_pairing(&c->coop, (const uint64_t*)g1, (const uint64_t*)g2, n, (uint64_t*)out, ms, launches, c->stream));
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- Fr, the Fr fold and the batched Groth16 verifier (zkp_groth16.hip)
+namespace {
+// validation mode for Fr elements: the host flavour reads the word back, the _dev flavour ORs into the sticky one
+int validate_fr_dev(zkp_ctx* c, const void* d, size_t n) {
+    if (!c->validate || !n || !d) return ZKP_OK;
+    HIPCHK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+    HIPCHK(c, zkp::fr_check_canonical((const uint64_t*)d, n, c->d_flag, c->stream));
+    int bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) { c->err = "input limbs >= r"; return ZKP_ERR_NONCANONICAL; }
+    return ZKP_OK;
+}
+int validate_fr_on_stream(zkp_ctx* c, const void* d, size_t n, hipStream_t s) {
+    if (!c->validate || !n || !d) return ZKP_OK;
+    HIPCHK(c, zkp::fr_check_canonical((const uint64_t*)d, n, c->d_flag + 2, s));
+    return ZKP_OK;
+}
+bool fr_op_unary(int op) { return op == ZKP_FR_NEG || op == ZKP_FR_SQUARE || op == ZKP_FR_INVERT; }
+bool fr_op_args_bad(const zkp_ctx* c, int op, const void* a, const void* b, size_t n, const void* out) {
+    return !c || op < 0 || op > ZKP_FR_INVERT || n > 0x7fffffffu || (n && (!a || !out || (!fr_op_unary(op) && !b)));
+}
+// the fold on device pointers: zeros for n == 0, else the partial sums in the context's workspace and the two stages
+int fr_fold_dev(zkp_ctx* c, const void* w, const void* x, size_t n, size_t l, void* out, void* sum_w, hipStream_t s) {
+    if (!n) {
+        if (l) HIPCHK(c, hipMemsetAsync(out, 0, l * 32, s));
+        if (sum_w) HIPCHK(c, hipMemsetAsync(sum_w, 0, 32, s));
+        return ZKP_OK;
+    }
+    const zkp::g16::FoldLayout L = zkp::g16::fold_layout(zkp::g16::fold_plan(n, l));
+    void* ws = nullptr;
+    if (int rc = zkp::ctxop::grow_g16(c, L.total, &ws)) return rc;
+    return coop_rc(c, "fr_fold", zkp::fr_fold((char*)ws + L.part, (char*)ws + L.sum, (const uint64_t*)w, (const uint64_t*)x, n, l, (uint64_t*)out,
+                                              (uint64_t*)sum_w, nullptr, s));
+}
+bool fr_fold_args_bad(const zkp_ctx* c, const void* w, const void* x, size_t n, size_t l, const void* out) {
+    return !c || zkp::g16::fold_args_bad(n, l) || (l && !out) || (n && (!w || (l && !x)));
+}
+bool g16_args_bad(const zkp_ctx* c, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const void* rand, int flags, const void* all_ok) {
+    if (!c || !vk || !b || !all_ok || zkp::g16::args_bad(b->n, vk->n_inputs, flags)) return true;
+    if (!b->n) return false;
+    return !rand || !vk->alpha_g1 || !vk->beta_g2 || !vk->gamma_g2 || !vk->delta_g2 || !vk->ic || !b->a || !b->b || !b->c || (vk->n_inputs && !b->inputs);
+}
+// validation mode: v(pointer, Fp count) over every coordinate array of the key and the batch
+template <class V>
+int g16_validate(const zkp_groth16_vk* vk, const zkp_groth16_batch* b, V&& v) {
+    int rc;
+    if ((rc = v(b->a, b->n * 2)) || (rc = v(b->b, b->n * 4)) || (rc = v(b->c, b->n * 2)) || (rc = v(vk->alpha_g1, 2)) || (rc = v(vk->beta_g2, 4)) ||
+        (rc = v(vk->gamma_g2, 4)) || (rc = v(vk->delta_g2, 4)) || (rc = v(vk->ic, (vk->n_inputs + 1) * 2)))
+        return rc;
+    return ZKP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_fr_op_batch_dev(zkp_ctx* c, int op, const void* a, const void* b, size_t n, void* out, void* stream) {
+    if (fr_op_args_bad(c, op, a, b, n, out)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = validate_fr_on_stream(c, a, n, S(stream))) || (!fr_op_unary(op) && (rc = validate_fr_on_stream(c, b, n, S(stream))))) return rc;
+    return coop_rc(c, "fr_op", zkp::fr_op(op, (const uint64_t*)a, (const uint64_t*)b, n, (uint64_t*)out, S(stream)));
+}
+int zkp_fr_op_batch(zkp_ctx* c, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+    if (fr_op_args_bad(c, op, a, b, n, out)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const bool unary = fr_op_unary(op);
+    HostIO io(c);
+    const void* da = io.in(0, a, n * 32);
+    const void* db = unary ? nullptr : io.in(1, b, n * 32);
+    void* dout = io.out(4, out, n * 32);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, da, n)) || (rc = validate_fr_dev(c, db, n)) ||
+        (rc = coop_rc(c, "fr_op", zkp::fr_op(op, (const uint64_t*)da, (const uint64_t*)db, n, (uint64_t*)dout, c->stream))))
+        return rc;
+    return io.finish();
+}
+int zkp_fr_from_wide_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out, void* stream) {
+    if (!c || n > 0x7fffffffu || (n && (!bytes || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    return coop_rc(c, "fr_from_wide", zkp::fr_from_wide((const uint8_t*)bytes, n, (uint64_t*)out, S(stream)));
+}
+int zkp_fr_from_wide_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out) {
+    if (!c || n > 0x7fffffffu || (n && (!bytes || !out))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* din = io.in(0, bytes, n * 64);
+    void* dout = io.out(4, out, n * 32);
+    int rc;
+    if ((rc = io.status()) || (rc = coop_rc(c, "fr_from_wide", zkp::fr_from_wide((const uint8_t*)din, n, (uint64_t*)dout, c->stream)))) return rc;
+    return io.finish();
+}
+int zkp_fr_fold_batch_dev(zkp_ctx* c, const void* w, const void* x, size_t n, size_t l, void* out, void* sum_w, void* stream) {
+    if (fr_fold_args_bad(c, w, x, n, l, out)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_fr_on_stream(c, w, n, S(stream))) || (rc = validate_fr_on_stream(c, x, n * l, S(stream)))) return rc;
+    return fr_fold_dev(c, w, x, n, l, out, sum_w, S(stream));
+}
+int zkp_fr_fold_batch(zkp_ctx* c, const uint64_t* w, const uint64_t* x, size_t n, size_t l, uint64_t* out, uint64_t* sum_w) {
+    if (fr_fold_args_bad(c, w, x, n, l, out)) return ZKP_ERR_ARG;
+    if (!n) {
+        if (l) memset(out, 0, l * 32);
+        if (sum_w) memset(sum_w, 0, 32);
+        return ZKP_OK;
+    }
+    HostIO io(c);
+    const void* dw = io.in(0, w, n * 32);
+    const void* dx = l ? io.in(1, x, n * l * 32) : nullptr;
+    char* dout = (char*)io.slot(4, (l + 1) * 32);   // the l outputs, then the sum of the weights
+    if (dout) {
+        io.get(l ? out : nullptr, dout, l * 32);
+        io.get(sum_w, dout + l * 32, 32);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, dw, n)) || (rc = validate_fr_dev(c, dx, n * l)) ||
+        (rc = fr_fold_dev(c, dw, dx, n, l, dout, sum_w ? dout + l * 32 : nullptr, c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_groth16_verify_batch_dev(zkp_ctx* c, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const void* rand, int flags, void* all_ok,
+                                 void* stream) {
+    if (g16_args_bad(c, vk, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (b->n)
+        if (int rc = g16_validate(vk, b, [&](const void* d, size_t n_fp) { return validate_on_stream(c, d, n_fp, S(stream)); })) return rc;
+    return zkp::groth16_check_dev(c, vk, b, (const uint64_t*)rand, flags, (int*)all_ok, S(stream));
+}
+// the key's and the batch's thirteen arrays one after the other in slot 0 (256-byte aligned), then the same driver as the _dev flavour
+int zkp_groth16_verify_batch(zkp_ctx* c, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const uint64_t* rand, int flags, int* all_ok) {
+    if (g16_args_bad(c, vk, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    if (!b->n) { *all_ok = 1; return ZKP_OK; }
+    const size_t n = b->n, l = vk->n_inputs;
+    zkp_groth16_vk dv = *vk;
+    zkp_groth16_batch d = *b;
+    const void* drand = rand;
+    const void** field[13] = {&d.a, &d.inf_a, &d.b, &d.inf_b, &d.c, &d.inf_c, &d.inputs, &dv.alpha_g1, &dv.beta_g2, &dv.gamma_g2, &dv.delta_g2, &dv.ic, &drand};
+    const size_t bytes[13] = {n * 96, n, n * 192, n, n * 96, n, n * l * 32, 96, 192, 192, 192, (l + 1) * 96, n * 16};
+    size_t off[13], total = 0;
+    for (int i = 0; i < 13; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    char* dev = (char*)io.slot(0, total);
+    for (int i = 0; i < 13; i++) *field[i] = bytes[i] ? io.put(dev + off[i], *field[i], bytes[i]) : nullptr;
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = g16_validate(&dv, &d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
+        (rc = zkp::groth16_check_dev(c, &dv, &d, (const uint64_t*)drand, flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
 }
 
 }  // extern "C"

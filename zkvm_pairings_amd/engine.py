@@ -476,6 +476,134 @@ class PairingEngine:
             f1[:, k + s2:], f2[:, k + s2:] = fl(fixed_inf1, (1, s1)), fl(col_inf2, (n, s1))
         return e1.reshape(-1, 12), e2.reshape(-1, 24), f1.reshape(-1), f2.reshape(-1), kk
 
+    # ---- the scalar field Fr (4 u64 per element, canonical), the Fr fold and the batched Groth16 verifier
+    FR_OPS = {"mul": 0, "add": 1, "sub": 2, "neg": 3, "square": 4, "invert": 5}
+
+    def fr_op(self, op, a, b=None):
+        """out[i] = a[i] op b[i] in Fr (zkp_fr_op_batch): op a name in FR_OPS or its number; neg / square / invert ignore b; 0 inverts to
+        0.  numpy (n, 4) uint64 in, the same out; resident torch tensors stay on the GPU (the current stream)."""
+        op = int(self.FR_OPS.get(op, op))
+        if _is_torch(a):
+            import torch
+            self._t_check(a, 4, "a")
+            n = a.numel() // 4
+            if b is not None:
+                self._t_check(b, 4, "b", rows=n)
+            out = torch.empty((n, 4), dtype=a.dtype, device=a.device)
+            self._chk(self._lib.zkp_fr_op_batch_dev(self._h, op, self._tp(a), self._tp(b), n, self._tp(out), self._stream()))
+            return out
+        a = _np(a, 4)
+        b = None if b is None else _np(b, 4)
+        if b is not None and b.shape != a.shape:
+            raise ValueError("fr_op: operand shapes differ")
+        out = np.empty_like(a)
+        self._chk(self._lib.zkp_fr_op_batch(self._h, op, _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
+        return out
+
+    def fr_from_wide(self, data):
+        """64 little-endian bytes per element -> the 512-bit integer mod r (Fr::from_bytes_wide), (n, 4) uint64; a uint8 array / bytes, or
+        a resident uint8 tensor"""
+        if _is_torch(data):
+            import torch
+            self._t_check(data, 64, "bytes", dtypes=(torch.uint8,))
+            n = data.numel() // 64
+            out = torch.empty((n, 4), dtype=torch.int64, device=data.device)
+            self._chk(self._lib.zkp_fr_from_wide_batch_dev(self._h, self._tp(data), n, self._tp(out), self._stream()))
+            return out
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if buf.size % 64:
+            raise ValueError("byte string is not a multiple of 64 bytes")
+        out = np.empty((buf.size // 64, 4), dtype=np.uint64)
+        self._chk(self._lib.zkp_fr_from_wide_batch(self._h, _ptr(buf), buf.size // 64, _ptr(out)))
+        return out
+
+    def fr_fold(self, w, x, l=None):
+        """(out (l, 4), sum_w (4,)): out[i] = sum_c w[c] x[c][i] mod r and sum_w = sum_c w[c] mod r (zkp_fr_fold_batch); w (n, 4), x (n, l, 4)
+        or (n l, 4) with l given.  Resident torch tensors stay on the GPU."""
+        if _is_torch(w):
+            import torch
+            self._t_check(w, 4, "w")
+            n = w.numel() // 4
+            self._t_check(x, 4, "x")
+            l = (x.shape[1] if x.dim() == 3 else (x.numel() // 4 // n if n else 0)) if l is None else int(l)
+            if x.numel() != n * l * 4:
+                raise ValueError("x holds %d elements for %d rows of %d" % (x.numel() // 4, n, l))
+            out = torch.empty((l, 4), dtype=w.dtype, device=w.device)
+            sw = torch.empty(4, dtype=w.dtype, device=w.device)
+            self._chk(self._lib.zkp_fr_fold_batch_dev(self._h, self._tp(w), self._tp(x) if n * l else None, n, l, self._tp(out) if l else None,
+                                                      self._tp(sw), self._stream()))
+            return out, sw
+        w = _np(w, 4)
+        n = w.shape[0]
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        l = (x.shape[1] if x.ndim == 3 else (x.size // 4 // n if n else 0)) if l is None else int(l)
+        if x.size != n * l * 4:
+            raise ValueError("x holds %d elements for %d rows of %d" % (x.size // 4, n, l))
+        out, sw = np.empty((l, 4), dtype=np.uint64), np.empty(4, dtype=np.uint64)
+        self._chk(self._lib.zkp_fr_fold_batch(self._h, _ptr(w), _ptr(x) if n * l else None, n, l, _ptr(out) if l else None, _ptr(sw)))
+        return out, sw
+
+    def groth16_verify_batch(self, alpha_g1, beta_g2, gamma_g2, delta_g2, ic, a, b, c, inputs, *, inf_a=None, inf_b=None, inf_c=None, rand=None,
+                             points_checked=False, vk_checked=False):
+        """n Groth16 proofs against one verifying key as ONE check (zkp_groth16_verify_batch): key points alpha (12,), beta / gamma /
+        delta (24,), ic (n_inputs + 1, 12); proofs a (n, 12), b (n, 24), c (n, 12); inputs (n, n_inputs, 4) canonical Fr elements.  True
+        iff the random combination holds, every point is valid (unless points_checked / vk_checked), every input is below r and no
+        (a_c, b_c) is zero; a batch with an invalid proof passes with probability <= 2^-128.  rand (n, 2) uint64, by default fresh from
+        os.urandom (rlc_random) - never a seeded generator.  Host arrays return a bool; resident torch tensors (all of them) an int32
+        tensor (1,) without synchronising."""
+        cnt = lambda x, w: (x.numel() if _is_torch(x) else np.asarray(x).size) // w
+        n, l = cnt(a, 12), cnt(ic, 12) - 1
+        if l < 0:
+            raise ValueError("ic holds no point")
+        if n == 0:
+            return True
+        if rand is None:
+            rand = self.rlc_random(n)
+        flags = (_lib.GROTH16_POINTS_CHECKED if points_checked else 0) | (_lib.GROTH16_VK_CHECKED if vk_checked else 0)
+        vk_arrays = [("alpha_g1", alpha_g1, 12, 1), ("beta_g2", beta_g2, 24, 1), ("gamma_g2", gamma_g2, 24, 1), ("delta_g2", delta_g2, 24, 1),
+                     ("ic", ic, 12, l + 1)]
+        b_arrays = [("a", a, 12, n), ("inf_a", inf_a, None, n), ("b", b, 24, n), ("inf_b", inf_b, None, n), ("c", c, 12, n), ("inf_c", inf_c, None, n),
+                    ("inputs", inputs, 4, n * l)]
+        vk = _lib.Groth16Vk(n_inputs=l)
+        bt = _lib.Groth16Batch(n=n)
+        keep = []
+        if _is_torch(a):
+            import torch
+            dev = torch.device("cuda", self.device)
+            for rec, arrays in ((vk, vk_arrays), (bt, b_arrays)):
+                for name, x, w, rows in arrays:
+                    if x is None or not rows:
+                        continue
+                    if w is None:
+                        self._t_bytes(x, rows, name)
+                    else:
+                        self._t_check(x, w, name, rows=rows)
+                        if x.numel() != rows * w:
+                            raise ValueError("%s holds %d elements, %d expected" % (name, x.numel() // w, rows))
+                    setattr(rec, name, x.data_ptr())
+            if not _is_torch(rand):
+                rand = torch.from_numpy(np.ascontiguousarray(rand, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
+            self._t_check(rand, 2, "rand", rows=n)
+            all_ok = torch.empty(1, dtype=torch.int32, device=dev)
+            self._chk(self._lib.zkp_groth16_verify_batch_dev(self._h, ctypes.byref(vk), ctypes.byref(bt), self._tp(rand), flags, self._tp(all_ok),
+                                                             self._stream()))
+            return all_ok
+        for rec, arrays in ((vk, vk_arrays), (bt, b_arrays)):
+            for name, x, w, rows in arrays:
+                if x is None or not rows:
+                    continue
+                arr = _flags(x, rows, name) if w is None else _np(x, w)
+                if w is not None and arr.shape[0] != rows:
+                    raise ValueError("%s holds %d elements, %d expected" % (name, arr.shape[0], rows))
+                keep.append(arr)
+                setattr(rec, name, arr.ctypes.data)
+        r = _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d proofs" % (r.shape[0], n))
+        res = ctypes.c_int(0)
+        self._chk(self._lib.zkp_groth16_verify_batch(self._h, ctypes.byref(vk), ctypes.byref(bt), _ptr(r), flags, ctypes.byref(res)))
+        return bool(res.value)
+
     def msm_profile(self, which, points, scalars, n_msm=1, shared_bases=False):
         """measurement: one MSM on torch tensors with the milliseconds of its six phases (zkp_msm_profile_dev)"""
         import torch

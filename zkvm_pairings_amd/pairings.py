@@ -245,3 +245,176 @@ def msm(points, scalars, engine=None):
     sc = np.stack([synthetic.int_to_scalar(k) for k in scalars])
     out, oi = (e.g2_msm if g2 else e.g1_msm)(pts, sc, 1, inf)
     return cls.from_array(out[0], bool(oi[0]))
+
+
+class Fr:
+    """An element of the scalar field (reference src/fr.rs): a Python integer in [0, r).  Single elements are host integers - an
+    operator on one element is not worth a launch; batches go through the engine (Fr.batch: zkp_fr_op_batch, Fr.fold: zkp_fr_fold_batch,
+    Fr.from_bytes_wide: zkp_fr_from_wide_batch)."""
+    MODULUS = synthetic.R_ORDER
+
+    def __init__(self, v=0):
+        self.v = int(v.v if isinstance(v, Fr) else v) % Fr.MODULUS
+
+    @classmethod
+    def from_array(cls, a):
+        return cls(synthetic.scalar_to_int(np.asarray(a, dtype=np.uint64).reshape(4)))
+
+    def to_array(self):
+        return synthetic.int_to_scalar(self.v)
+
+    def __int__(self):
+        return self.v
+
+    def __eq__(self, o):
+        return self.v == Fr(o).v
+
+    def __hash__(self):
+        return hash(self.v)
+
+    def __repr__(self):
+        return "Fr(0x%064x)" % self.v
+
+    def __add__(self, o):
+        return Fr(self.v + Fr(o).v)
+
+    def __sub__(self, o):
+        return Fr(self.v - Fr(o).v)
+
+    def __mul__(self, o):
+        return Fr(self.v * Fr(o).v)
+
+    def __neg__(self):
+        return Fr(-self.v)
+
+    def square(self):
+        return Fr(self.v * self.v)
+
+    def invert(self):
+        """the inverse, or None for zero (src/fr.rs:266)"""
+        return Fr(pow(self.v, Fr.MODULUS - 2, Fr.MODULUS)) if self.v else None
+
+    @staticmethod
+    def _rows(elems):
+        elems = list(elems)
+        return np.stack([Fr(e).to_array() for e in elems]) if elems else np.zeros((0, 4), dtype=np.uint64)
+
+    @staticmethod
+    def batch(op, a, b=None, engine=None):
+        """[a_i op b_i] on the GPU; op: "mul", "add", "sub", "neg", "square", "invert" (0 inverts to 0)"""
+        out = (engine or default_engine()).fr_op(op, Fr._rows(a), None if b is None else Fr._rows(b))
+        return [Fr.from_array(r) for r in out]
+
+    @staticmethod
+    def fold(w, x, engine=None):
+        """([sum_c w_c x_c[i] for i], sum_c w_c) on the GPU; x: one row of l elements per weight"""
+        x = [list(row) for row in x]
+        l = len(x[0]) if x else 0
+        out, sw = (engine or default_engine()).fr_fold(Fr._rows(w), Fr._rows([e for row in x for e in row]), l)
+        return [Fr.from_array(r) for r in out], Fr.from_array(sw)
+
+    @staticmethod
+    def from_bytes_wide(data, engine=None):
+        """64 little-endian bytes -> the integer mod r (src/fr.rs:192-217), on the GPU"""
+        if len(data) != 64:
+            raise ValueError("from_bytes_wide takes 64 bytes")
+        return Fr.from_array((engine or default_engine()).fr_from_wide(bytes(data))[0])
+
+
+class Groth16VerifyingKey:
+    """alpha in G1, beta / gamma / delta in G2 and IC_0 .. IC_l in G1 (l public inputs), as wire arrays; every point is finite"""
+
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, ic):
+        arr = lambda p, w: (p.to_array() if hasattr(p, "to_array") else np.ascontiguousarray(p, dtype=np.uint64)).reshape(w)
+        self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2 = arr(alpha_g1, 12), arr(beta_g2, 24), arr(gamma_g2, 24), arr(delta_g2, 24)
+        ic = [arr(p, 12) for p in ic] if not isinstance(ic, np.ndarray) else ic
+        self.ic = np.ascontiguousarray(ic, dtype=np.uint64).reshape(-1, 12)
+        if self.ic.shape[0] < 1:
+            raise ValueError("a verifying key holds at least IC_0")
+
+    @property
+    def n_inputs(self):
+        return self.ic.shape[0] - 1
+
+    def arrays(self):
+        return self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2, self.ic
+
+
+def _g2_neg_array(q):
+    """-Q on a (24,) wire array, on the host like G2Affine.__neg__"""
+    q = G2Affine.from_array(q)
+    return (-q).to_array()
+
+
+def _groth16_proofs(proofs, e):
+    """(a, b, c, inf_a, inf_b, inf_c, decoded): proofs as three point arrays, or an (n, 192) uint8 array of compressed A | B | C
+    (48 + 96 + 48 bytes) decompressed on the GPU from contiguous column copies; decoded[c] = 0 where a point of proof c failed to
+    decompress"""
+    if isinstance(proofs, (tuple, list)) and len(proofs) == 3:
+        a, b, c = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, w) for x, w in zip(proofs, (12, 24, 12)))
+        if not (a.shape[0] == b.shape[0] == c.shape[0]):
+            raise ValueError("A, B and C differ in number of points")
+        return a, b, c, None, None, None, np.ones(a.shape[0], dtype=bool)
+    raw = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 192)
+    a, ia, sa = e.decompress_points(np.ascontiguousarray(raw[:, :48]), 1)
+    b, ib, sb = e.decompress_points(np.ascontiguousarray(raw[:, 48:144]), 2)
+    c, ic, sc = e.decompress_points(np.ascontiguousarray(raw[:, 144:]), 1)
+    return a, b, c, ia, ib, ic, (sa | sb | sc) == 0
+
+
+def _groth16_inputs(inputs, n, l):
+    x = np.ascontiguousarray(inputs, dtype=np.uint64) if inputs is not None and l else np.zeros((n, 0, 4), dtype=np.uint64)
+    if x.size != n * l * 4:
+        raise ValueError("inputs hold %d elements for %d proofs of %d" % (x.size // 4, n, l))
+    return x.reshape(n, l, 4)
+
+
+def groth16_verify_batch(vk, proofs, inputs, engine=None, rand=None, points_checked=False, vk_checked=False):
+    """True iff every one of the n proofs verifies against vk (zkp_groth16_verify_batch: one random combination, one final
+    exponentiation; a batch with an invalid proof passes with probability <= 2^-128).  proofs: (A, B, C) point arrays or an (n, 192)
+    uint8 array of compressed A | B | C - a proof that fails to decompress fails the batch; inputs (n, n_inputs, 4) uint64, each below
+    r.  groth16_verify_each finds the bad proof when this returns False."""
+    e = engine or default_engine()
+    a, b, c, ia, ib, ic, decoded = _groth16_proofs(proofs, e)
+    n = a.shape[0]
+    x = _groth16_inputs(inputs, n, vk.n_inputs)
+    if not decoded.all():
+        return False
+    return e.groth16_verify_batch(*vk.arrays(), a, b, c, x, inf_a=ia, inf_b=ib, inf_c=ic, rand=rand, points_checked=points_checked, vk_checked=vk_checked)
+
+
+def groth16_verify_each(vk, proofs, inputs, engine=None):
+    """bool array (n,): proof c verifies.  The per-proof path, composed only of calls that do not know Groth16: vk_x_c = IC_0 +
+    sum_i x_{c,i} IC_{i+1} through msm(shared_bases) with the scalar 1 for IC_0, then pairing_check with k = 4 on
+    (A_c, B_c), (alpha, -beta), (vk_x_c, -gamma), (C_c, -delta), ANDed with is_valid of every point and with every input < r."""
+    e = engine or default_engine()
+    a, b, c, ia, ib, ic, ok = _groth16_proofs(proofs, e)
+    n, l = a.shape[0], vk.n_inputs
+    x = _groth16_inputs(inputs, n, l)
+    ok = ok.copy()
+    if n == 0:
+        return ok
+    key_ok = not (e.g1_is_valid(vk.alpha_g1).any() or e.g1_is_valid(vk.ic).any() or
+                  e.g2_is_valid(np.stack([vk.beta_g2, vk.gamma_g2, vk.delta_g2])).any())
+    ok &= key_ok
+    ok &= (e.g1_is_valid(a, ia) == 0) & (e.g2_is_valid(b, ib) == 0) & (e.g1_is_valid(c, ic) == 0)
+    ok &= synthetic.below_r(x.reshape(-1, 4)).reshape(n, l).all(axis=1)
+    sc = np.zeros((n, l + 1, 4), dtype=np.uint64)
+    sc[:, 0, 0] = 1
+    sc[:, 1:] = x
+    vkx, vinf = np.empty((n, 12), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+    step = max(1, (1 << 24) // (l + 1))            # the MSM's limit on m * n_msm
+    for lo in range(0, n, step):
+        hi = min(n, lo + step)
+        vkx[lo:hi], vinf[lo:hi] = e.g1_msm(vk.ic, sc[lo:hi].reshape(-1, 4), hi - lo, shared_bases=True)
+    g1 = np.empty((n, 4, 12), dtype=np.uint64)
+    g2 = np.empty((n, 4, 24), dtype=np.uint64)
+    g1[:, 0], g1[:, 1], g1[:, 2], g1[:, 3] = a, vk.alpha_g1, vkx, c
+    g2[:, 0], g2[:, 1], g2[:, 2], g2[:, 3] = b, _g2_neg_array(vk.beta_g2), _g2_neg_array(vk.gamma_g2), _g2_neg_array(vk.delta_g2)
+    i1 = np.zeros((n, 4), dtype=np.uint8)
+    i2 = np.zeros((n, 4), dtype=np.uint8)
+    i1[:, 2] = vinf
+    if ia is not None:
+        i1[:, 0], i2[:, 0], i1[:, 3] = ia, ib, ic
+    per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 4, i1.reshape(-1), i2.reshape(-1))
+    return ok & (np.asarray(per).reshape(-1) != 0)

@@ -97,3 +97,51 @@ def random_pairs(engine, n, seed=SEED, offset=0, device_tensors=False):
     g1, _ = engine.g1_mul(G1_GENERATOR, a)
     g2, _ = engine.g2_mul(G2_GENERATOR, b)
     return g1, g2, a, b
+
+
+def below_r(w):
+    """(n,4) little-endian uint64 values: value < r (zero included), elementwise - the canonical Fr elements"""
+    w = np.asarray(w, dtype=np.uint64).reshape(-1, 4)
+    lt = np.zeros(w.shape[0], dtype=bool)
+    eq = np.ones(w.shape[0], dtype=bool)
+    for i in (3, 2, 1, 0):
+        lt |= eq & (w[:, i] < _R_LIMBS[i])
+        eq &= w[:, i] == _R_LIMBS[i]
+    return lt
+
+
+def _ints(w):
+    return [int.from_bytes(row.tobytes(), "little") for row in np.ascontiguousarray(w, dtype=np.uint64).reshape(-1, 4)]
+
+
+def _rows(vals):
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def groth16_instance(seed, n, n_inputs, bad=(), engine=None):
+    """A synthetic Groth16 verifying key, n proofs and their public inputs, built from secret exponents (Python integers mod r):
+        key    alpha = [a] G1, beta = [b] G2, gamma = [g] G2, delta = [d] G2, IC_i = [k_i] G1 (i <= n_inputs)
+        proof  A = [s] G1, B = [t] G2, C = [(s t - a b - g (k_0 + sum_i x_i k_{i+1})) / d] G1
+    so that e(A, B) = e(alpha, beta) e(vk_x, gamma) e(C, delta) holds by construction; the proofs listed in `bad` get C + G1 and fail.
+    The points come through the engine's g1_mul / g2_mul.  -> (key, proofs, inputs): key = (alpha (12,), beta (24,), gamma (24,),
+    delta (24,), ic (n_inputs + 1, 12)), proofs = (A (n,12), B (n,24), C (n,12)), inputs (n, n_inputs, 4) uint64."""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    r, l = R_ORDER, int(n_inputs)
+    a, b, g, d = _ints(scalars(seed ^ 0x616, 4))
+    k = _ints(scalars(seed ^ 0x1C, l + 1))
+    s, t = _ints(scalars(seed ^ 0x0A, n)), _ints(scalars(seed ^ 0x0B, n))
+    xw = scalars(seed ^ 0x0C, n * l).reshape(n, l, 4)
+    x = _ints(xw)
+    dinv = pow(d, r - 2, r)
+    bad = set(int(i) for i in bad)
+    cexp = []
+    for c in range(n):
+        vkx = (k[0] + sum(x[c * l + i] * k[i + 1] for i in range(l))) % r
+        cexp.append(((s[c] * t[c] - a * b - g * vkx) * dinv + (1 if c in bad else 0)) % r)
+    g1s, _ = engine.g1_mul(G1_GENERATOR, _rows([a] + k + s + cexp))
+    g2s, _ = engine.g2_mul(G2_GENERATOR, _rows([b, g, d] + t))
+    key = (g1s[0].copy(), g2s[0].copy(), g2s[1].copy(), g2s[2].copy(), g1s[1:l + 2].copy())
+    proofs = (g1s[l + 2:l + 2 + n].copy(), g2s[3:].copy(), g1s[l + 2 + n:].copy())
+    return key, proofs, xw
