@@ -23,6 +23,9 @@
  *   zkp_fr_from_wide_batch          Fr::from_bytes_wide / from_u512           src/fr.rs:192-217
  *   zkp_fr_fold_batch,              sum_c w_c x_{c,i} in Fr and the batched Groth16 verifier built on it (no upstream counterpart:
  *   zkp_groth16_verify_batch        Fr Mul / Add and pairing() composed)
+ *   zkp_fr_invert_batch             Fr::invert over a batch by Montgomery's trick (one power per CALL) src/fr.rs:266-362
+ *   zkp_fr_eval_batch,              a polynomial in evaluation form at a point (barycentric formula over the 2^k-th roots of unity,
+ *   zkp_kzg_verify_batch            FR_GENERATOR / FR_S of src/common.rs) and the batch KZG opening verifier (no upstream counterpart)
  *   zkp_tower_op_batch              Fp2 / Fp6 / Fp12 mul, square, mul_by_014, src/fp2.rs:171-209, src/fp6.rs:188-288,
  *                                   conjugate, frobenius_map (the TRUE map),  src/fp12.rs:99-210 (:143-170 is wrong)
  *                                   invert, mul_by_nonresidue, mul_by_1 / 01  src/fp2.rs:95-102,161-168,278-296, src/fp6.rs:102-141,291-309
@@ -301,6 +304,61 @@ int zkp_groth16_verify_batch(zkp_ctx* ctx, const zkp_groth16_vk* vk, const zkp_g
 /* device flavour: the key's and the batch's pointers, d_rand and d_all_ok are device pointers (the descriptors are host structs) */
 int zkp_groth16_verify_batch_dev(zkp_ctx* ctx, const zkp_groth16_vk* vk, const zkp_groth16_batch* b, const void* d_rand, int flags,
                                  void* d_all_ok, void* stream);
+
+/* ---- batched Fr inversion, barycentric evaluation and the batch KZG opening verifier (symbols added under ABI version 4) ----------------
+ * zkp_fr_invert_batch: out[i] = a[i]^-1 mod r, and 0 for 0: bit for bit what zkp_fr_op_batch(ZKP_FR_INVERT) gives, by Montgomery's trick
+ * (zkvm_pairings_amd/csrc/zkp_kzg.hip): a thread multiplies up a run of 4 consecutive elements, a workgroup its 256 run totals over LDS, one
+ * middle launch the workgroup totals, where the call's ONE power r - 2 is taken; a back-sweep gives the inverses.  out may be exactly a (in
+ * place); any other overlap is the caller's error.  n <= 2^31 - 1, else ZKP_ERR_ARG; n == 0 is legal.  Validation mode as zkp_fr_op_batch.
+ * Cost: at most 8 Montgomery products per element (7.25 in a full workgroup of 1024) and one power per call, against about 380 products per
+ * element for ZKP_FR_INVERT; no atomics; exact, so the result does not depend on the grid.  Workspace (grow-only, layout
+ * zkvm_pairings_amd/csrc/zkp_kzg_plan.hpp): 64 B per 1024 elements.  The _dev flavour is asynchronous and capturable into a hipGraph once that
+ * workspace has reached the call's size.
+ * zkp_fr_eval_batch: n_poly polynomials, each given by its N = 2^log2_n evaluations f_{j,i} over the domain {w^i}, w = 7^((r - 1) / N), at one
+ * point z_j each: out[j] = (z_j^N - 1) / N * sum_i f_{j,i} w^i / (z_j - w^i), and f_{j,i} where z_j = w^i (found on the device, from the zero
+ * denominator).  With ZKP_FR_EVAL_BITREV evaluation i belongs to w^bitrev(i) (log2_n bits reversed), the order blobs are stored in.
+ * log2_n <= 20, n_poly N <= 2^26, unknown flags: ZKP_ERR_ARG, refused before a byte is read; n_poly == 0 is legal.  Inputs are canonical
+ * (validation mode as above).  The domain table (32 B N, built on the device the first time a call needs that many points) and the workspace
+ * (32 B per evaluation for the denominators, which are inverted in place by the routine above, plus that routine's 64 B per 1024) are kept by
+ * the context.  The _dev flavour is asynchronous and capturable after a first call of that size.
+ * zkp_kzg_verify_batch: n openings (C_i, z_i, y_i, pi_i) - commitment, point, value, proof - against ONE setup (g1, g2, [tau]g2).  Opening i
+ * holds iff e(C_i - [y_i]g1 + [z_i]pi_i, g2) == e(pi_i, [tau]g2).  The call tests, with r_i = a_i + b_i z^2 from rand[2i], rand[2i + 1] exactly
+ * as zkp_pairing_check_batch_rlc forms them (draw them uniformly at random, per call, from a cryptographic source), t_i = r_i z_i mod r and
+ * u = sum_i r_i y_i mod r:
+ *     e(sum_i [r_i] C_i + sum_i [t_i] pi_i - [u] g1, -g2) * e(sum_i [r_i] pi_i, [tau]g2) == 1
+ * *all_ok = that test AND every point valid AND every z_i, y_i < r AND no (a_i, b_i) = (0, 0): 1 implies, with probability at least
+ * 1 - 2^-128, that every opening holds, and a batch of true openings always gives 1.  The setup points are finite; the inf_* arrays of the batch
+ * may be NULL; a flagged infinity is a valid point (the zero polynomial opens as C = infinity, y = 0, pi = infinity).  An invalid point, a z or y
+ * >= r and a zero (a, b) are RESULTS (*all_ok = 0), not errors, in either validation mode; coordinates >= p keep the library's rule
+ * (ZKP_ERR_NONCANONICAL / the validation word when validation is on).  Unless flags says otherwise every C_i and pi_i
+ * (ZKP_KZG_POINTS_CHECKED) and g1, g2, [tau]g2 (ZKP_KZG_VK_CHECKED) go through is_valid first.  n == 0 gives 1.  ZKP_ERR_ARG: null pointers
+ * with a non-zero count, n > 2^22, unknown flags.  Cost: 2 n Fr products and the fold of u, one shared-bases G1 MSM call of two sums over 2 n + 1 points
+ * (two calls at n = 2^22), one Miller product over two pairs, ONE final exponentiation; the sign is handled on the device (g2 is negated).  The _dev flavour is asynchronous
+ * (no read-back) and capturable into a hipGraph once the context's workspaces have reached the call's size; d_all_ok (one int32) is required.
+ * Workspace (grow-only, zkp_kzg_plan.hpp) per opening: 128 B of scalars, 194 B of copied points and flags, 2 B of status without
+ * ZKP_KZG_POINTS_CHECKED; plus the MSM workspace of 2 n + 1 terms and the Miller loop's own. */
+#define ZKP_FR_EVAL_BITREV 1           /* flags: evaluation i belongs to w^bitrev(i) */
+typedef struct {
+    const void *g1, *g2, *tau_g2;                           /* one finite point each */
+} zkp_kzg_vk;
+typedef struct {
+    size_t n;
+    const void *c, *inf_c, *proof, *inf_proof;              /* n G1, n G1 (+ optional infinity bytes) */
+    const void *z, *y;                                      /* n x 4 u64 each */
+} zkp_kzg_batch;
+#define ZKP_KZG_POINTS_CHECKED 1       /* flags: the commitments and proofs are known valid */
+#define ZKP_KZG_VK_CHECKED     2       /* flags: the setup points are known valid */
+int zkp_fr_invert_batch(zkp_ctx* ctx, const uint64_t* a, size_t n, uint64_t* out);
+int zkp_fr_invert_batch_dev(zkp_ctx* ctx, const void* d_a, size_t n, void* d_out, void* stream);
+int zkp_fr_eval_batch(zkp_ctx* ctx, const uint64_t* evals /* n_poly x N x 4 */, const uint64_t* z /* n_poly x 4 */, size_t n_poly, unsigned log2_n,
+                      int flags, uint64_t* out /* n_poly x 4 */);
+int zkp_fr_eval_batch_dev(zkp_ctx* ctx, const void* d_evals, const void* d_z, size_t n_poly, unsigned log2_n, int flags, void* d_out, void* stream);
+/* host flavour: the setup's and the batch's pointers are host arrays */
+int zkp_kzg_verify_batch(zkp_ctx* ctx, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const uint64_t* rand /* 2 u64 per opening */, int flags,
+                         int* all_ok);
+/* device flavour: the setup's and the batch's pointers, d_rand and d_all_ok are device pointers (the descriptors are host structs) */
+int zkp_kzg_verify_batch_dev(zkp_ctx* ctx, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const void* d_rand, int flags, void* d_all_ok,
+                             void* stream);
 
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).

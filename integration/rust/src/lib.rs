@@ -82,6 +82,31 @@ pub struct zkp_groth16_batch {
 /// flags of `zkp_groth16_verify_batch`: the proof points / the key points are known valid
 pub const ZKP_GROTH16_POINTS_CHECKED: c_int = 1;
 pub const ZKP_GROTH16_VK_CHECKED: c_int = 2;
+/// the setup of `zkp_kzg_verify_batch[_dev]` (include/zkp_pairings.h `zkp_kzg_vk`, same field order): one finite point each
+#[repr(C)]
+#[allow(non_camel_case_types)]
+pub struct zkp_kzg_vk {
+    pub g1: *const c_void,
+    pub g2: *const c_void,
+    pub tau_g2: *const c_void,
+}
+/// n openings: commitments and proofs (G1, optional infinity bytes), points z and values y (n x 4 u64 each), `zkp_kzg_batch`
+#[repr(C)]
+#[allow(non_camel_case_types)]
+pub struct zkp_kzg_batch {
+    pub n: usize,
+    pub c: *const c_void,
+    pub inf_c: *const c_void,
+    pub proof: *const c_void,
+    pub inf_proof: *const c_void,
+    pub z: *const c_void,
+    pub y: *const c_void,
+}
+/// flags of `zkp_kzg_verify_batch`: the commitments and proofs / the setup points are known valid
+pub const ZKP_KZG_POINTS_CHECKED: c_int = 1;
+pub const ZKP_KZG_VK_CHECKED: c_int = 2;
+/// flags of `zkp_fr_eval_batch`: evaluation i belongs to w^bitrev(i)
+pub const ZKP_FR_EVAL_BITREV: c_int = 1;
 /// zkp_fr_op (Fr elements: 4 u64, canonical)
 pub const ZKP_FR_MUL: c_int = 0;
 pub const ZKP_FR_ADD: c_int = 1;
@@ -230,6 +255,16 @@ extern "C" {
                                     all_ok: *mut c_int) -> c_int;
     pub fn zkp_groth16_verify_batch_dev(ctx: *mut ZkpCtx, vk: *const zkp_groth16_vk, b: *const zkp_groth16_batch, d_rand: *const c_void,
                                         flags: c_int, d_all_ok: *mut c_void, stream: *mut c_void) -> c_int;
+    // batched Fr inversion, barycentric evaluation and the batch KZG opening verifier (added under ABI version 4)
+    pub fn zkp_fr_invert_batch(ctx: *mut ZkpCtx, a: *const u64, n: usize, out: *mut u64) -> c_int;
+    pub fn zkp_fr_invert_batch_dev(ctx: *mut ZkpCtx, d_a: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_fr_eval_batch(ctx: *mut ZkpCtx, evals: *const u64, z: *const u64, n_poly: usize, log2_n: c_uint, flags: c_int, out: *mut u64) -> c_int;
+    pub fn zkp_fr_eval_batch_dev(ctx: *mut ZkpCtx, d_evals: *const c_void, d_z: *const c_void, n_poly: usize, log2_n: c_uint, flags: c_int,
+                                 d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn zkp_kzg_verify_batch(ctx: *mut ZkpCtx, vk: *const zkp_kzg_vk, b: *const zkp_kzg_batch, rand: *const u64, flags: c_int,
+                                all_ok: *mut c_int) -> c_int;
+    pub fn zkp_kzg_verify_batch_dev(ctx: *mut ZkpCtx, vk: *const zkp_kzg_vk, b: *const zkp_kzg_batch, d_rand: *const c_void, flags: c_int,
+                                    d_all_ok: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn zkp_g1_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g1: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g2_decompress_batch(ctx: *mut ZkpCtx, bytes: *const u8, n: usize, out_g2: *mut u64, out_inf: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_g1_compress_batch(ctx: *mut ZkpCtx, g1: *const u64, inf: *const u8, n: usize, out_bytes: *mut u8) -> c_int;

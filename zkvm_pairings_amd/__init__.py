@@ -8,9 +8,11 @@ from ._lib import ZkpError
 _lib.load()
 
 from .engine import KERNEL_AUTO, KERNEL_COOP, KERNEL_THREAD, PairingEngine  # noqa: E402
-from .pairings import (Fr, G1Affine, G2Affine, Groth16VerifyingKey, Gt, MillerLoopResult, final_exponentiation,  # noqa: E402
-                       groth16_verify_batch, groth16_verify_each, msm, multi_miller_loop, pairing)
+from .pairings import (Fr, G1Affine, G2Affine, Groth16VerifyingKey, Gt, KzgSetup, MillerLoopResult, final_exponentiation,  # noqa: E402
+                       groth16_verify_batch, groth16_verify_each, kzg_verify_batch, kzg_verify_blob_batch, kzg_verify_each, msm,
+                       multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
 __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "pairing", "multi_miller_loop", "msm",
-           "final_exponentiation", "Fr", "Groth16VerifyingKey", "groth16_verify_batch", "groth16_verify_each", "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]
+           "final_exponentiation", "Fr", "Groth16VerifyingKey", "groth16_verify_batch", "groth16_verify_each", "KzgSetup", "kzg_verify_batch", "kzg_verify_each",
+           "kzg_verify_blob_batch", "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

@@ -40,6 +40,21 @@ class Groth16Batch(ctypes.Structure):
     _fields_ = [("n", c_sz), ("a", c_vp), ("inf_a", c_vp), ("b", c_vp), ("inf_b", c_vp), ("c", c_vp), ("inf_c", c_vp), ("inputs", c_vp)]
 
 
+FR_EVAL_BITREV = 1           # ZKP_FR_EVAL_BITREV
+KZG_POINTS_CHECKED = 1       # ZKP_KZG_POINTS_CHECKED
+KZG_VK_CHECKED = 2           # ZKP_KZG_VK_CHECKED
+
+
+class KzgVk(ctypes.Structure):
+    """zkp_kzg_vk: the setup points of zkp_kzg_verify_batch[_dev] (field order of include/zkp_pairings.h)"""
+    _fields_ = [("g1", c_vp), ("g2", c_vp), ("tau_g2", c_vp)]
+
+
+class KzgBatch(ctypes.Structure):
+    """zkp_kzg_batch: n openings (commitment, proof, point, value)"""
+    _fields_ = [("n", c_sz), ("c", c_vp), ("inf_c", c_vp), ("proof", c_vp), ("inf_proof", c_vp), ("z", c_vp), ("y", c_vp)]
+
+
 # name -> (restype, argtypes); MUST list every symbol include/zkp_pairings.h declares
 SIGNATURES = {
     "zkp_abi_version": (c_int, []),
@@ -109,6 +124,12 @@ SIGNATURES = {
     "zkp_fr_fold_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp]),
     "zkp_groth16_verify_batch": (c_int, [c_vp, ctypes.POINTER(Groth16Vk), ctypes.POINTER(Groth16Batch), c_vp, c_int, ctypes.POINTER(c_int)]),
     "zkp_groth16_verify_batch_dev": (c_int, [c_vp, ctypes.POINTER(Groth16Vk), ctypes.POINTER(Groth16Batch), c_vp, c_int, c_vp, c_vp]),
+    "zkp_fr_invert_batch": (c_int, [c_vp, c_vp, c_sz, c_vp]),
+    "zkp_fr_invert_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_fr_eval_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp]),
+    "zkp_fr_eval_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp]),
+    "zkp_kzg_verify_batch": (c_int, [c_vp, ctypes.POINTER(KzgVk), ctypes.POINTER(KzgBatch), c_vp, c_int, ctypes.POINTER(c_int)]),
+    "zkp_kzg_verify_batch_dev": (c_int, [c_vp, ctypes.POINTER(KzgVk), ctypes.POINTER(KzgBatch), c_vp, c_int, c_vp, c_vp]),
     "zkp_g1_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g2_decompress_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "zkp_g1_compress_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -1,7 +1,8 @@
 // zkp_fr.hpp -- the BLS12-381 scalar field Fr (r = the order of G1 / G2 / Gt, 255 bits) on 8 x 32-bit Montgomery limbs (R = 2^256), and
 // the exact wide accumulator of the fold sum_c w_c x_c.  Every function is __host__ __device__ and free of HIP types: zkp_groth16.hip
-// compiles this text for gfx950 (v_mad_u64_u32 does the 32 x 32 + 64 steps), tests/test_fr_cpu.py compiles the same text with g++ and
-// compares it with Python integers.
+// and zkp_kzg.hip compile this text for gfx950 (v_mad_u64_u32 does the 32 x 32 + 64 steps), tests/test_fr_cpu.py and
+// tests/test_kzg_cpu.py compile the same text with g++ and compare it with Python integers.  Further down: powers, the roots of unity
+// (DERIVED like the other constants) and the per-thread pieces of the batched inversion.
 //
 // What each function stands in for in the reference (paths relative to /root/reference):
 //   add :402-411, sub :384-398, neg :415-431, mul :365-381 (a BigUint product and remainder there, a Montgomery product here),
@@ -25,6 +26,11 @@
 #define ZKP_FR_INL inline
 #define ZKP_FR_UNROLL
 #define ZKP_FR_NOUNROLL
+#endif
+
+// a host test may count the Montgomery products a routine performs: it defines this before the include
+#ifndef ZKP_FR_COUNT_MUL
+#define ZKP_FR_COUNT_MUL (void)0
 #endif
 
 namespace zkp {
@@ -169,6 +175,7 @@ ZKP_FR_INL void neg(uint32_t* out, const uint32_t* a) {
 // 32-bit words; out may alias a or b.
 ZKP_FR_INL void mont_mul(uint32_t* out, const uint32_t* a, const uint32_t* b) {
     constexpr Consts K = make_consts();
+    ZKP_FR_COUNT_MUL;
     uint32_t A[NW], B[NW], t[NW + 2];
 ZKP_FR_UNROLL
     for (int i = 0; i < NW; i++) { A[i] = a[i]; B[i] = b[i]; t[i] = 0; }
@@ -284,6 +291,185 @@ ZKP_FR_UNROLL
     mont_mul(b, t, K.r4);
     add(a, a, b);
     from_mont(out, a);
+}
+
+
+// ---- powers ------------------------------------------------------------------------------------------------------------------------
+// out = a^e in Montgomery form (a and out in Montgomery form, e a plain 256-bit integer, low word first; e = 0 gives one).  Left to
+// right, one bit per turn; the exponent is shifted through its eight words, so nothing is indexed by a variable.  out may alias a.
+ZKP_FR_INL void mont_pow(uint32_t* out, const uint32_t* a, const uint32_t* e) {
+    constexpr Consts K = make_consts();
+    uint32_t base[NW], res[NW], ee[NW];
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) { base[i] = a[i]; res[i] = K.one[i]; ee[i] = e[i]; }
+ZKP_FR_NOUNROLL
+    for (int b = 0; b < 32 * NW; b++) {
+        mont_mul(res, res, res);
+        if (ee[NW - 1] >> 31) mont_mul(res, res, base);
+ZKP_FR_UNROLL
+        for (int w = NW - 1; w > 0; w--) ee[w] = (ee[w] << 1) | (ee[w - 1] >> 31);
+        ee[0] <<= 1;
+    }
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) out[i] = res[i];
+}
+// canonical in, canonical out
+ZKP_FR_INL void pow(uint32_t* out, const uint32_t* a, const uint32_t* e) {
+    uint32_t t[NW];
+    to_mont(t, a);
+    mont_pow(t, t, e);
+    from_mont(out, t);
+}
+// the inverse under the Montgomery product: mont_mul(a, mont_inv(a)) = one for a != 0 mod r, and 0 for 0.  One power r - 2.
+ZKP_FR_INL void mont_inv(uint32_t* out, const uint32_t* a) {
+    constexpr Consts K = make_consts();
+    mont_pow(out, a, K.rm2);
+}
+
+// ---- the roots of unity ------------------------------------------------------------------------------------------------------------
+// r - 1 = 2^32 * odd: omega[32] = 7^((r - 1) / 2^32) generates the 2^32-point domain (the reference's FR_GENERATOR = 7, FR_S = 32,
+// src/common.rs), omega[k] = omega[k + 1]^2 the 2^k-point one.  DERIVED like Consts, with a compile-time Montgomery product.
+struct Roots {
+    uint32_t omega[33][NW];      // Montgomery form
+    uint32_t inv_pow2[33][NW];   // 2^-k mod r, Montgomery form
+    uint32_t rinv[NW];           // R^-1 mod r as a plain integer: mont_mul(x, rinv) = x / R^2
+};
+ZKP_FR_HD constexpr void k_mont_mul(uint32_t* out, const uint32_t* a, const uint32_t* b, const Consts& k) {
+    uint32_t A[NW] = {}, B[NW] = {}, t[NW + 2] = {};
+    for (int i = 0; i < NW; i++) { A[i] = a[i]; B[i] = b[i]; }
+    for (int i = 0; i < NW; i++) {
+        uint64_t c = 0;
+        for (int j = 0; j < NW; j++) {
+            c += (uint64_t)A[j] * B[i] + t[j];
+            t[j] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[NW];
+        t[NW] = (uint32_t)c;
+        t[NW + 1] = (uint32_t)(c >> 32);
+        const uint32_t m = t[0] * k.inv;
+        c = (uint64_t)m * k.r[0] + t[0];
+        c >>= 32;
+        for (int j = 1; j < NW; j++) {
+            c += (uint64_t)m * k.r[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[NW];
+        t[NW - 1] = (uint32_t)c;
+        t[NW] = t[NW + 1] + (uint32_t)(c >> 32);
+    }
+    bool ge = t[NW] != 0;   // t >= r ?
+    if (!ge) {
+        ge = true;
+        for (int i = NW - 1; i >= 0; i--)
+            if (t[i] != k.r[i]) { ge = t[i] > k.r[i]; break; }
+    }
+    int64_t bw = 0;
+    for (int i = 0; i < NW; i++) {
+        bw += (int64_t)t[i] - (ge ? k.r[i] : 0u);
+        out[i] = (uint32_t)bw;
+        bw >>= 32;
+    }
+}
+ZKP_FR_HD constexpr Roots make_roots() {
+    const Consts k = make_consts();
+    Roots w{};
+    uint32_t g[NW] = {7, 0, 0, 0, 0, 0, 0, 0}, acc[NW] = {};
+    k_mont_mul(g, g, k.r2, k);
+    for (int i = 0; i < NW; i++) acc[i] = k.one[i];
+    for (int wi = NW - 1; wi >= 1; wi--)          // (r - 1) >> 32 is words 1 .. 7 of r (its word 0 is 1)
+        for (int b = 31; b >= 0; b--) {
+            k_mont_mul(acc, acc, acc, k);
+            if ((k.r[wi] >> b) & 1) k_mont_mul(acc, acc, g, k);
+        }
+    for (int lg = 32; lg >= 0; lg--) {
+        for (int i = 0; i < NW; i++) w.omega[lg][i] = acc[i];
+        k_mont_mul(acc, acc, acc, k);
+    }
+    for (int i = 0; i < NW; i++) acc[i] = k.one[i];
+    for (int lg = 0; lg <= 32; lg++) {
+        for (int i = 0; i < NW; i++) w.inv_pow2[lg][i] = acc[i];
+        uint64_t c = 0;                            // acc <- acc / 2: (acc + r) / 2 for an odd acc (below 2^256: r < 2^255)
+        const bool odd = acc[0] & 1;
+        for (int i = 0; i < NW; i++) {
+            c += (uint64_t)acc[i] + (odd ? k.r[i] : 0u);
+            acc[i] = (uint32_t)c;
+            c >>= 32;
+        }
+        for (int i = 0; i < NW; i++) acc[i] = (acc[i] >> 1) | (i + 1 < NW ? acc[i + 1] << 31 : 0u);
+    }
+    const uint32_t one[NW] = {1, 0, 0, 0, 0, 0, 0, 0};
+    k_mont_mul(w.rinv, one, one, k);
+    return w;
+}
+
+// ---- the batched inversion's per-thread pieces (Montgomery's trick; zkp_kzg.hip runs them on the device, tests/test_kzg_cpu.py on the
+// host).  Canonical elements are taken AS Montgomery forms (of a / R): under mont_mul they form a group with identity `one`, and the
+// inverse in it, mont_inv(a) = R^2 / a, is the canonical 1 / a after one product with rinv - which is applied once, to the inverse of
+// the call's grand total, and reaches every element because the back-sweep is linear in it.
+constexpr int INV_RUN = 4;        // consecutive elements of a thread
+constexpr int INV_TPB = 256;      // threads of a workgroup
+constexpr int INV_BLOCK = INV_RUN * INV_TPB;
+// A thread's run: elements x0 .. x3 and their prefix products p1 .. p3 (p0 is x0), named one by one - nothing here is indexed by a loop
+// variable, so every word stays in a register.  The back-sweep leaves the inverses in x0, p1, p2, p3.
+struct InvRun {
+    uint32_t x0[NW], x1[NW], x2[NW], x3[NW], p1[NW], p2[NW], p3[NW];
+};
+static_assert(INV_RUN == 4, "InvRun names the elements of a run");
+// element j joins the run: a zero is replaced by one and noted in the mask; tot <- tot x, pj <- tot (j > 0).  One product unless j == 0.
+ZKP_FR_INL void inv_fwd_step(uint32_t* xj, uint32_t* pj, uint32_t* tot, uint32_t* zero_mask, int j) {
+    constexpr Consts K = make_consts();
+    uint32_t nz = 0;
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) nz |= xj[i];
+    if (!nz) *zero_mask |= 1u << j;
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) xj[i] = nz ? xj[i] : K.one[i];
+    if (j == 0) {
+ZKP_FR_UNROLL
+        for (int i = 0; i < NW; i++) tot[i] = xj[i];
+    } else {
+        mont_mul(tot, tot, xj);
+ZKP_FR_UNROLL
+        for (int i = 0; i < NW; i++) pj[i] = tot[i];
+    }
+}
+// the run's m <= INV_RUN elements (canonical): p_j = x_0 ... x_j, tot = p_{m-1}, one for an empty run.  m - 1 products.
+ZKP_FR_INL void inv_run_prefix(InvRun& r, uint32_t* tot, uint32_t* zero_mask, int m) {
+    constexpr Consts K = make_consts();
+    *zero_mask = 0;
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) tot[i] = K.one[i];
+    if (m > 0) inv_fwd_step(r.x0, nullptr, tot, zero_mask, 0);
+    if (m > 1) inv_fwd_step(r.x1, r.p1, tot, zero_mask, 1);
+    if (m > 2) inv_fwd_step(r.x2, r.p2, tot, zero_mask, 2);
+    if (m > 3) inv_fwd_step(r.x3, r.p3, tot, zero_mask, 3);
+}
+// u = the (scaled) inverse of p_j: pj <- u p_{j-1} = the inverse of x_j (0 where the mask says so), u <- u x_j = the inverse of p_{j-1}.
+// Two products; for j == 0 (pprev null) pj <- u and none.  pj may be pprev's successor only: p_j itself is no longer needed by then.
+ZKP_FR_INL void inv_back_step(const uint32_t* xj, const uint32_t* pprev, uint32_t* pj, uint32_t* u, uint32_t zero_mask, int j) {
+    uint32_t o[NW];
+    if (pprev) {
+        mont_mul(o, u, pprev);
+        mont_mul(u, u, xj);
+    } else {
+ZKP_FR_UNROLL
+        for (int i = 0; i < NW; i++) o[i] = u[i];
+    }
+    const bool z = (zero_mask >> j) & 1;
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) pj[i] = z ? 0u : o[i];
+}
+// u = the (scaled) inverse of the run's total: x0, p1, p2, p3 <- the inverses of x0 .. x3.  2 (m - 1) products.
+ZKP_FR_INL void inv_run_back(InvRun& r, const uint32_t* u_in, uint32_t zero_mask, int m) {
+    uint32_t u[NW];
+ZKP_FR_UNROLL
+    for (int i = 0; i < NW; i++) u[i] = u_in[i];
+    if (m > 3) inv_back_step(r.x3, r.p2, r.p3, u, zero_mask, 3);
+    if (m > 2) inv_back_step(r.x2, r.p1, r.p2, u, zero_mask, 2);
+    if (m > 1) inv_back_step(r.x1, r.x0, r.p1, u, zero_mask, 1);
+    if (m > 0) inv_back_step(r.x0, nullptr, r.x0, u, zero_mask, 0);
 }
 
 }  // namespace fr

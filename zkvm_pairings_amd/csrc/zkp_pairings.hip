@@ -24,6 +24,8 @@
 #include "zkp_rlc_plan.hpp"
 #include "zkp_groth16.hpp"
 #include "zkp_groth16_plan.hpp"
+#include "zkp_kzg.hpp"
+#include "zkp_kzg_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -458,6 +460,10 @@ struct zkp_ctx {
     size_t rlc_cap = 0;
     void* g16_ws = nullptr;     // grow-only workspace of the Fr fold and the Groth16 verifier (zkp_groth16_plan.hpp layout)
     size_t g16_cap = 0;
+    void* kzg_ws = nullptr;     // grow-only workspace of the batched inversion, the evaluation and the KZG verifier (zkp_kzg_plan.hpp layouts)
+    size_t kzg_cap = 0;
+    uint32_t* kzg_dom = nullptr;   // omega^i for i < 2^kzg_dom_log2, Montgomery form: the evaluation's domain table (-1: none yet)
+    int kzg_dom_log2 = -1;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -880,6 +886,8 @@ void zkp_free(zkp_ctx* c) {
     if (c->msm_ws) (void)hipFree(c->msm_ws);
     if (c->rlc_ws) (void)hipFree(c->rlc_ws);
     if (c->g16_ws) (void)hipFree(c->g16_ws);
+    if (c->kzg_ws) (void)hipFree(c->kzg_ws);
+    if (c->kzg_dom) (void)hipFree(c->kzg_dom);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1550,9 +1558,34 @@ int grow_g16(zkp_ctx* c, size_t bytes, void** ws) {
     *ws = c->g16_ws;
     return ZKP_OK;
 }
+int grow_kzg(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->kzg_cap) {
+        if (c->kzg_ws) { HIPCHK(c, hipFree(c->kzg_ws)); c->kzg_ws = nullptr; c->kzg_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->kzg_ws, bytes));
+        zkp_dbg_alloc("ctx.kzg", c->kzg_ws, bytes);
+        c->kzg_cap = bytes;
+    }
+    *ws = c->kzg_ws;
+    return ZKP_OK;
+}
+int kzg_domain(zkp_ctx* c, unsigned log2_n, const uint32_t** table, unsigned* table_log2, hipStream_t s) {
+    if ((int)log2_n > c->kzg_dom_log2) {
+        if (c->kzg_dom) { HIPCHK(c, hipFree(c->kzg_dom)); c->kzg_dom = nullptr; c->kzg_dom_log2 = -1; }
+        HIPCHK(c, hipMalloc((void**)&c->kzg_dom, zkp::kzg::domain_bytes(log2_n)));
+        zkp_dbg_alloc("ctx.kzg_dom", c->kzg_dom, zkp::kzg::domain_bytes(log2_n));
+        HIPCHK(c, zkp::fr_domain_build(c->kzg_dom, log2_n, s));
+        c->kzg_dom_log2 = (int)log2_n;
+    }
+    *table = c->kzg_dom;
+    *table_log2 = (unsigned)c->kzg_dom_log2;
+    return ZKP_OK;
+}
 int grow_msm(zkp_ctx* c, size_t bytes) { return msm_grow(c, bytes); }
 int msm(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, void* out, void* out_inf, hipStream_t s) {
     return msm_dev(c, which, pts, inf, sc, m, n_msm, 0, out, out_inf, s, nullptr);
+}
+int msm_shared(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, void* out, void* out_inf, hipStream_t s) {
+    return msm_dev(c, which, pts, inf, sc, m, n_msm, 1, out, out_inf, s, nullptr);
 }
 int valid(zkp_ctx* c, int which, const void* pts, const void* inf, size_t n, void* status, hipStream_t s) { return valid_dev(c, which, pts, inf, n, status, s); }
 int miller_product(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_t* i1, const uint8_t* i2, size_t n, uint64_t* out, hipStream_t s) {
@@ -2245,6 +2278,115 @@ int zkp_groth16_verify_batch(zkp_ctx* c, const zkp_groth16_vk* vk, const zkp_gro
     int rc;
     if ((rc = io.status()) || (rc = g16_validate(&dv, &d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
         (rc = zkp::groth16_check_dev(c, &dv, &d, (const uint64_t*)drand, flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- batched Fr inversion, barycentric evaluation, the KZG verifier (zkp_kzg.hip)
+namespace {
+int fr_invert_dev(zkp_ctx* c, const void* a, size_t n, void* out, hipStream_t s) {
+    void* ws = nullptr;
+    if (int rc = zkp::ctxop::grow_kzg(c, zkp::kzg::inv_plan(n).total, &ws)) return rc;
+    return coop_rc(c, "fr_invert", zkp::fr_invert(ws, (const uint64_t*)a, n, (uint64_t*)out, s));
+}
+int fr_eval_dev(zkp_ctx* c, const void* evals, const void* z, size_t n_poly, unsigned log2_n, int flags, void* out, hipStream_t s) {
+    void* ws = nullptr;
+    const uint32_t* table = nullptr;
+    unsigned table_log2 = 0;
+    int rc;
+    if ((rc = zkp::ctxop::grow_kzg(c, zkp::kzg::eval_layout(n_poly, log2_n).total, &ws)) || (rc = zkp::ctxop::kzg_domain(c, log2_n, &table, &table_log2, s)))
+        return rc;
+    return coop_rc(c, "fr_eval", zkp::fr_eval(ws, table, table_log2, (const uint64_t*)evals, (const uint64_t*)z, n_poly, log2_n, flags, (uint64_t*)out, s));
+}
+bool fr_eval_args_bad(const zkp_ctx* c, const void* evals, const void* z, size_t n_poly, unsigned log2_n, int flags, const void* out) {
+    return !c || zkp::kzg::eval_args_bad(n_poly, log2_n, flags) || (n_poly && (!evals || !z || !out));
+}
+bool kzg_args_bad(const zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const void* rand, int flags, const void* all_ok) {
+    if (!c || !vk || !b || !all_ok || zkp::kzg::args_bad(b->n, flags)) return true;
+    if (!b->n) return false;
+    return !rand || !vk->g1 || !vk->g2 || !vk->tau_g2 || !b->c || !b->proof || !b->z || !b->y;
+}
+// validation mode: v(pointer, Fp count) over every coordinate array of the setup and the batch
+template <class V>
+int kzg_validate(const zkp_kzg_vk* vk, const zkp_kzg_batch* b, V&& v) {
+    int rc;
+    if ((rc = v(b->c, b->n * 2)) || (rc = v(b->proof, b->n * 2)) || (rc = v(vk->g1, 2)) || (rc = v(vk->g2, 4)) || (rc = v(vk->tau_g2, 4))) return rc;
+    return ZKP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_fr_invert_batch_dev(zkp_ctx* c, const void* a, size_t n, void* out, void* stream) {
+    if (!c || zkp::kzg::inv_args_bad(n) || (n && (!a || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    if (int rc = validate_fr_on_stream(c, a, n, S(stream))) return rc;
+    return fr_invert_dev(c, a, n, out, S(stream));
+}
+int zkp_fr_invert_batch(zkp_ctx* c, const uint64_t* a, size_t n, uint64_t* out) {
+    if (!c || zkp::kzg::inv_args_bad(n) || (n && (!a || !out))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    void* d = io.slot(0, n * 32);     // inverted in place on the device
+    io.put(d, a, n * 32);
+    io.get(out, d, n * 32);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, d, n)) || (rc = fr_invert_dev(c, d, n, d, c->stream))) return rc;
+    return io.finish();
+}
+int zkp_fr_eval_batch_dev(zkp_ctx* c, const void* evals, const void* z, size_t n_poly, unsigned log2_n, int flags, void* out, void* stream) {
+    if (fr_eval_args_bad(c, evals, z, n_poly, log2_n, flags, out)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_poly) return ZKP_OK;
+    int rc;
+    if ((rc = validate_fr_on_stream(c, evals, n_poly << log2_n, S(stream))) || (rc = validate_fr_on_stream(c, z, n_poly, S(stream)))) return rc;
+    return fr_eval_dev(c, evals, z, n_poly, log2_n, flags, out, S(stream));
+}
+int zkp_fr_eval_batch(zkp_ctx* c, const uint64_t* evals, const uint64_t* z, size_t n_poly, unsigned log2_n, int flags, uint64_t* out) {
+    if (fr_eval_args_bad(c, evals, z, n_poly, log2_n, flags, out)) return ZKP_ERR_ARG;
+    if (!n_poly) return ZKP_OK;
+    HostIO io(c);
+    const void* de = io.in(0, evals, (n_poly << log2_n) * 32);
+    const void* dz = io.in(1, z, n_poly * 32);
+    void* dout = io.out(4, out, n_poly * 32);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, de, n_poly << log2_n)) || (rc = validate_fr_dev(c, dz, n_poly)) ||
+        (rc = fr_eval_dev(c, de, dz, n_poly, log2_n, flags, dout, c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_kzg_verify_batch_dev(zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const void* rand, int flags, void* all_ok, void* stream) {
+    if (kzg_args_bad(c, vk, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (b->n)
+        if (int rc = kzg_validate(vk, b, [&](const void* d, size_t n_fp) { return validate_on_stream(c, d, n_fp, S(stream)); })) return rc;
+    return zkp::kzg_check_dev(c, vk, b, (const uint64_t*)rand, flags, (int*)all_ok, S(stream));
+}
+// the setup's and the batch's ten arrays one after the other in slot 0 (256-byte aligned), then the same driver as the _dev flavour
+int zkp_kzg_verify_batch(zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const uint64_t* rand, int flags, int* all_ok) {
+    if (kzg_args_bad(c, vk, b, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    if (!b->n) { *all_ok = 1; return ZKP_OK; }
+    const size_t n = b->n;
+    zkp_kzg_vk dv = *vk;
+    zkp_kzg_batch d = *b;
+    const void* drand = rand;
+    const void** field[10] = {&d.c, &d.inf_c, &d.proof, &d.inf_proof, &d.z, &d.y, &dv.g1, &dv.g2, &dv.tau_g2, &drand};
+    const size_t bytes[10] = {n * 96, n, n * 96, n, n * 32, n * 32, 96, 192, 192, n * 16};
+    size_t off[10], total = 0;
+    for (int i = 0; i < 10; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    char* dev = (char*)io.slot(0, total);
+    for (int i = 0; i < 10; i++) *field[i] = io.put(dev + off[i], *field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = kzg_validate(&dv, &d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
+        (rc = zkp::kzg_check_dev(c, &dv, &d, (const uint64_t*)drand, flags, c->d_flag + 1, c->stream)))
         return rc;
     return io.finish();
 }

@@ -604,6 +604,102 @@ class PairingEngine:
         self._chk(self._lib.zkp_groth16_verify_batch(self._h, ctypes.byref(vk), ctypes.byref(bt), _ptr(r), flags, ctypes.byref(res)))
         return bool(res.value)
 
+    def fr_invert(self, a, out=None):
+        """out[i] = a[i]^-1 in Fr, 0 for 0 (zkp_fr_invert_batch: Montgomery's trick, one power per call; the same bits as
+        fr_op("invert")).  numpy (n, 4) uint64 in, the same out; resident torch tensors stay on the GPU (the current stream), and
+        out=a inverts in place."""
+        if _is_torch(a):
+            import torch
+            self._t_check(a, 4, "a")
+            n = a.numel() // 4
+            if out is None:
+                out = torch.empty((n, 4), dtype=a.dtype, device=a.device)
+            else:
+                self._t_check(out, 4, "out", rows=n)
+            self._chk(self._lib.zkp_fr_invert_batch_dev(self._h, self._tp(a), n, self._tp(out), self._stream()))
+            return out
+        a = _np(a, 4)
+        res = np.empty_like(a)
+        self._chk(self._lib.zkp_fr_invert_batch(self._h, _ptr(a), a.shape[0], _ptr(res)))
+        return res
+
+    def fr_eval(self, evals, z, log2_n, bitrev=False):
+        """(n_poly, 4): polynomial j, given by its N = 2^log2_n evaluations evals[j] over the N-th roots of unity w^i (in bit-reversed
+        order with bitrev, as blobs are stored), at the point z[j] (zkp_fr_eval_batch: the barycentric formula; z[j] = w^i gives
+        evals[j][i]).  evals (n_poly, N, 4) or (n_poly N, 4), z (n_poly, 4), canonical.  Resident torch tensors stay on the GPU."""
+        log2_n, flags = int(log2_n), _lib.FR_EVAL_BITREV if bitrev else 0
+        if _is_torch(evals):
+            import torch
+            self._t_check(z, 4, "z")
+            n_poly = z.numel() // 4
+            self._t_check(evals, 4, "evals")
+            if log2_n < 0 or evals.numel() != (n_poly << log2_n) * 4:
+                raise ValueError("evals hold %d elements for %d polynomials of 2^%d" % (evals.numel() // 4, n_poly, log2_n))
+            out = torch.empty((n_poly, 4), dtype=z.dtype, device=z.device)
+            self._chk(self._lib.zkp_fr_eval_batch_dev(self._h, self._tp(evals), self._tp(z), n_poly, log2_n, flags, self._tp(out), self._stream()))
+            return out
+        z = _np(z, 4)
+        n_poly = z.shape[0]
+        evals = np.ascontiguousarray(evals, dtype=np.uint64)
+        if log2_n < 0 or evals.size != (n_poly << log2_n) * 4:
+            raise ValueError("evals hold %d elements for %d polynomials of 2^%d" % (evals.size // 4, n_poly, log2_n))
+        out = np.empty((n_poly, 4), dtype=np.uint64)
+        self._chk(self._lib.zkp_fr_eval_batch(self._h, _ptr(evals), _ptr(z), n_poly, log2_n, flags, _ptr(out)))
+        return out
+
+    def kzg_verify_batch(self, g1, g2, tau_g2, c, z, y, proof, *, inf_c=None, inf_proof=None, rand=None, points_checked=False, vk_checked=False):
+        """n KZG openings against one setup as ONE check (zkp_kzg_verify_batch): setup points g1 (12,), g2 / tau_g2 (24,); commitments c
+        and proofs (n, 12); points z and values y (n, 4).  True iff the random combination holds, every point is valid (unless
+        points_checked / vk_checked), every z and y is below r and no (a_i, b_i) is zero; a batch with a false opening passes with
+        probability <= 2^-128.  rand (n, 2) uint64, by default fresh from os.urandom (rlc_random) - never a seeded generator.  Host
+        arrays return a bool; resident torch tensors (all of them) an int32 tensor (1,) without synchronising."""
+        n = (c.numel() if _is_torch(c) else np.asarray(c).size) // 12
+        if n == 0:
+            return True
+        if rand is None:
+            rand = self.rlc_random(n)
+        flags = (_lib.KZG_POINTS_CHECKED if points_checked else 0) | (_lib.KZG_VK_CHECKED if vk_checked else 0)
+        vk_arrays = [("g1", g1, 12, 1), ("g2", g2, 24, 1), ("tau_g2", tau_g2, 24, 1)]
+        b_arrays = [("c", c, 12, n), ("inf_c", inf_c, None, n), ("proof", proof, 12, n), ("inf_proof", inf_proof, None, n), ("z", z, 4, n), ("y", y, 4, n)]
+        vk = _lib.KzgVk()
+        bt = _lib.KzgBatch(n=n)
+        if _is_torch(c):
+            import torch
+            dev = torch.device("cuda", self.device)
+            for rec, arrays in ((vk, vk_arrays), (bt, b_arrays)):
+                for name, x, w, rows in arrays:
+                    if x is None:
+                        continue
+                    if w is None:
+                        self._t_bytes(x, rows, name)
+                    else:
+                        self._t_check(x, w, name, rows=rows)
+                        if x.numel() != rows * w:
+                            raise ValueError("%s holds %d elements, %d expected" % (name, x.numel() // w, rows))
+                    setattr(rec, name, x.data_ptr())
+            if not _is_torch(rand):
+                rand = torch.from_numpy(np.ascontiguousarray(rand, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
+            self._t_check(rand, 2, "rand", rows=n)
+            all_ok = torch.empty(1, dtype=torch.int32, device=dev)
+            self._chk(self._lib.zkp_kzg_verify_batch_dev(self._h, ctypes.byref(vk), ctypes.byref(bt), self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            return all_ok
+        keep = []
+        for rec, arrays in ((vk, vk_arrays), (bt, b_arrays)):
+            for name, x, w, rows in arrays:
+                if x is None:
+                    continue
+                arr = _flags(x, rows, name) if w is None else _np(x, w)
+                if w is not None and arr.shape[0] != rows:
+                    raise ValueError("%s holds %d elements, %d expected" % (name, arr.shape[0], rows))
+                keep.append(arr)
+                setattr(rec, name, arr.ctypes.data)
+        r = _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d openings" % (r.shape[0], n))
+        res = ctypes.c_int(0)
+        self._chk(self._lib.zkp_kzg_verify_batch(self._h, ctypes.byref(vk), ctypes.byref(bt), _ptr(r), flags, ctypes.byref(res)))
+        return bool(res.value)
+
     def msm_profile(self, which, points, scalars, n_msm=1, shared_bases=False):
         """measurement: one MSM on torch tensors with the milliseconds of its six phases (zkp_msm_profile_dev)"""
         import torch

@@ -314,6 +314,22 @@ class Fr:
         return [Fr.from_array(r) for r in out], Fr.from_array(sw)
 
     @staticmethod
+    def invert_batch(a, engine=None):
+        """[a_i^-1] on the GPU by Montgomery's trick (zkp_fr_invert_batch: one power per call); 0 inverts to 0"""
+        return [Fr.from_array(r) for r in (engine or default_engine()).fr_invert(Fr._rows(a))]
+
+    @staticmethod
+    def evaluate(evals, z, bitrev=False, engine=None):
+        """p(z) for the polynomial of degree < N with p(w^i) = evals[i] over the N-th roots of unity (N = len(evals), a power of two;
+        evals[i] belongs to w^bitrev(i) with bitrev), on the GPU (zkp_fr_eval_batch)"""
+        evals = list(evals)
+        log2_n = len(evals).bit_length() - 1
+        if len(evals) != 1 << log2_n:
+            raise ValueError("the number of evaluations is not a power of two")
+        out = (engine or default_engine()).fr_eval(Fr._rows(evals), Fr._rows([z]), log2_n, bitrev)
+        return Fr.from_array(out[0])
+
+    @staticmethod
     def from_bytes_wide(data, engine=None):
         """64 little-endian bytes -> the integer mod r (src/fr.rs:192-217), on the GPU"""
         if len(data) != 64:
@@ -418,3 +434,89 @@ def groth16_verify_each(vk, proofs, inputs, engine=None):
         i1[:, 0], i2[:, 0], i1[:, 3] = ia, ib, ic
     per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 4, i1.reshape(-1), i2.reshape(-1))
     return ok & (np.asarray(per).reshape(-1) != 0)
+
+
+class KzgSetup:
+    """the verifier's side of a KZG setup: g1 in G1, g2 and [tau] g2 in G2, as wire arrays; every point is finite"""
+
+    def __init__(self, g1, g2, tau_g2):
+        arr = lambda p, w: (p.to_array() if hasattr(p, "to_array") else np.ascontiguousarray(p, dtype=np.uint64)).reshape(w)
+        self.g1, self.g2, self.tau_g2 = arr(g1, 12), arr(g2, 24), arr(tau_g2, 24)
+
+    def arrays(self):
+        return self.g1, self.g2, self.tau_g2
+
+
+def _kzg_arrays(commitments, z, y, proofs):
+    c, p = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 12) for x in (commitments, proofs))
+    z, y = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (z, y))
+    if not (c.shape[0] == p.shape[0] == z.shape[0] == y.shape[0]):
+        raise ValueError("commitments, z, y and proofs differ in number")
+    return c, z, y, p
+
+
+def kzg_verify_batch(setup, commitments, z, y, proofs, engine=None, rand=None, inf_c=None, inf_proof=None, points_checked=False, vk_checked=False):
+    """True iff every one of the n openings (C_i, z_i, y_i, pi_i) holds against the setup (zkp_kzg_verify_batch: one random combination,
+    one MSM call, one final exponentiation; a batch with a false opening passes with probability <= 2^-128).  commitments / proofs (n, 12),
+    z / y (n, 4) uint64, each below r.  kzg_verify_each finds the bad opening when this returns False."""
+    e = engine or default_engine()
+    c, z, y, p = _kzg_arrays(commitments, z, y, proofs)
+    return e.kzg_verify_batch(*setup.arrays(), c, z, y, p, inf_c=inf_c, inf_proof=inf_proof, rand=rand, points_checked=points_checked,
+                              vk_checked=vk_checked)
+
+
+def kzg_verify_each(setup, commitments, z, y, proofs, engine=None, inf_c=None, inf_proof=None):
+    """bool array (n,): opening i holds.  The per-opening path, composed only of calls that do not know KZG: -[y_i] g1 + [z_i] pi_i
+    through msm (n sums of two terms), C_i added by g1_add, then pairing_check with k = 2 on (C_i - [y_i] g1 + [z_i] pi_i, -g2),
+    (pi_i, [tau] g2), ANDed with is_valid of every point and with z_i, y_i < r."""
+    e = engine or default_engine()
+    c, z, y, p = _kzg_arrays(commitments, z, y, proofs)
+    n = c.shape[0]
+    ok = np.ones(n, dtype=bool)
+    if n == 0:
+        return ok
+    ic = np.zeros(n, dtype=np.uint8) if inf_c is None else np.ascontiguousarray(inf_c, dtype=np.uint8).reshape(n)
+    ip = np.zeros(n, dtype=np.uint8) if inf_proof is None else np.ascontiguousarray(inf_proof, dtype=np.uint8).reshape(n)
+    ok &= not (e.g1_is_valid(setup.g1).any() or e.g2_is_valid(np.stack([setup.g2, setup.tau_g2])).any())
+    ok &= (e.g1_is_valid(c, ic) == 0) & (e.g1_is_valid(p, ip) == 0)
+    ok &= synthetic.below_r(z) & synthetic.below_r(y)
+    r = synthetic.R_ORDER
+    pts = np.empty((n, 2, 12), dtype=np.uint64)
+    pts[:, 0], pts[:, 1] = setup.g1, p
+    sc = np.empty((n, 2, 4), dtype=np.uint64)
+    sc[:, 0] = synthetic._rows([-v % r for v in synthetic._ints(y)])
+    sc[:, 1] = z
+    inf = np.zeros((n, 2), dtype=np.uint8)
+    inf[:, 1] = ip
+    s, s_inf = e.g1_msm(pts.reshape(-1, 12), sc.reshape(-1, 4), n, inf.reshape(-1))
+    lhs, lhs_inf = e.g1_add(c, s, ic, s_inf)
+    g1 = np.empty((n, 2, 12), dtype=np.uint64)
+    g2 = np.empty((n, 2, 24), dtype=np.uint64)
+    g1[:, 0], g1[:, 1] = lhs, p
+    g2[:, 0], g2[:, 1] = _g2_neg_array(setup.g2), setup.tau_g2
+    i1 = np.zeros((n, 2), dtype=np.uint8)
+    i1[:, 0], i1[:, 1] = lhs_inf, ip
+    per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 2, i1.reshape(-1), np.zeros(2 * n, dtype=np.uint8))
+    return ok & (np.asarray(per).reshape(-1) != 0)
+
+
+def kzg_verify_blob_batch(setup, evals, commitments, z, proofs, bitrev=True, engine=None, rand=None):
+    """True iff proof j opens commitment j at z_j to the value of polynomial j there, the polynomial given by its N = 2^k evaluations
+    evals[j] over the N-th roots of unity (bit-reversed order with bitrev, the order blobs are stored in): y = fr_eval(evals, z) on
+    the device, then kzg_verify_batch on the same tensors - nothing returns to the host in between.  evals (n, N, 4)."""
+    import torch
+    e = engine or default_engine()
+    ev = np.ascontiguousarray(evals, dtype=np.uint64)
+    n = np.ascontiguousarray(z, dtype=np.uint64).size // 4
+    if n == 0:
+        return True
+    big_n = ev.size // 4 // n
+    log2_n = big_n.bit_length() - 1
+    if big_n < 1 or big_n != 1 << log2_n or ev.size != n * big_n * 4:
+        raise ValueError("evals hold %d elements for %d polynomials" % (ev.size // 4, n))
+    dev = torch.device("cuda", e.device)
+    t = lambda a, w: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, w).view(np.int64)).to(dev)
+    tz = t(z, 4)
+    ty = e.fr_eval(t(ev, 4), tz, log2_n, bitrev)
+    flag = e.kzg_verify_batch(*[t(a, w) for a, w in zip(setup.arrays(), (12, 24, 24))], t(commitments, 12), tz, ty, t(proofs, 12), rand=rand)
+    return bool(flag.item())

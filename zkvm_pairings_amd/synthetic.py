@@ -145,3 +145,90 @@ def groth16_instance(seed, n, n_inputs, bad=(), engine=None):
     key = (g1s[0].copy(), g2s[0].copy(), g2s[1].copy(), g2s[2].copy(), g1s[1:l + 2].copy())
     proofs = (g1s[l + 2:l + 2 + n].copy(), g2s[3:].copy(), g1s[l + 2 + n:].copy())
     return key, proofs, xw
+
+
+FR_GENERATOR, FR_S = 7, 32      # r - 1 = 2^32 * odd, 7 generates Fr* (reference src/common.rs)
+
+
+def fr_root_of_unity(log2_n):
+    """the generator w of the 2^log2_n-point domain: 7^((r - 1) / 2^log2_n), i.e. (7^((r - 1) / 2^32))^(2^(32 - log2_n))"""
+    if not 0 <= log2_n <= FR_S:
+        raise ValueError("log2_n outside 0 .. 32")
+    return pow(FR_GENERATOR, (R_ORDER - 1) >> log2_n, R_ORDER)
+
+
+def bit_reverse(i, bits):
+    return int(format(i, "0%db" % bits)[::-1], 2) if bits else 0
+
+
+def barycentric_eval(evals, z, log2_n, bitrev=False):
+    """the polynomial of degree < N = 2^log2_n with p(w^i) = evals[i] (evals[i] belongs to w^bit_reverse(i) with bitrev) at z, on Python
+    integers: (z^N - 1) / N * sum_i f_i w^i / (z - w^i), and f_i itself where z = w^i"""
+    r, n = R_ORDER, 1 << log2_n
+    if len(evals) != n:
+        raise ValueError("evals hold %d values for N = %d" % (len(evals), n))
+    w, z = fr_root_of_unity(log2_n), z % r
+    dom = [1] * n
+    for i in range(1, n):
+        dom[i] = dom[i - 1] * w % r
+    pts = [dom[bit_reverse(i, log2_n)] for i in range(n)] if bitrev else dom
+    acc = 0
+    for f, x in zip(evals, pts):
+        if x == z:
+            return int(f) % r
+        acc += int(f) * x * pow(z - x, -1, r)
+    return (pow(z, n, r) - 1) * pow(n, -1, r) * acc % r
+
+
+def _kzg_points(engine, tau, cexp, pexp):
+    n = len(cexp)
+    g1s, inf = engine.g1_mul(G1_GENERATOR, _rows(list(cexp) + list(pexp)))
+    tg2, _ = engine.g2_mul(G2_GENERATOR, _rows([tau]))
+    setup = (G1_GENERATOR.copy(), G2_GENERATOR.copy(), tg2[0].copy())
+    return setup, (g1s[:n].copy(), inf[:n].copy()), (g1s[n:].copy(), inf[n:].copy())
+
+
+def kzg_instance(seed, n, bad=(), engine=None):
+    """n synthetic KZG openings of one setup, built from secret exponents (Python integers mod r), no polynomial needed:
+        setup   g1 = G1, g2 = G2, [tau] G2
+        opening C_i = [c_i] G1, z_i, y_i random, pi_i = [(c_i - y_i) / (tau - z_i)] G1
+    so that e(C_i - [y_i] g1 + [z_i] pi_i, g2) = e(pi_i, [tau] g2) holds by construction; the openings listed in `bad` get C + G1 and fail.
+    -> (setup, commitments (n, 12), z (n, 4), y (n, 4), proofs (n, 12)), setup = (g1 (12,), g2 (24,), tau_g2 (24,))."""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    r = R_ORDER
+    (tau,) = _ints(scalars(seed ^ 0x7A0, 1))
+    c = _ints(scalars(seed ^ 0x0C, n))
+    zw, yw = scalars(seed ^ 0x0D, n), scalars(seed ^ 0x0E, n)
+    z, y = _ints(zw), _ints(yw)
+    bad = set(int(i) for i in bad)
+    pexp = [(c[i] - y[i]) * pow(tau - z[i], -1, r) % r for i in range(n)]
+    cexp = [(c[i] + (1 if i in bad else 0)) % r for i in range(n)]
+    setup, (cp, _), (pp, _) = _kzg_points(engine, tau, cexp, pexp)
+    return setup, cp, zw, yw, pp
+
+
+def kzg_blob_instance(seed, n, log2_n, bitrev=True, bad=(), engine=None):
+    """n polynomials given by N = 2^log2_n random evaluations each (stored in bit-reversed order with bitrev, like blobs), their
+    commitments [p_j(tau)] G1, a random point z_j each, y_j = p_j(z_j) and the proof [(p_j(tau) - y_j) / (tau - z_j)] G1 - the exponents by
+    the barycentric formula on Python integers.  The polynomials listed in `bad` get C + G1.
+    -> (setup, evals (n, N, 4), commitments (n, 12), z (n, 4), y (n, 4), proofs (n, 12))."""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    r, big_n = R_ORDER, 1 << log2_n
+    (tau,) = _ints(scalars(seed ^ 0x7A1, 1))
+    ew = scalars(seed ^ 0x0F, n * big_n).reshape(n, big_n, 4)
+    zw = scalars(seed ^ 0x10, n)
+    z = _ints(zw)
+    bad = set(int(i) for i in bad)
+    cexp, pexp, y = [], [], []
+    for j in range(n):
+        f = _ints(ew[j])
+        pt, yj = barycentric_eval(f, tau, log2_n, bitrev), barycentric_eval(f, z[j], log2_n, bitrev)
+        y.append(yj)
+        cexp.append((pt + (1 if j in bad else 0)) % r)
+        pexp.append((pt - yj) * pow(tau - z[j], -1, r) % r)
+    setup, (cp, _), (pp, _) = _kzg_points(engine, tau, cexp, pexp)
+    return setup, ew, cp, zw, _rows(y), pp
