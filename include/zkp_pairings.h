@@ -380,7 +380,9 @@ int zkp_tower_op_batch(zkp_ctx* ctx, int op, const uint64_t* a, const uint64_t* 
 
 /* ---- device-pointer entry points (buffers already resident in HBM; asynchronous on `stream`) ---- */
 /* `stream` is a hipStream_t passed as void* (NULL = default stream).  Same formats as above. */
-/* hipGraph capture (round 6): a `_dev` call on a stream that is being captured enqueues kernel / memset nodes only - no allocation once
+/* hipGraph capture (round 6): a `_dev` call on a stream that is being captured enqueues kernel nodes and, in some paths, memset and
+ * device-to-device copy nodes (the points check's counter, the RLC's fixed points and flags, the 576-byte results of the product calls;
+ * tests/test_gpu_graph_replay.py replays every entry point repeatedly on changed inputs) - no allocation once
  * the context's workspaces have reached the call's size (run the call once outside the capture first), no host synchronisation, and
  * the internal pipeline streams join the capture through their fork / join events.  The hand-over of the context's workspace between
  * calls on DIFFERENT streams (an event per context) is skipped under capture: order a replayed graph against the context's other

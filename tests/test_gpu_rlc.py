@@ -11,6 +11,7 @@ import pytest
 
 import bls12_381_model as bm
 import oracle_lib as o
+from replay_cases import free_checks, groth_checks      # the batch builders, shared with the replay and call-order tests
 
 pytestmark = pytest.mark.gpu
 P, R = bm.P, bm.R_ORDER
@@ -116,53 +117,6 @@ def test_endo_resident_tensors(eng):
 
 
 # ------------------------------------------------------------------------------------------------------------------- batch construction
-def free_checks(eng, rng, n, k, bad=(), zero_first=False):
-    """n checks of k pairs ([x_j]G1, [y_j]G2) with sum x_j y_j = 0 (mod r); checks in `bad` get x_(k-1) + 1.  k = 1: the G1 point is
-    the identity (flagged).  zero_first: the first pair of every check has x = 0, flagged as infinity."""
-    xs, ys, inf1 = [], [], np.zeros(n * k, dtype=np.uint8)
-    for c in range(n):
-        x = [rng.randrange(1, R) for _ in range(k)]
-        y = [rng.randrange(1, R) for _ in range(k)]
-        if zero_first or k == 1:
-            x[0] = 0
-            inf1[c * k] = 1
-        if k > 1:
-            x[k - 1] = (-sum(x[j] * y[j] for j in range(k - 1)) * pow(y[k - 1], -1, R)) % R
-        if c in bad:
-            x[k - 1] = (x[k - 1] + 1) % R
-            if k == 1:
-                inf1[c * k] = 0
-        xs += x
-        ys += y
-    return _g1(eng, xs), _g2(eng, ys), inf1
-
-
-def groth_checks(eng, rng, n, s2=3, bad=(), inf_col=False, inf_fixed=False):
-    """e(A, B) prod_j e(C_j, D_j) = 1: a b + sum c_j d_j = 0, D_j fixed.  inf_col: C_1 of every check is the identity (c_1 = 0);
-    inf_fixed: D_2 is the identity (d_2 = 0, C_2 arbitrary)."""
-    d = [rng.randrange(1, R) for _ in range(s2)]
-    if inf_fixed:
-        d[2] = 0
-    av, bv, cv = [], [], []
-    ci = np.zeros(n * s2, dtype=np.uint8)
-    for c in range(n):
-        a, b = rng.randrange(1, R), rng.randrange(1, R)
-        cc = [rng.randrange(1, R) for _ in range(s2)]
-        if inf_col:
-            cc[1] = 0
-            ci[c * s2 + 1] = 1
-        cc[0] = (-(a * b + sum(cc[j] * d[j] for j in range(1, s2))) * pow(d[0], -1, R)) % R
-        if c in bad:
-            cc[0] = (cc[0] + 1) % R
-        av.append(a)
-        bv.append(b)
-        cv += cc
-    fixed = _g2(eng, d)
-    fi = np.array([1 if x == 0 else 0 for x in d], dtype=np.uint8)
-    return dict(g1=_g1(eng, av), g2=_g2(eng, bv), k=1, col_g1=_g1(eng, cv), col_inf1=ci if inf_col else None, fixed_g2=fixed,
-                fixed_inf2=fi if inf_fixed else None)
-
-
 def bls_checks(eng, rng, n, bad=()):
     """e(pk, H) e(-G1, sigma) = 1 with pk = [x]G1, H = [h]G2, sigma = [x h]G2: the generator is the fixed G1 of one column"""
     xv = [rng.randrange(1, R) for _ in range(n)]
