@@ -8,6 +8,8 @@
 use core::ffi::{c_char, c_int, c_uint, c_void};
 use core::ptr;
 
+pub mod poly;
+
 #[repr(C)]
 pub struct ZkpCtx {
     _private: [u8; 0],

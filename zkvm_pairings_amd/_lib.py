@@ -1,4 +1,4 @@
-"""ctypes loader for libzkp_pairings.so (the C ABI declared in include/zkp_pairings.h).
+"""ctypes loader for libzkp_pairings.so (the C ABI declared in include/zkp_pairings.h and include/zkp_poly.h).
 
 No fallback of any kind: if the library is missing or a GPU is not usable the import / call
 raises.  The product never imports anything under oracle/."""
@@ -164,6 +164,16 @@ SIGNATURES = {
     "zkp_time_pairing_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_int, ctypes.POINTER(ctypes.c_float)]),
 }
 
+NTT_INVERSE, NTT_BITREV, NTT_COSET = 1, 2, 4   # ZKP_NTT_INVERSE / _BITREV / _COSET
+
+# name -> (restype, argtypes); MUST list every symbol include/zkp_poly.h declares (the second header of the same library)
+POLY_SIGNATURES = {
+    "zkp_fr_ntt_batch": (c_int, [c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp]),
+    "zkp_fr_ntt_batch_dev": (c_int, [c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp]),
+    "zkp_kzg_open_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp]),
+    "zkp_kzg_open_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -190,7 +200,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

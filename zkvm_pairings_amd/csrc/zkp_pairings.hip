@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/zkp_pairings.h"
+#include "../../include/zkp_poly.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -26,6 +27,8 @@
 #include "zkp_groth16_plan.hpp"
 #include "zkp_kzg.hpp"
 #include "zkp_kzg_plan.hpp"
+#include "zkp_poly.hpp"
+#include "zkp_poly_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -464,6 +467,7 @@ struct zkp_ctx {
     size_t kzg_cap = 0;
     uint32_t* kzg_dom = nullptr;   // omega^i for i < 2^kzg_dom_log2, Montgomery form: the evaluation's domain table (-1: none yet)
     int kzg_dom_log2 = -1;
+    uint32_t* poly_coset = nullptr;   // the NTT's coset tables (zkp_poly_plan.hpp: COSET_BYTES), built at the first coset call
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -888,6 +892,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->g16_ws) (void)hipFree(c->g16_ws);
     if (c->kzg_ws) (void)hipFree(c->kzg_ws);
     if (c->kzg_dom) (void)hipFree(c->kzg_dom);
+    if (c->poly_coset) (void)hipFree(c->poly_coset);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1578,6 +1583,17 @@ int kzg_domain(zkp_ctx* c, unsigned log2_n, const uint32_t** table, unsigned* ta
     }
     *table = c->kzg_dom;
     *table_log2 = (unsigned)c->kzg_dom_log2;
+    return ZKP_OK;
+}
+int poly_coset(zkp_ctx* c, const uint32_t** coset, hipStream_t s) {
+    if (!c->poly_coset) {
+        HIPCHK(c, hipMalloc((void**)&c->poly_coset, zkp::poly::COSET_BYTES));
+        zkp_dbg_alloc("ctx.poly_coset", c->poly_coset, zkp::poly::COSET_BYTES);
+        const hipError_t e = zkp::poly_coset_build(c->poly_coset, s);
+        if (e != hipSuccess) { (void)hipFree(c->poly_coset); c->poly_coset = nullptr; }
+        HIPCHK(c, e);
+    }
+    *coset = c->poly_coset;
     return ZKP_OK;
 }
 int grow_msm(zkp_ctx* c, size_t bytes) { return msm_grow(c, bytes); }
@@ -2387,6 +2403,87 @@ int zkp_kzg_verify_batch(zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* 
     int rc;
     if ((rc = io.status()) || (rc = kzg_validate(&dv, &d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
         (rc = zkp::kzg_check_dev(c, &dv, &d, (const uint64_t*)drand, flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the batched Fr NTT and the KZG opening (zkp_poly.hip, include/zkp_poly.h)
+namespace {
+int fr_ntt_dev(zkp_ctx* c, const void* in, size_t n_poly, unsigned log2_n, int flags, void* out, hipStream_t s) {
+    void* ws = nullptr;
+    const uint32_t *table = nullptr, *coset = nullptr;
+    unsigned table_log2 = 0;
+    int rc;
+    const size_t bytes = zkp::poly::ntt_workspace_bytes(n_poly, log2_n, flags);
+    if ((bytes && (rc = zkp::ctxop::grow_kzg(c, bytes, &ws))) || (rc = zkp::ctxop::kzg_domain(c, log2_n, &table, &table_log2, s)) ||
+        ((flags & ZKP_NTT_COSET) && (rc = zkp::ctxop::poly_coset(c, &coset, s))))
+        return rc;
+    return coop_rc(c, "fr_ntt", zkp::fr_ntt(ws, table, table_log2, coset, (const uint64_t*)in, n_poly, log2_n, flags, (uint64_t*)out, s));
+}
+bool fr_ntt_args_bad(const zkp_ctx* c, const void* in, size_t n_poly, unsigned log2_n, int flags, const void* out) {
+    return !c || zkp::poly::ntt_args_bad(n_poly, log2_n, flags) || (n_poly && (!in || !out));
+}
+bool kzg_open_args_bad(const zkp_ctx* c, const void* lagrange, const void* evals, const void* z, size_t n, unsigned log2_n, int flags, const void* y,
+                       const void* proof, const void* inf) {
+    return !c || zkp::poly::open_args_bad(n, log2_n, flags) || (n && (!lagrange || !evals || !z || !y || !proof || !inf));
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_fr_ntt_batch_dev(zkp_ctx* c, const void* in, size_t n_poly, unsigned log2_n, int flags, void* out, void* stream) {
+    if (fr_ntt_args_bad(c, in, n_poly, log2_n, flags, out)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_poly) return ZKP_OK;
+    if (int rc = validate_fr_on_stream(c, in, n_poly << log2_n, S(stream))) return rc;
+    return fr_ntt_dev(c, in, n_poly, log2_n, flags, out, S(stream));
+}
+int zkp_fr_ntt_batch(zkp_ctx* c, const uint64_t* in, size_t n_poly, unsigned log2_n, int flags, uint64_t* out) {
+    if (fr_ntt_args_bad(c, in, n_poly, log2_n, flags, out)) return ZKP_ERR_ARG;
+    if (!n_poly) return ZKP_OK;
+    const size_t bytes = (n_poly << log2_n) * 32;
+    HostIO io(c);
+    void* d = io.slot(0, bytes);      // transformed in place on the device
+    io.put(d, in, bytes);
+    io.get(out, d, bytes);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, d, n_poly << log2_n)) || (rc = fr_ntt_dev(c, d, n_poly, log2_n, flags, d, c->stream))) return rc;
+    return io.finish();
+}
+int zkp_kzg_open_batch_dev(zkp_ctx* c, const void* lagrange, const void* evals, const void* z, size_t n, unsigned log2_n, int flags, void* out_y,
+                           void* out_proof, void* out_inf, void* stream) {
+    if (kzg_open_args_bad(c, lagrange, evals, z, n, log2_n, flags, out_y, out_proof, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = validate_on_stream(c, lagrange, ((size_t)1 << log2_n) * 2, S(stream))) || (rc = validate_fr_on_stream(c, evals, n << log2_n, S(stream))) ||
+        (rc = validate_fr_on_stream(c, z, n, S(stream))))
+        return rc;
+    return zkp::kzg_open_dev(c, lagrange, (const uint64_t*)evals, (const uint64_t*)z, n, log2_n, flags, (uint64_t*)out_y, (uint64_t*)out_proof,
+                             (uint8_t*)out_inf, S(stream));
+}
+// the three outputs one after the other in slot 4 (256-byte aligned), then the same driver as the _dev flavour
+int zkp_kzg_open_batch(zkp_ctx* c, const uint64_t* lagrange, const uint64_t* evals, const uint64_t* z, size_t n, unsigned log2_n, int flags, uint64_t* out_y,
+                       uint64_t* out_proof, uint8_t* out_inf) {
+    if (kzg_open_args_bad(c, lagrange, evals, z, n, log2_n, flags, out_y, out_proof, out_inf)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t N = (size_t)1 << log2_n, off_p = (n * 32 + 255) & ~(size_t)255, off_i = off_p + ((n * 96 + 255) & ~(size_t)255);
+    HostIO io(c);
+    const void* dl = io.in(0, lagrange, N * 96);
+    const void* de = io.in(1, evals, (n << log2_n) * 32);
+    const void* dz = io.in(2, z, n * 32);
+    char* dout = (char*)io.slot(4, off_i + n);
+    if (dout) {
+        io.get(out_y, dout, n * 32);
+        io.get(out_proof, dout + off_p, n * 96);
+        io.get(out_inf, dout + off_i, n);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dl, N * 2)) || (rc = validate_fr_dev(c, de, n << log2_n)) || (rc = validate_fr_dev(c, dz, n)) ||
+        (rc = zkp::kzg_open_dev(c, dl, (const uint64_t*)de, (const uint64_t*)dz, n, log2_n, flags, (uint64_t*)dout, (uint64_t*)(dout + off_p),
+                                (uint8_t*)(dout + off_i), c->stream)))
         return rc;
     return io.finish();
 }

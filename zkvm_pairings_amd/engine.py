@@ -647,6 +647,70 @@ class PairingEngine:
         self._chk(self._lib.zkp_fr_eval_batch(self._h, _ptr(evals), _ptr(z), n_poly, log2_n, flags, _ptr(out)))
         return out
 
+    def fr_ntt(self, x, log2_n, inverse=False, bitrev=False, coset=False, out=None):
+        """The NTT of n_poly polynomials of N = 2^log2_n coefficients each over the N-th roots of unity w^i (zkp_fr_ntt_batch):
+        out[j][i] = sum_k x[j][k] (s w^i)^k, s = 7 with coset; with bitrev the evaluation side is bit-reversed (slot i belongs to
+        w^bitrev(i), the order fr_eval's bitrev reads); inverse is the exact inverse map under the same other flags.  x (n_poly, N, 4)
+        or (n_poly N, 4) uint64, canonical; the result has x's shape.  Resident torch tensors stay on the GPU (the current stream),
+        and out=x transforms in place."""
+        log2_n = int(log2_n)
+        flags = (_lib.NTT_INVERSE if inverse else 0) | (_lib.NTT_BITREV if bitrev else 0) | (_lib.NTT_COSET if coset else 0)
+        if _is_torch(x):
+            import torch
+            self._t_check(x, 4, "x")
+            n_el = x.numel() // 4
+            if log2_n < 0 or log2_n > 63 or n_el % (1 << log2_n):
+                raise ValueError("x holds %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+            if out is None:
+                out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            else:
+                self._t_check(out, 4, "out", rows=n_el)
+            self._chk(self._lib.zkp_fr_ntt_batch_dev(self._h, self._tp(x), n_el >> log2_n, log2_n, flags, self._tp(out), self._stream()))
+            return out
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        n_el = x.size // 4
+        if log2_n < 0 or log2_n > 63 or x.size % 4 or n_el % (1 << log2_n):
+            raise ValueError("x holds %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+        if out is None:
+            out = np.empty_like(x)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous and out.size == x.size):
+            raise ValueError("out must be a C-contiguous uint64 array of x's size")
+        self._chk(self._lib.zkp_fr_ntt_batch(self._h, _ptr(x), n_el >> log2_n, log2_n, flags, _ptr(out)))
+        return out
+
+    def kzg_open(self, lagrange_g1, evals, z, log2_n, bitrev=False):
+        """KZG openings on the GPU (zkp_kzg_open_batch): polynomial j, given by its N = 2^log2_n evaluations evals[j] (bit-reversed
+        order with bitrev), at the point z[j], against the Lagrange setup lagrange_g1 (N, 12) in the SAME order as the evaluations.
+        -> (y (n, 4), proofs (n, 12), inf (n,)): y[j] = f_j(z[j]) and the proof [(f_j(tau) - y[j]) / (tau - z[j])] g1 that
+        kzg_verify_batch consumes.  The setup points are trusted (check them once with g1_is_valid).  Resident torch tensors (all
+        three) stay on the GPU."""
+        log2_n, flags = int(log2_n), _lib.FR_EVAL_BITREV if bitrev else 0
+        if log2_n < 0 or log2_n > 63:
+            raise ValueError("log2_n out of range")
+        if _is_torch(evals):
+            import torch
+            self._t_check(z, 4, "z")
+            n = z.numel() // 4
+            self._t_check(evals, 4, "evals", rows=n << log2_n)
+            self._t_check(lagrange_g1, 12, "lagrange_g1", rows=1 << log2_n)
+            y = torch.empty((n, 4), dtype=z.dtype, device=z.device)
+            proof = torch.empty((n, 12), dtype=z.dtype, device=z.device)
+            inf = torch.empty(n, dtype=torch.uint8, device=z.device)
+            self._chk(self._lib.zkp_kzg_open_batch_dev(self._h, self._tp(lagrange_g1), self._tp(evals), self._tp(z), n, log2_n, flags, self._tp(y),
+                                                       self._tp(proof), self._tp(inf), self._stream()))
+            return y, proof, inf
+        z = _np(z, 4)
+        n = z.shape[0]
+        evals = np.ascontiguousarray(evals, dtype=np.uint64)
+        setup = _np(lagrange_g1, 12)
+        if evals.size != (n << log2_n) * 4:
+            raise ValueError("evals hold %d elements for %d polynomials of 2^%d" % (evals.size // 4, n, log2_n))
+        if setup.shape[0] != 1 << log2_n:
+            raise ValueError("the setup holds %d points for polynomials of 2^%d" % (setup.shape[0], log2_n))
+        y, proof, inf = np.empty((n, 4), dtype=np.uint64), np.empty((n, 12), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_kzg_open_batch(self._h, _ptr(setup), _ptr(evals), _ptr(z), n, log2_n, flags, _ptr(y), _ptr(proof), _ptr(inf)))
+        return y, proof, inf
+
     def kzg_verify_batch(self, g1, g2, tau_g2, c, z, y, proof, *, inf_c=None, inf_proof=None, rand=None, points_checked=False, vk_checked=False):
         """n KZG openings against one setup as ONE check (zkp_kzg_verify_batch): setup points g1 (12,), g2 / tau_g2 (24,); commitments c
         and proofs (n, 12); points z and values y (n, 4).  True iff the random combination holds, every point is valid (unless

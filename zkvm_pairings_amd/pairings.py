@@ -330,6 +330,17 @@ class Fr:
         return Fr.from_array(out[0])
 
     @staticmethod
+    def ntt(coeffs, inverse=False, bitrev=False, coset=False, engine=None):
+        """the evaluations of the polynomial sum_k coeffs[k] X^k over the N-th roots of unity w^i (N = len(coeffs), a power of two), on
+        the GPU (zkp_fr_ntt_batch); coset: over 7 w^i; bitrev: slot i belongs to w^bitrev(i); inverse: evaluations in, coefficients out"""
+        coeffs = list(coeffs)
+        log2_n = len(coeffs).bit_length() - 1
+        if len(coeffs) != 1 << log2_n:
+            raise ValueError("the number of coefficients is not a power of two")
+        out = (engine or default_engine()).fr_ntt(Fr._rows(coeffs), log2_n, inverse=inverse, bitrev=bitrev, coset=coset)
+        return [Fr.from_array(r) for r in out]
+
+    @staticmethod
     def from_bytes_wide(data, engine=None):
         """64 little-endian bytes -> the integer mod r (src/fr.rs:192-217), on the GPU"""
         if len(data) != 64:
@@ -498,6 +509,40 @@ def kzg_verify_each(setup, commitments, z, y, proofs, engine=None, inf_c=None, i
     i1[:, 0], i1[:, 1] = lhs_inf, ip
     per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 2, i1.reshape(-1), np.zeros(2 * n, dtype=np.uint8))
     return ok & (np.asarray(per).reshape(-1) != 0)
+
+
+def _kzg_poly_arrays(lagrange_g1, evals):
+    setup = np.ascontiguousarray(lagrange_g1, dtype=np.uint64).reshape(-1, 12)
+    big_n = setup.shape[0]
+    log2_n = big_n.bit_length() - 1
+    ev = np.ascontiguousarray(evals, dtype=np.uint64)
+    if big_n < 1 or big_n != 1 << log2_n or ev.size % (4 * big_n):
+        raise ValueError("%d setup points and %d evaluations: no whole number of polynomials of a power-of-two size" % (big_n, ev.size // 4))
+    return setup, ev.reshape(-1, 4), log2_n, ev.size // (4 * big_n)
+
+
+def kzg_commit_batch(lagrange_g1, evals, engine=None):
+    """(commitments (n, 12), inf (n,)): C_j = sum_i evals[j][i] lagrange_g1[i] = [f_j(tau)] g1 for polynomials in evaluation form over the
+    N = len(lagrange_g1) roots of unity, the setup in the same order as the evaluations (natural or bit-reversed): ONE shared-bases MSM
+    (g1_msm) of n sums over the N setup points.  evals (n, N, 4)."""
+    e = engine or default_engine()
+    setup, ev, _, n = _kzg_poly_arrays(lagrange_g1, evals)
+    if n == 0:
+        return np.zeros((0, 12), dtype=np.uint64), np.zeros(0, dtype=np.uint8)
+    return e.g1_msm(setup, ev, n, None, shared_bases=True)
+
+
+def kzg_open_batch(lagrange_g1, evals, z, bitrev=True, engine=None):
+    """(y (n, 4), proofs (n, 12), inf (n,)): polynomial j - its N evaluations evals[j] over the N-th roots of unity, in bit-reversed order
+    with bitrev as blobs are stored - opened at z[j] on the GPU (zkp_kzg_open_batch): y[j] = f_j(z[j]), proofs[j] = [q_j(tau)] g1 with
+    q_j = (f_j - y[j]) / (X - z[j]).  lagrange_g1 (N, 12) is the setup in the order of the evaluations, trusted.  The result is what
+    kzg_verify_batch consumes."""
+    e = engine or default_engine()
+    setup, ev, log2_n, n = _kzg_poly_arrays(lagrange_g1, evals)
+    z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+    if z.shape[0] != n:
+        raise ValueError("%d points for %d polynomials" % (z.shape[0], n))
+    return e.kzg_open(setup, ev, z, log2_n, bitrev)
 
 
 def kzg_verify_blob_batch(setup, evals, commitments, z, proofs, bitrev=True, engine=None, rand=None):
