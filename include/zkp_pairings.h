@@ -360,6 +360,7 @@ int zkp_kzg_verify_batch(zkp_ctx* ctx, const zkp_kzg_vk* vk, const zkp_kzg_batch
 int zkp_kzg_verify_batch_dev(zkp_ctx* ctx, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const void* d_rand, int flags, void* d_all_ok,
                              void* stream);
 /* the producer side - the batched Fr NTT and the KZG opening - is declared in zkp_poly.h, a second header of this library */
+/* the Groth16 producer side - the Fr sparse product, the QAP quotient, the batched prover - is declared in zkp_prove.h, a third header */
 
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).

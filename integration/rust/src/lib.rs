@@ -9,6 +9,7 @@ use core::ffi::{c_char, c_int, c_uint, c_void};
 use core::ptr;
 
 pub mod poly;
+pub mod prove;
 
 #[repr(C)]
 pub struct ZkpCtx {

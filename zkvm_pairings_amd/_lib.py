@@ -1,4 +1,4 @@
-"""ctypes loader for libzkp_pairings.so (the C ABI declared in include/zkp_pairings.h and include/zkp_poly.h).
+"""ctypes loader for libzkp_pairings.so (the C ABI declared in include/zkp_pairings.h, include/zkp_poly.h and include/zkp_prove.h).
 
 No fallback of any kind: if the library is missing or a GPU is not usable the import / call
 raises.  The product never imports anything under oracle/."""
@@ -174,6 +174,35 @@ POLY_SIGNATURES = {
     "zkp_kzg_open_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp, c_vp]),
 }
 
+
+
+class FrCsr(ctypes.Structure):
+    """zkp_fr_csr: a sparse matrix over Fr in compressed rows (field order of include/zkp_prove.h)"""
+    _fields_ = [("n_rows", c_sz), ("n_cols", c_sz), ("nnz", c_sz), ("row_ptr", c_vp), ("col", c_vp), ("val", c_vp)]
+
+
+class R1cs(ctypes.Structure):
+    """zkp_r1cs: the three matrices of a rank-one constraint system over the 2^log2_n-point domain"""
+    _fields_ = [("log2_n", ctypes.c_uint), ("n_inputs", c_sz), ("a", FrCsr), ("b", FrCsr), ("c", FrCsr)]
+
+
+class Groth16Pk(ctypes.Structure):
+    """zkp_groth16_pk: a proving key for zkp_groth16_prove_batch[_dev]"""
+    _fields_ = [(name, c_vp) for name in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2", "a_query", "a_inf", "b_g1_query", "b_g1_inf",
+                                          "b_g2_query", "b_g2_inf", "l_query", "l_inf", "h_query")]
+
+
+# name -> (restype, argtypes); MUST list every symbol include/zkp_prove.h declares (the third header of the same library)
+PROVE_SIGNATURES = {
+    "zkp_fr_spmv_batch": (c_int, [c_vp, ctypes.POINTER(FrCsr), c_vp, c_sz, c_sz, c_vp]),
+    "zkp_fr_spmv_batch_dev": (c_int, [c_vp, ctypes.POINTER(FrCsr), c_vp, c_sz, c_sz, c_vp, c_vp]),
+    "zkp_groth16_quotient_batch": (c_int, [c_vp, ctypes.POINTER(R1cs), c_vp, c_sz, c_vp, c_vp]),
+    "zkp_groth16_quotient_batch_dev": (c_int, [c_vp, ctypes.POINTER(R1cs), c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_groth16_prove_batch": (c_int, [c_vp, ctypes.POINTER(R1cs), ctypes.POINTER(Groth16Pk), c_vp, c_vp, c_sz, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_groth16_prove_batch_dev": (c_int, [c_vp, ctypes.POINTER(R1cs), ctypes.POINTER(Groth16Pk), c_vp, c_vp, c_sz, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
+}
+
 _lib = None
 
 
@@ -200,7 +229,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -16,6 +16,7 @@
 
 #include "../../include/zkp_pairings.h"
 #include "../../include/zkp_poly.h"
+#include "../../include/zkp_prove.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -29,6 +30,8 @@
 #include "zkp_kzg_plan.hpp"
 #include "zkp_poly.hpp"
 #include "zkp_poly_plan.hpp"
+#include "zkp_prove.hpp"
+#include "zkp_prove_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -468,6 +471,8 @@ struct zkp_ctx {
     uint32_t* kzg_dom = nullptr;   // omega^i for i < 2^kzg_dom_log2, Montgomery form: the evaluation's domain table (-1: none yet)
     int kzg_dom_log2 = -1;
     uint32_t* poly_coset = nullptr;   // the NTT's coset tables (zkp_poly_plan.hpp: COSET_BYTES), built at the first coset call
+    void* prove_ws = nullptr;   // grow-only workspace of the QAP quotient and the Groth16 prover (zkp_prove_plan.hpp layout)
+    size_t prove_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -759,7 +764,7 @@ int host_sliced(zkp_ctx* c, const uint64_t* g1, const uint64_t* g2, const uint8_
 struct Staging {
     zkp_ctx* c;
     int rc = ZKP_OK;
-    struct Copy { void* host; const void* dev; size_t bytes; } down[4];   // the most a call needs: the points check's
+    struct Copy { void* host; const void* dev; size_t bytes; } down[8];   // the most a call needs: the prover's seven
     int n_down = 0;
     explicit Staging(zkp_ctx* ctx) : c(ctx) {}
     int status() const { return rc; }
@@ -773,7 +778,7 @@ struct Staging {
     }
     void get(void* host, const void* dev, size_t bytes) {
         if (!host || !bytes || rc) return;
-        if (n_down == 4) { c->err = "Staging: more than four downloads"; rc = ZKP_ERR_ARG; return; }
+        if (n_down == 8) { c->err = "Staging: more than eight downloads"; rc = ZKP_ERR_ARG; return; }
         down[n_down++] = {host, dev, bytes};
     }
     const void* in(int i, const void* host, size_t bytes) { return host ? put(slot(i, bytes), host, bytes) : nullptr; }
@@ -891,6 +896,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->rlc_ws) (void)hipFree(c->rlc_ws);
     if (c->g16_ws) (void)hipFree(c->g16_ws);
     if (c->kzg_ws) (void)hipFree(c->kzg_ws);
+    if (c->prove_ws) (void)hipFree(c->prove_ws);
     if (c->kzg_dom) (void)hipFree(c->kzg_dom);
     if (c->poly_coset) (void)hipFree(c->poly_coset);
     for (int i = 0; i < 2; i++) {
@@ -1595,6 +1601,23 @@ int poly_coset(zkp_ctx* c, const uint32_t** coset, hipStream_t s) {
     }
     *coset = c->poly_coset;
     return ZKP_OK;
+}
+int grow_prove(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->prove_cap) {
+        if (c->prove_ws) { HIPCHK(c, hipFree(c->prove_ws)); c->prove_ws = nullptr; c->prove_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->prove_ws, bytes));
+        zkp_dbg_alloc("ctx.prove", c->prove_ws, bytes);
+        c->prove_cap = bytes;
+    }
+    *ws = c->prove_ws;
+    return ZKP_OK;
+}
+int* validation_word(zkp_ctx* c) { return c->d_flag + 2; }
+int mul(zkp_ctx* c, int which, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, hipStream_t s) {
+    return mul_dev(c, which, base, stride, sc, n, out, out_inf, s);
+}
+int add(zkp_ctx* c, int which, const void* a, const void* inf_a, const void* b, const void* inf_b, size_t n, void* out, void* out_inf, hipStream_t s) {
+    return add_dev(c, which, a, inf_a, b, inf_b, n, out, out_inf, s);
 }
 int grow_msm(zkp_ctx* c, size_t bytes) { return msm_grow(c, bytes); }
 int msm(zkp_ctx* c, int which, const void* pts, const void* inf, const void* sc, size_t m, size_t n_msm, void* out, void* out_inf, hipStream_t s) {
@@ -2484,6 +2507,202 @@ int zkp_kzg_open_batch(zkp_ctx* c, const uint64_t* lagrange, const uint64_t* eva
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dl, N * 2)) || (rc = validate_fr_dev(c, de, n << log2_n)) || (rc = validate_fr_dev(c, dz, n)) ||
         (rc = zkp::kzg_open_dev(c, dl, (const uint64_t*)de, (const uint64_t*)dz, n, log2_n, flags, (uint64_t*)dout, (uint64_t*)(dout + off_p),
                                 (uint8_t*)(dout + off_i), c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the Fr sparse product, the QAP quotient and the Groth16 prover (zkp_prove.hip,
+// include/zkp_prove.h)
+namespace {
+bool csr_ptrs_bad(const zkp_fr_csr* m) { return (m->n_rows && !m->row_ptr) || (m->nnz && (!m->col || !m->val)); }
+bool spmv_args_bad(const zkp_ctx* c, const zkp_fr_csr* m, const void* x, size_t n, size_t out_stride, const void* out) {
+    if (!c || !m || zkp::prove::spmv_args_bad(m->n_rows, m->n_cols, m->nnz, n, out_stride) || csr_ptrs_bad(m)) return true;
+    return n && ((out_stride && !out) || (m->n_cols && !x));
+}
+bool r1cs_args_bad(const zkp_ctx* c, const zkp_r1cs* r, const void* witness, size_t n) {
+    if (!c || !r ||
+        zkp::prove::r1cs_args_bad(r->log2_n, r->n_inputs, r->a.n_rows, r->a.n_cols, r->a.nnz, r->b.n_rows, r->b.n_cols, r->b.nnz, r->c.n_rows, r->c.n_cols,
+                                  r->c.nnz, n) ||
+        csr_ptrs_bad(&r->a) || csr_ptrs_bad(&r->b) || csr_ptrs_bad(&r->c))
+        return true;
+    return n && !witness;
+}
+bool prove_args_bad(const zkp_ctx* c, const zkp_r1cs* r, const zkp_groth16_pk* pk, const void* witness, const void* rs, size_t n, int flags, const void* a,
+                    const void* ia, const void* b, const void* ib, const void* cc, const void* ic, const void* sat) {
+    if (flags || !pk || r1cs_args_bad(c, r, witness, n)) return true;
+    if (!n) return false;
+    if (!rs || !a || !ia || !b || !ib || !cc || !ic || !sat) return true;
+    if (!pk->alpha_g1 || !pk->beta_g1 || !pk->delta_g1 || !pk->beta_g2 || !pk->delta_g2 || !pk->a_query || !pk->b_g1_query || !pk->b_g2_query || !pk->h_query)
+        return true;
+    return r->a.n_cols - r->n_inputs - 1 && !pk->l_query;
+}
+// what the host flavour can check and the _dev flavour cannot: the row bounds and the columns of a matrix in host memory
+bool csr_malformed(const zkp_fr_csr* m) {
+    const uint32_t* rp = (const uint32_t*)m->row_ptr;
+    const uint32_t* col = (const uint32_t*)m->col;
+    if (m->n_rows) {
+        if (rp[0] != 0 || rp[m->n_rows] != m->nnz) return true;
+        for (size_t k = 0; k < m->n_rows; k++)
+            if (rp[k] > rp[k + 1]) return true;
+    } else if (m->nnz) {
+        return true;
+    }
+    for (size_t e = 0; e < m->nnz; e++)
+        if (col[e] >= m->n_cols) return true;
+    return false;
+}
+// a matrix's three arrays into one workspace slot (256-byte aligned one after the other): *d is m with device pointers
+size_t csr_bytes(const zkp_fr_csr* m) {
+    return zkp::prove::up256((m->n_rows + 1) * 4) + zkp::prove::up256(m->nnz * 4) + zkp::prove::up256(m->nnz * 32);
+}
+char* csr_put(Staging& io, char* dev, const zkp_fr_csr* m, zkp_fr_csr* d) {
+    *d = *m;
+    d->row_ptr = m->n_rows ? io.put(dev, m->row_ptr, (m->n_rows + 1) * 4) : nullptr;
+    dev += zkp::prove::up256((m->n_rows + 1) * 4);
+    d->col = io.put(dev, m->col, m->nnz * 4);
+    dev += zkp::prove::up256(m->nnz * 4);
+    d->val = io.put(dev, m->val, m->nnz * 32);
+    return dev + zkp::prove::up256(m->nnz * 32);
+}
+int spmv_dev(zkp_ctx* c, const zkp_fr_csr* m, const void* x, size_t n, size_t out_stride, void* out, hipStream_t s) {
+    return coop_rc(c, "fr_spmv", zkp::fr_spmv(m, (const uint64_t*)x, n, out_stride, 0, (uint64_t*)out, c->d_flag + 2, s));
+}
+// validation mode: v(pointer, Fr count) over the values of the three matrices
+template <class V>
+int r1cs_validate(const zkp_r1cs* r, V&& v) {
+    int rc;
+    if ((rc = v(r->a.val, r->a.nnz)) || (rc = v(r->b.val, r->b.nnz)) || (rc = v(r->c.val, r->c.nnz))) return rc;
+    return ZKP_OK;
+}
+// validation mode: v(pointer, Fp count) over every coordinate array of a proving key
+template <class V>
+int pk_validate(const zkp_r1cs* r, const zkp_groth16_pk* pk, V&& v) {
+    const size_t m = r->a.n_cols, N = (size_t)1 << r->log2_n;
+    int rc;
+    if ((rc = v(pk->alpha_g1, 2)) || (rc = v(pk->beta_g1, 2)) || (rc = v(pk->delta_g1, 2)) || (rc = v(pk->beta_g2, 4)) || (rc = v(pk->delta_g2, 4)) ||
+        (rc = v(pk->a_query, m * 2)) || (rc = v(pk->b_g1_query, m * 2)) || (rc = v(pk->b_g2_query, m * 4)) ||
+        (rc = v(pk->l_query, (m - r->n_inputs - 1) * 2)) || (rc = v(pk->h_query, (N - 1) * 2)))
+        return rc;
+    return ZKP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_fr_spmv_batch_dev(zkp_ctx* c, const zkp_fr_csr* m, const void* x, size_t n, size_t out_stride, void* out, void* stream) {
+    if (spmv_args_bad(c, m, x, n, out_stride, out)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n || !out_stride) return ZKP_OK;
+    int rc;
+    if ((rc = validate_fr_on_stream(c, m->val, m->nnz, S(stream))) || (rc = validate_fr_on_stream(c, x, n * m->n_cols, S(stream)))) return rc;
+    return spmv_dev(c, m, x, n, out_stride, out, S(stream));
+}
+int zkp_fr_spmv_batch(zkp_ctx* c, const zkp_fr_csr* m, const uint64_t* x, size_t n, size_t out_stride, uint64_t* out) {
+    if (spmv_args_bad(c, m, x, n, out_stride, out)) return ZKP_ERR_ARG;
+    if (csr_malformed(m)) return ZKP_ERR_ARG;
+    if (!n || !out_stride) return ZKP_OK;
+    HostIO io(c);
+    zkp_fr_csr d;
+    char* dev = (char*)io.slot(0, csr_bytes(m));
+    csr_put(io, dev, m, &d);
+    const void* dx = io.in(1, x, n * m->n_cols * 32);
+    void* dout = io.out(4, out, n * out_stride * 32);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_fr_dev(c, d.val, d.nnz)) || (rc = validate_fr_dev(c, dx, n * m->n_cols)) ||
+        (rc = spmv_dev(c, &d, dx, n, out_stride, dout, c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_groth16_quotient_batch_dev(zkp_ctx* c, const zkp_r1cs* r, const void* witness, size_t n, void* out_h, void* out_sat, void* stream) {
+    if (r1cs_args_bad(c, r, witness, n) || (n && (!out_h || !out_sat))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = r1cs_validate(r, [&](const void* d, size_t cnt) { return validate_fr_on_stream(c, d, cnt, S(stream)); })) ||
+        (rc = validate_fr_on_stream(c, witness, n * r->a.n_cols, S(stream))))
+        return rc;
+    return zkp::groth16_quotient_dev(c, r, (const uint64_t*)witness, n, (uint64_t*)out_h, (uint8_t*)out_sat, S(stream));
+}
+// the three matrices one after the other in slot 0, the witness in slot 1, h and sat in slots 4 and 5, then the _dev flavour's driver
+int zkp_groth16_quotient_batch(zkp_ctx* c, const zkp_r1cs* r, const uint64_t* witness, size_t n, uint64_t* out_h, uint8_t* out_sat) {
+    if (r1cs_args_bad(c, r, witness, n) || (n && (!out_h || !out_sat))) return ZKP_ERR_ARG;
+    if (csr_malformed(&r->a) || csr_malformed(&r->b) || csr_malformed(&r->c)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t m = r->a.n_cols, N = (size_t)1 << r->log2_n;
+    HostIO io(c);
+    zkp_r1cs d = *r;
+    char* dev = (char*)io.slot(0, csr_bytes(&r->a) + csr_bytes(&r->b) + csr_bytes(&r->c));
+    dev = csr_put(io, dev, &r->a, &d.a);
+    dev = csr_put(io, dev, &r->b, &d.b);
+    csr_put(io, dev, &r->c, &d.c);
+    const void* dw = io.in(1, witness, n * m * 32);
+    void* dh = io.out(4, out_h, n * N * 32);
+    void* dsat = io.out(5, out_sat, n);
+    int rc;
+    if ((rc = io.status()) || (rc = r1cs_validate(&d, [&](const void* p, size_t cnt) { return validate_fr_dev(c, p, cnt); })) ||
+        (rc = validate_fr_dev(c, dw, n * m)) || (rc = zkp::groth16_quotient_dev(c, &d, (const uint64_t*)dw, n, (uint64_t*)dh, (uint8_t*)dsat, c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_groth16_prove_batch_dev(zkp_ctx* c, const zkp_r1cs* r, const zkp_groth16_pk* pk, const void* witness, const void* rs, size_t n, int flags,
+                                void* out_a, void* out_inf_a, void* out_b, void* out_inf_b, void* out_c, void* out_inf_c, void* out_sat, void* stream) {
+    if (prove_args_bad(c, r, pk, witness, rs, n, flags, out_a, out_inf_a, out_b, out_inf_b, out_c, out_inf_c, out_sat)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = r1cs_validate(r, [&](const void* d, size_t cnt) { return validate_fr_on_stream(c, d, cnt, S(stream)); })) ||
+        (rc = validate_fr_on_stream(c, witness, n * r->a.n_cols, S(stream))) || (rc = validate_fr_on_stream(c, rs, n * 2, S(stream))) ||
+        (rc = pk_validate(r, pk, [&](const void* d, size_t n_fp) { return validate_on_stream(c, d, n_fp, S(stream)); })))
+        return rc;
+    return zkp::groth16_prove_dev(c, r, pk, (const uint64_t*)witness, (const uint64_t*)rs, n, (uint64_t*)out_a, (uint8_t*)out_inf_a, (uint64_t*)out_b,
+                                  (uint8_t*)out_inf_b, (uint64_t*)out_c, (uint8_t*)out_inf_c, (uint8_t*)out_sat, S(stream));
+}
+// the matrices in slot 0, the witness in slot 1, rs in slot 2, the key's fourteen arrays one after the other in slot 3, the seven
+// outputs one after the other in slot 4 (everything 256-byte aligned), then the _dev flavour's driver
+int zkp_groth16_prove_batch(zkp_ctx* c, const zkp_r1cs* r, const zkp_groth16_pk* pk, const uint64_t* witness, const uint64_t* rs, size_t n, int flags,
+                            uint64_t* out_a, uint8_t* out_inf_a, uint64_t* out_b, uint8_t* out_inf_b, uint64_t* out_c, uint8_t* out_inf_c, uint8_t* out_sat) {
+    if (prove_args_bad(c, r, pk, witness, rs, n, flags, out_a, out_inf_a, out_b, out_inf_b, out_c, out_inf_c, out_sat)) return ZKP_ERR_ARG;
+    if (csr_malformed(&r->a) || csr_malformed(&r->b) || csr_malformed(&r->c)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t m = r->a.n_cols, N = (size_t)1 << r->log2_n, nl = m - r->n_inputs - 1;
+    HostIO io(c);
+    zkp_r1cs d = *r;
+    char* dev = (char*)io.slot(0, csr_bytes(&r->a) + csr_bytes(&r->b) + csr_bytes(&r->c));
+    dev = csr_put(io, dev, &r->a, &d.a);
+    dev = csr_put(io, dev, &r->b, &d.b);
+    csr_put(io, dev, &r->c, &d.c);
+    const void* dw = io.in(1, witness, n * m * 32);
+    const void* drs = io.in(2, rs, n * 64);
+    zkp_groth16_pk dk = *pk;
+    const void** field[14] = {&dk.alpha_g1, &dk.beta_g1, &dk.delta_g1, &dk.beta_g2, &dk.delta_g2, &dk.a_query, &dk.a_inf, &dk.b_g1_query, &dk.b_g1_inf,
+                              &dk.b_g2_query, &dk.b_g2_inf, &dk.l_query, &dk.l_inf, &dk.h_query};
+    const size_t bytes[14] = {96, 96, 96, 192, 192, m * 96, m, m * 96, m, m * 192, m, nl * 96, nl, (N - 1) * 96};
+    size_t off[14], total = 0;
+    for (int i = 0; i < 14; i++) {
+        off[i] = total;
+        total += zkp::prove::up256(bytes[i]);
+    }
+    char* dpk = (char*)io.slot(3, total);
+    for (int i = 0; i < 14; i++) *field[i] = bytes[i] ? io.put(dpk + off[i], *field[i], bytes[i]) : nullptr;
+    void* const host_out[7] = {out_a, out_inf_a, out_b, out_inf_b, out_c, out_inf_c, out_sat};
+    const size_t out_bytes[7] = {n * 96, n, n * 192, n, n * 96, n, n};
+    size_t out_off[7], out_total = 0;
+    for (int i = 0; i < 7; i++) {
+        out_off[i] = out_total;
+        out_total += zkp::prove::up256(out_bytes[i]);
+    }
+    char* dout = (char*)io.slot(4, out_total);
+    if (dout)
+        for (int i = 0; i < 7; i++) io.get(host_out[i], dout + out_off[i], out_bytes[i]);
+    int rc;
+    if ((rc = io.status()) || (rc = r1cs_validate(&d, [&](const void* p, size_t cnt) { return validate_fr_dev(c, p, cnt); })) ||
+        (rc = validate_fr_dev(c, dw, n * m)) || (rc = validate_fr_dev(c, drs, n * 2)) ||
+        (rc = pk_validate(&d, &dk, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
+        (rc = zkp::groth16_prove_dev(c, &d, &dk, (const uint64_t*)dw, (const uint64_t*)drs, n, (uint64_t*)(dout + out_off[0]), (uint8_t*)(dout + out_off[1]),
+                                     (uint64_t*)(dout + out_off[2]), (uint8_t*)(dout + out_off[3]), (uint64_t*)(dout + out_off[4]),
+                                     (uint8_t*)(dout + out_off[5]), (uint8_t*)(dout + out_off[6]), c->stream)))
         return rc;
     return io.finish();
 }

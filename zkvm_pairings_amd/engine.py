@@ -711,6 +711,162 @@ class PairingEngine:
         self._chk(self._lib.zkp_kzg_open_batch(self._h, _ptr(setup), _ptr(evals), _ptr(z), n, log2_n, flags, _ptr(y), _ptr(proof), _ptr(inf)))
         return y, proof, inf
 
+    # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
+    def _csr(self, mat, name, keep, resident):
+        """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""
+        n_rows, n_cols, row_ptr, col, val = mat
+        n_rows, n_cols = int(n_rows), int(n_cols)
+        if n_rows < 0 or n_cols < 0:
+            raise ValueError("%s: negative shape" % name)
+        rec = _lib.FrCsr(n_rows=n_rows, n_cols=n_cols)
+        if resident:
+            import torch
+            i32 = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+            self._t_check(col, None, name + ".col", dtypes=i32)
+            nnz = col.numel()
+            self._t_check(val, 4, name + ".val", rows=nnz)
+            self._t_check(row_ptr, None, name + ".row_ptr", rows=n_rows + 1, dtypes=i32)
+            if val.numel() != nnz * 4 or row_ptr.numel() != n_rows + 1:
+                raise ValueError("%s: %d row bounds, %d columns, %d values for %d rows" % (name, row_ptr.numel(), nnz, val.numel() // 4, n_rows))
+            rec.nnz, rec.row_ptr, rec.col, rec.val = nnz, row_ptr.data_ptr(), col.data_ptr() if nnz else None, val.data_ptr() if nnz else None
+            return rec
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint32).reshape(-1)
+        col = np.ascontiguousarray(col, dtype=np.uint32).reshape(-1)
+        val = _np(val, 4)
+        if row_ptr.size != n_rows + 1 or val.shape[0] != col.size:
+            raise ValueError("%s: %d row bounds, %d columns, %d values for %d rows" % (name, row_ptr.size, col.size, val.shape[0], n_rows))
+        keep += [row_ptr, col, val]
+        rec.nnz, rec.row_ptr, rec.col, rec.val = col.size, row_ptr.ctypes.data, col.ctypes.data if col.size else None, val.ctypes.data if col.size else None
+        return rec
+
+    def _r1cs(self, log2_n, n_inputs, a, b, c, keep, resident):
+        rec = _lib.R1cs(log2_n=int(log2_n), n_inputs=int(n_inputs))
+        rec.a, rec.b, rec.c = (self._csr(x, name, keep, resident) for x, name in ((a, "a"), (b, "b"), (c, "c")))
+        if not 0 <= int(log2_n) <= 63 or int(n_inputs) < 0:
+            raise ValueError("log2_n or n_inputs out of range")
+        return rec
+
+    def fr_spmv(self, mat, x, out_stride=None):
+        """out (n, out_stride, 4): the sparse matrix mat = (n_rows, n_cols, row_ptr, col, val) in compressed rows times n dense vectors x
+        (n, n_cols, 4) over Fr (zkp_fr_spmv_batch): out[j][k] = sum_e val[e] x[j][col[e]] over row k, zero from n_rows to out_stride
+        (default n_rows).  Canonical in, canonical out.  Host arrays have their matrix checked (ZkpError on a malformed one); resident
+        torch tensors (all of them) stay on the GPU, where a malformed matrix reads nothing outside its arrays and sets the
+        validation word."""
+        n_rows, n_cols = int(mat[0]), int(mat[1])
+        out_stride = n_rows if out_stride is None else int(out_stride)
+        resident = _is_torch(x)
+        keep = []
+        rec = self._csr(mat, "mat", keep, resident)
+        if out_stride < 0:
+            raise ValueError("out_stride is negative")
+        if resident:
+            import torch
+            self._t_check(x, 4, "x")
+            if n_cols == 0 or x.numel() % (4 * n_cols):
+                raise ValueError("x holds no whole number of vectors of %d elements" % n_cols)
+            n = x.numel() // (4 * n_cols)
+            out = torch.empty((n, out_stride, 4), dtype=x.dtype, device=x.device)
+            self._chk(self._lib.zkp_fr_spmv_batch_dev(self._h, ctypes.byref(rec), self._tp(x), n, out_stride, self._tp(out), self._stream()))
+            return out
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        if n_cols == 0 or x.size % (4 * n_cols):
+            raise ValueError("x holds no whole number of vectors of %d elements" % n_cols)
+        n = x.size // (4 * n_cols)
+        out = np.empty((n, out_stride, 4), dtype=np.uint64)
+        self._chk(self._lib.zkp_fr_spmv_batch(self._h, ctypes.byref(rec), _ptr(x), n, out_stride, _ptr(out)))
+        return out
+
+    def groth16_quotient(self, log2_n, n_inputs, a, b, c, witness):
+        """(h (n, N, 4), sat (n,) uint8): the QAP quotient of n witnesses (n, m, 4) of the constraint system A, B, C (each a matrix
+        tuple as in fr_spmv, n_rows x m) over the N = 2^log2_n-point domain (zkp_groth16_quotient_batch): h = (a b - c) / (X^N - 1)
+        by its N coefficients, natural order, and sat[j] = 1 iff witness j satisfies every row.  Resident torch tensors stay on the
+        GPU."""
+        resident = _is_torch(witness)
+        keep = []
+        rec = self._r1cs(log2_n, n_inputs, a, b, c, keep, resident)
+        m, big_n = int(a[1]), 1 << int(log2_n)
+        if resident:
+            import torch
+            self._t_check(witness, 4, "witness")
+            if m == 0 or witness.numel() % (4 * m):
+                raise ValueError("the witnesses hold no whole number of vectors of %d elements" % m)
+            n = witness.numel() // (4 * m)
+            h = torch.empty((n, big_n, 4), dtype=witness.dtype, device=witness.device)
+            sat = torch.empty(n, dtype=torch.uint8, device=witness.device)
+            self._chk(self._lib.zkp_groth16_quotient_batch_dev(self._h, ctypes.byref(rec), self._tp(witness), n, self._tp(h), self._tp(sat), self._stream()))
+            return h, sat
+        w = np.ascontiguousarray(witness, dtype=np.uint64)
+        if m == 0 or w.size % (4 * m):
+            raise ValueError("the witnesses hold no whole number of vectors of %d elements" % m)
+        n = w.size // (4 * m)
+        h, sat = np.empty((n, big_n, 4), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_groth16_quotient_batch(self._h, ctypes.byref(rec), _ptr(w), n, _ptr(h), _ptr(sat)))
+        return h, sat
+
+    _PK_FIELDS = (("alpha_g1", 12), ("beta_g1", 12), ("delta_g1", 12), ("beta_g2", 24), ("delta_g2", 24), ("a_query", 12), ("a_inf", None), ("b_g1_query", 12),
+                  ("b_g1_inf", None), ("b_g2_query", 24), ("b_g2_inf", None), ("l_query", 12), ("l_inf", None), ("h_query", 12))
+
+    def groth16_prove(self, log2_n, n_inputs, a, b, c, pk, witness, rs):
+        """n Groth16 proofs of one circuit (zkp_groth16_prove_batch): the constraint system as in groth16_quotient, the proving key pk a
+        mapping of zkp_groth16_pk's field names to wire arrays (alpha_g1 / beta_g1 / delta_g1 (12,), beta_g2 / delta_g2 (24,), a_query
+        and b_g1_query (m, 12), b_g2_query (m, 24), l_query (m - n_inputs - 1, 12), h_query (N - 1, 12), optional infinity bytes
+        a_inf / b_g1_inf / b_g2_inf / l_inf), witnesses (n, m, 4) and the blinding scalars rs (n, 2, 4) - draw them uniformly and fresh
+        per proof.  -> (A (n, 12), inf_a, B (n, 24), inf_b, C (n, 12), inf_c, sat): what groth16_verify_batch consumes, and sat[j] = 1 iff
+        witness j satisfies the system.  The key points are trusted.  Resident torch tensors (all of them) stay on the GPU."""
+        resident = _is_torch(witness)
+        keep = []
+        rec = self._r1cs(log2_n, n_inputs, a, b, c, keep, resident)
+        m, big_n, l = int(a[1]), 1 << int(log2_n), int(n_inputs)
+        rows = {"a_query": m, "a_inf": m, "b_g1_query": m, "b_g1_inf": m, "b_g2_query": m, "b_g2_inf": m, "l_query": m - l - 1, "l_inf": m - l - 1,
+                "h_query": big_n - 1}
+        if m - l - 1 < 0:
+            raise ValueError("n_inputs + 1 exceeds the number of variables")
+        key = _lib.Groth16Pk()
+        for name, w in self._PK_FIELDS:
+            x = pk.get(name)
+            cnt = rows.get(name, 1)
+            if x is None or cnt == 0:
+                if w is not None and cnt:
+                    raise ValueError("the proving key lacks %s" % name)
+                continue
+            if resident:
+                if w is None:
+                    self._t_bytes(x, cnt, name)
+                else:
+                    self._t_check(x, w, name, rows=cnt)
+                setattr(key, name, x.data_ptr())
+            else:
+                arr = _flags(x, cnt, name) if w is None else _np(x, w)
+                if w is not None and arr.shape[0] != cnt:
+                    raise ValueError("%s holds %d points, %d expected" % (name, arr.shape[0], cnt))
+                keep.append(arr)
+                setattr(key, name, arr.ctypes.data)
+        if resident:
+            import torch
+            self._t_check(witness, 4, "witness")
+            if m == 0 or witness.numel() % (4 * m):
+                raise ValueError("the witnesses hold no whole number of vectors of %d elements" % m)
+            n = witness.numel() // (4 * m)
+            self._t_check(rs, 8, "rs", rows=n)
+            dev, dt = witness.device, witness.dtype
+            pa, pb, pc = (torch.empty((n, w), dtype=dt, device=dev) for w in (12, 24, 12))
+            ia, ib, ic, sat = (torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(4))
+            self._chk(self._lib.zkp_groth16_prove_batch_dev(self._h, ctypes.byref(rec), ctypes.byref(key), self._tp(witness), self._tp(rs), n, 0, self._tp(pa),
+                                                            self._tp(ia), self._tp(pb), self._tp(ib), self._tp(pc), self._tp(ic), self._tp(sat), self._stream()))
+            return pa, ia, pb, ib, pc, ic, sat
+        w = np.ascontiguousarray(witness, dtype=np.uint64)
+        if m == 0 or w.size % (4 * m):
+            raise ValueError("the witnesses hold no whole number of vectors of %d elements" % m)
+        n = w.size // (4 * m)
+        rs = _np(rs, 8)
+        if rs.shape[0] != n:
+            raise ValueError("rs holds %d pairs for %d witnesses" % (rs.shape[0], n))
+        pa, pb, pc = (np.empty((n, cols), dtype=np.uint64) for cols in (12, 24, 12))
+        ia, ib, ic, sat = (np.empty(n, dtype=np.uint8) for _ in range(4))
+        self._chk(self._lib.zkp_groth16_prove_batch(self._h, ctypes.byref(rec), ctypes.byref(key), _ptr(w), _ptr(rs), n, 0, _ptr(pa), _ptr(ia), _ptr(pb), _ptr(ib),
+                                                    _ptr(pc), _ptr(ic), _ptr(sat)))
+        return pa, ia, pb, ib, pc, ic, sat
+
     def kzg_verify_batch(self, g1, g2, tau_g2, c, z, y, proof, *, inf_c=None, inf_proof=None, rand=None, points_checked=False, vk_checked=False):
         """n KZG openings against one setup as ONE check (zkp_kzg_verify_batch): setup points g1 (12,), g2 / tau_g2 (24,); commitments c
         and proofs (n, 12); points z and values y (n, 4).  True iff the random combination holds, every point is valid (unless

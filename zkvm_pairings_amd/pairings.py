@@ -9,6 +9,8 @@
 Names, argument meaning and the infinity convention follow the reference's types
 (G1Affine{x,y,is_infinity} src/g1.rs:7-11, G2Affine src/g2.rs:8-12, Fp12::one src/fp12.rs:87).
 Every call executes on the GPU through the C ABI; there is no host arithmetic here."""
+import os
+
 import numpy as np
 
 from . import synthetic
@@ -445,6 +447,68 @@ def groth16_verify_each(vk, proofs, inputs, engine=None):
         i1[:, 0], i2[:, 0], i1[:, 3] = ia, ib, ic
     per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 4, i1.reshape(-1), i2.reshape(-1))
     return ok & (np.asarray(per).reshape(-1) != 0)
+
+
+class R1CS:
+    """A rank-one constraint system over the N = 2^log2_n-point domain: three sparse matrices A, B, C of n_rows x m in compressed rows,
+    each a tuple (row_ptr (n_rows + 1) uint32, col (nnz) uint32, val (nnz, 4) uint64, canonical).  Variable 0 is the constant one,
+    variables 1 .. n_inputs are public.  No input-consistency rows are added (include/zkp_prove.h)."""
+
+    def __init__(self, log2_n, n_rows, m, n_inputs, a, b, c):
+        self.log2_n, self.n_rows, self.m, self.n_inputs = int(log2_n), int(n_rows), int(m), int(n_inputs)
+        if self.n_rows > 1 << self.log2_n or self.n_inputs + 1 > self.m:
+            raise ValueError("more rows than the domain holds, or more public inputs than variables")
+        mats = []
+        for row_ptr, col, val in (a, b, c):
+            mats.append((np.ascontiguousarray(row_ptr, dtype=np.uint32).reshape(-1), np.ascontiguousarray(col, dtype=np.uint32).reshape(-1),
+                         np.ascontiguousarray(val, dtype=np.uint64).reshape(-1, 4)))
+        self.a, self.b, self.c = mats
+
+    def matrices(self):
+        """the three matrices as the engine takes them: (n_rows, n_cols, row_ptr, col, val)"""
+        return tuple((self.n_rows, self.m) + x for x in (self.a, self.b, self.c))
+
+
+class Groth16ProvingKey:
+    """A Groth16 proving key as wire arrays, the fields of zkp_groth16_pk: alpha_g1, beta_g1, delta_g1 (12,), beta_g2, delta_g2 (24,),
+    a_query and b_g1_query (m, 12), b_g2_query (m, 24), l_query (m - n_inputs - 1, 12), h_query (N - 1, 12); a_inf, b_g1_inf, b_g2_inf,
+    l_inf: optional infinity bytes of the four per-variable queries.  The points are trusted: check a key once with g1_is_valid /
+    g2_is_valid."""
+    FIELDS = tuple(name for name, _ in PairingEngine._PK_FIELDS)
+
+    def __init__(self, **arrays):
+        unknown = set(arrays) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown proving key fields: %s" % sorted(unknown))
+        for name, w in PairingEngine._PK_FIELDS:
+            x = arrays.get(name)
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1) if w is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, w)
+            setattr(self, name, x)
+
+    def arrays(self):
+        return {name: getattr(self, name) for name in self.FIELDS}
+
+
+def groth16_quotient_batch(r1cs, witnesses, engine=None):
+    """(h (n, N, 4), sat (n,)): the quotient polynomial h = (a b - c) / (X^N - 1) of each witness (n, m, 4) by its N coefficients, and
+    whether the witness satisfies every constraint (zkp_groth16_quotient_batch)."""
+    e = engine or default_engine()
+    return e.groth16_quotient(r1cs.log2_n, r1cs.n_inputs, *r1cs.matrices(), witnesses)
+
+
+def groth16_prove_batch(r1cs, pk, witnesses, rs=None, engine=None):
+    """n proofs of one circuit on the GPU (zkp_groth16_prove_batch) -> ((A (n, 12), B (n, 24), C (n, 12)), (inf_a, inf_b, inf_c), sat):
+    the proofs in the form groth16_verify_batch takes, and sat[j] = 1 iff witness j satisfies the system (the proof of an unsatisfied
+    witness is written too; it does not verify).  rs (n, 2, 4): the blinding scalars r_j, s_j, by default fresh from os.urandom and
+    reduced below r - never a seeded generator; zeros give a deterministic proof without zero knowledge."""
+    e = engine or default_engine()
+    w = np.ascontiguousarray(witnesses, dtype=np.uint64)
+    n = w.size // (4 * r1cs.m) if r1cs.m else 0
+    if rs is None:
+        rs = e.fr_from_wide(np.frombuffer(os.urandom(n * 2 * 64), dtype=np.uint8).reshape(n * 2, 64)) if n else np.zeros((0, 8), dtype=np.uint64)
+    pa, ia, pb, ib, pc, ic, sat = e.groth16_prove(r1cs.log2_n, r1cs.n_inputs, *r1cs.matrices(), pk.arrays(), w, rs)
+    return (pa, pb, pc), (ia, ib, ic), sat
 
 
 class KzgSetup:

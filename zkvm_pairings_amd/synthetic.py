@@ -147,6 +147,104 @@ def groth16_instance(seed, n, n_inputs, bad=(), engine=None):
     return key, proofs, xw
 
 
+def groth16_circuit_secrets(seed, log2_n, n_rows, m, n_inputs, n, row_lengths=None, bad=()):
+    """The part of groth16_circuit_instance that needs no GPU, on Python integers: a random satisfiable constraint system, n witnesses
+    and the trapdoor.  The last n_rows variables are PRODUCT variables: row k has sparse random A and B rows over the variables before
+    its product variable p_k = m - n_rows + k (columns drawn with repetition, so a column may repeat inside a row) and the single C
+    entry 1 at p_k, which each witness sets to a_k b_k.  row_lengths[k]: the entries of row k in A and in B (default 1 .. 3 at
+    random); the first A entries name the constant and the public variables in turn.  Witnesses listed in `bad` get the last product variable off by one.  -> dict: rows_a / rows_b / rows_c (per row, a list
+    of (column, value)), z (n lists of m integers), tau alpha beta gamma delta, u_tau v_tau w_tau (the QAP polynomials of every
+    variable at tau), log2_n n_rows m n_inputs."""
+    import random
+    r, big_n, l = R_ORDER, 1 << int(log2_n), int(n_inputs)
+    free = m - n_rows
+    if n_rows > big_n or free < 1 or l + 1 > m:
+        raise ValueError("n_rows <= N, m > n_rows and n_inputs < m are needed")
+    rng = random.Random(seed)
+    rows_a, rows_b, rows_c = [], [], []
+    need = list(range(min(free, l + 1)))[::-1]   # every public variable takes part (the first A entries): a verifying key has no infinite IC_i
+    for k in range(n_rows):
+        cnt = rng.randrange(1, 4) if row_lengths is None else int(row_lengths[k])
+        rows_a.append([(need.pop() if need else rng.randrange(free + k), rng.randrange(1, r)) for _ in range(cnt)])
+        rows_b.append([(rng.randrange(free + k), rng.randrange(1, r)) for _ in range(cnt)])
+        rows_c.append([(free + k, 1)])
+    dot = lambda row, z: sum(v * z[c] for c, v in row) % r
+    bad = set(int(j) for j in bad)
+    if bad and not n_rows:
+        raise ValueError("no constraint to violate")
+    zs = []
+    for j in range(n):
+        z = [1] + [rng.randrange(r) for _ in range(free - 1)] + [0] * n_rows
+        for k in range(n_rows):
+            z[free + k] = dot(rows_a[k], z) * dot(rows_b[k], z) % r
+        if j in bad:
+            z[m - 1] = (z[m - 1] + 1) % r
+        zs.append(z)
+    w = fr_root_of_unity(log2_n)
+    while True:
+        tau, alpha, beta, gamma, delta = (rng.randrange(1, r) for _ in range(5))
+        if pow(tau, big_n, r) != 1:
+            break
+    scale = (pow(tau, big_n, r) - 1) * pow(big_n, -1, r) % r
+    u, v, ww = [0] * m, [0] * m, [0] * m
+    wk = 1
+    for k in range(n_rows):
+        lk = scale * wk % r * pow(tau - wk, -1, r) % r          # l_k(tau)
+        for dst, row in ((u, rows_a[k]), (v, rows_b[k]), (ww, rows_c[k])):
+            for c, val in row:
+                dst[c] = (dst[c] + val * lk) % r
+        wk = wk * w % r
+    return dict(rows_a=rows_a, rows_b=rows_b, rows_c=rows_c, z=zs, tau=tau, alpha=alpha, beta=beta, gamma=gamma, delta=delta, u_tau=u, v_tau=v, w_tau=ww,
+                log2_n=int(log2_n), n_rows=int(n_rows), m=int(m), n_inputs=l)
+
+
+def csr_arrays(rows):
+    """per row a list of (column, value) -> (row_ptr uint32, col uint32, val (nnz, 4) uint64)"""
+    row_ptr = np.zeros(len(rows) + 1, dtype=np.uint32)
+    row_ptr[1:] = np.cumsum([len(x) for x in rows], dtype=np.uint64)
+    col = np.array([c for x in rows for c, _ in x], dtype=np.uint32)
+    vals = [v for x in rows for _, v in x]
+    return row_ptr, col, _rows(vals) if vals else np.zeros((0, 4), dtype=np.uint64)
+
+
+def groth16_circuit_instance(seed, log2_n, n_rows, m, n_inputs, n, row_lengths=None, bad=(), engine=None):
+    """A synthetic circuit with its Groth16 keys and n witnesses -> (r1cs, pk, vk, witnesses (n, m, 4) uint64, secrets): the constraint
+    system, witnesses and trapdoor of groth16_circuit_secrets (returned as `secrets`), the proving key
+        a_query_i = [u_i(tau)] g1, b_g1_query_i = [v_i(tau)] g1, b_g2_query_i = [v_i(tau)] g2,
+        l_query_i = [(beta u_i + alpha v_i + w_i)(tau) / delta] g1 (i > n_inputs), h_query_i = [tau^i (tau^N - 1) / delta] g1 (i < N - 1)
+    with its infinite query entries flagged (a variable absent from A or B), and the verifying key with
+    IC_i = [(beta u_i + alpha v_i + w_i)(tau) / gamma] g1.  The points come through the engine's g1_mul / g2_mul."""
+    from .pairings import R1CS, Groth16ProvingKey, Groth16VerifyingKey, default_engine
+    if engine is None:
+        engine = default_engine()
+    s = groth16_circuit_secrets(seed, log2_n, n_rows, m, n_inputs, n, row_lengths, bad)
+    r, big_n, l = R_ORDER, 1 << int(log2_n), int(n_inputs)
+    tau, alpha, beta, gamma, delta = s["tau"], s["alpha"], s["beta"], s["gamma"], s["delta"]
+    u, v, w = s["u_tau"], s["v_tau"], s["w_tau"]
+    dinv, ginv = pow(delta, -1, r), pow(gamma, -1, r)
+    comb = [(beta * u[i] + alpha * v[i] + w[i]) % r for i in range(m)]
+    t_tau = (pow(tau, big_n, r) - 1) % r
+    lq = [comb[i] * dinv % r for i in range(l + 1, m)]
+    hq = [pow(tau, i, r) * t_tau % r * dinv % r for i in range(big_n - 1)]
+    ic = [comb[i] * ginv % r for i in range(l + 1)]
+    g1e = [alpha, beta, delta] + u + v + lq + hq + ic
+    g1s, g1i = engine.g1_mul(G1_GENERATOR, _rows(g1e))
+    g2s, g2i = engine.g2_mul(G2_GENERATOR, _rows([beta, gamma, delta] + v))
+    at = [3]
+    for cnt in (m, m, len(lq), len(hq), len(ic)):
+        at.append(at[-1] + cnt)
+    cut = lambda i: (g1s[at[i]:at[i + 1]].copy(), np.ascontiguousarray(g1i[at[i]:at[i + 1]], dtype=np.uint8))
+    (aq, ai), (bq, bi), (lqp, li), (hqp, hi), (icp, ici) = (cut(i) for i in range(5))
+    if hi.any() or ici.any():
+        raise ValueError("the trapdoor gives an infinite h_query or IC entry; take another seed")
+    pk = Groth16ProvingKey(alpha_g1=g1s[0], beta_g1=g1s[1], delta_g1=g1s[2], beta_g2=g2s[0], delta_g2=g2s[2], a_query=aq, a_inf=ai, b_g1_query=bq, b_g1_inf=bi,
+                           b_g2_query=g2s[3:].copy(), b_g2_inf=np.ascontiguousarray(g2i[3:], dtype=np.uint8), l_query=lqp, l_inf=li, h_query=hqp)
+    vk = Groth16VerifyingKey(g1s[0].copy(), g2s[0].copy(), g2s[1].copy(), g2s[2].copy(), icp)
+    r1cs = R1CS(log2_n, n_rows, m, l, csr_arrays(s["rows_a"]), csr_arrays(s["rows_b"]), csr_arrays(s["rows_c"]))
+    wit = _rows([x for z in s["z"] for x in z]).reshape(n, m, 4) if n else np.zeros((0, m, 4), dtype=np.uint64)
+    return r1cs, pk, vk, wit, s
+
+
 FR_GENERATOR, FR_S = 7, 32      # r - 1 = 2^32 * odd, 7 generates Fr* (reference src/common.rs)
 
 
