@@ -10,6 +10,7 @@ use core::ptr;
 
 pub mod poly;
 pub mod prove;
+pub mod fk20;
 
 #[repr(C)]
 pub struct ZkpCtx {

@@ -203,6 +203,16 @@ PROVE_SIGNATURES = {
                                             c_vp]),
 }
 
+# name -> (restype, argtypes); MUST list every symbol include/zkp_fk20.h declares (the fourth header of the same library)
+FK20_SIGNATURES = {
+    "zkp_g1_ntt_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp]),
+    "zkp_g1_ntt_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp]),
+    "zkp_kzg_fk20_setup": (c_int, [c_vp, c_vp, ctypes.c_uint, c_vp, c_vp]),
+    "zkp_kzg_fk20_setup_dev": (c_int, [c_vp, c_vp, ctypes.c_uint, c_vp, c_vp, c_vp]),
+    "zkp_kzg_fk20_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp]),
+    "zkp_kzg_fk20_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -229,7 +239,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -1851,6 +1851,185 @@ __global__ void __launch_bounds__(64, 2) k_g1_mul_endo28(const uint64_t* base, c
     if (out_inf) out_inf[i] = pinf ? 1 : 0;
 }
 
+// =============================================================================== the G1 NTT and the FK20 scalar products (zkp_fk20.hip drives
+// them; zkp_fk20_plan.hpp holds every index).  One lane per butterfly, Jacobian records (jrec_*) in a workspace between the stages, every
+// stage in place: a lane reads and writes the same two records.
+namespace fk = zkp::fk20;
+
+// p <- [a + b z^2] p for a JACOBIAN p in G1 and a, b of 128 bits: k_g1_mul_endo28's joint double-and-add, 128 doublings, with the table
+// Q = p (LDS slots 0..2), phi'(Q) = (beta X, -Y, Z) (not stored: one product at the load) and T = Q + phi'(Q) (slots 3..5).  Every addition
+// is the full jac_add: Q may be infinite, T is infinite when phi'(Q) = -Q, and the accumulator meets +-Q on ordinary inputs.
+__device__ __forceinline__ void jac_mul_split(const F1& f, JacP& p, int4* park, int lane, uint64_t a_lo, uint64_t a_hi, uint64_t b_lo, uint64_t b_hi) {
+    jac_park(park, lane, 0, p);
+    jac_add(f, p, [&](int v) -> Fp28 {
+        const Fp28 q = valid_unpark(park, lane, v);
+        return v == 0 ? f.mul(q, f_const(K28_BETA)) : v == 1 ? c_neg(q) : q;
+    });
+    jac_park(park, lane, 3, p);
+    jac_set_inf(f, p);
+#pragma unroll 1
+    for (int h = 1; h >= 0; h--) {
+        const uint64_t a = h ? a_hi : a_lo, b = h ? b_hi : b_lo;
+#pragma unroll 1
+        for (int bit = 63; bit >= 0; bit--) {
+            jac_dbl(f, p);
+            const int sel = (int)((a >> bit) & 1) | (int)((b >> bit) & 1) << 1;   // 1: Q, 2: phi'(Q), 3: T
+            if (sel)
+                jac_add(f, p, [&](int v) -> Fp28 {
+                    if (sel == 3) return valid_unpark(park, lane, 3 + v);
+                    const Fp28 q = valid_unpark(park, lane, v);
+                    if (sel == 1 || v == 2) return q;
+                    return v == 0 ? f.mul(q, f_const(K28_BETA)) : c_neg(q);
+                });
+        }
+    }
+}
+
+__device__ __forceinline__ JacP jrec_get(const int4* rec, uint32_t item) {
+    JacP p;
+    p.x = jrec_ld<1>(rec, item, 0, 0);
+    p.y = jrec_ld<1>(rec, item, 1, 0);
+    p.z = jrec_ld<1>(rec, item, 2, 0);
+    return p;
+}
+
+// The stage on bit 0 (twiddle one, no product): A + B and A - B of the two inputs of a lane, read where fk::first_source says - the
+// caller's wire points and flags in its order, the FK20 setup vector, or records of the workspace - and stored as records.  k = 0: a copy.
+template <int MODE>
+__global__ void __launch_bounds__(64, 2) k_g1ntt_first(const uint64_t* in, const uint8_t* inf, int4* rec, fk::First a) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_lane) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[3 * 4 * 64];   // B: affine (slots 0, 1) from the wire, Jacobian from records
+    const uint32_t k = a.at.k, j = k ? t >> (k - 1) : t, e0 = k ? (t & fk::low_mask(k - 1)) << 1 : 0;
+    const int64_t sa = fk::first_source(a, j, e0), sb = k ? fk::first_source(a, j, e0 + 1) : fk::SRC_INFINITY;
+    const uint32_t r0 = fk::span_record(a.at, j, e0);
+    JacP p;
+    bool b_inf;
+    if (MODE == fk::SRC_REC) {
+        p = jrec_get(rec, (uint32_t)sa);
+        b_inf = sb == fk::SRC_INFINITY;
+        if (!b_inf) jrec_park<1>(park, lane, rec, (uint32_t)sb, 0);
+    } else {
+        jac_set_inf(f, p);
+        if (sa != fk::SRC_INFINITY && !(inf && inf[sa])) {
+            fp28_from_wire(p.x, in + 12 * (size_t)sa);
+            fp28_from_wire(p.y, in + 12 * (size_t)sa + 6);
+            p.z = f.one();
+        }
+        b_inf = sb == fk::SRC_INFINITY || (inf && inf[sb]);
+        if (!b_inf) {
+            Fp28 qx, qy;
+            fp28_from_wire(qx, in + 12 * (size_t)sb);
+            fp28_from_wire(qy, in + 12 * (size_t)sb + 6);
+            valid_park(park, lane, 0, qx);
+            valid_park(park, lane, 1, qy);
+        }
+    }
+    if (!k) { jrec_st<1>(rec, r0, 0, p); return; }
+    if (b_inf) {           // A + inf = A - inf = A
+        jrec_st<1>(rec, r0, 0, p);
+        jrec_st<1>(rec, r0 + 1, 0, p);
+        return;
+    }
+    JacP d = p;
+    if (MODE == fk::SRC_REC) {
+        jac_add(f, d, [&](int v) -> Fp28 { const Fp28 q = valid_unpark(park, lane, v); return v == 1 ? c_neg(q) : q; });
+        jrec_st<1>(rec, r0 + 1, 0, d);
+        p = jrec_get(rec, (uint32_t)sa);
+        jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    } else {
+        jac_madd(f, d, [&](int v) -> Fp28 { const Fp28 q = valid_unpark(park, lane, v); return v == 1 ? c_neg(q) : q; });
+        jrec_st<1>(rec, r0 + 1, 0, d);
+        jac_set_inf(f, p);
+        if (sa != fk::SRC_INFINITY && !(inf && inf[sa])) {
+            fp28_from_wire(p.x, in + 12 * (size_t)sa);
+            fp28_from_wire(p.y, in + 12 * (size_t)sa + 6);
+            p.z = f.one();
+        }
+        jac_madd(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    }
+    jrec_st<1>(rec, r0, 0, p);
+}
+
+// A twiddled stage: T = [w^t] B through the split twiddle of the context's table, then A - T and A + T, both by the full addition with T
+// in LDS.  B's record takes A - T before A's takes A + T: A is read twice, never kept across the products.
+__global__ void __launch_bounds__(64, 2) k_g1ntt_stage(int4* rec, const uint64_t* __restrict__ split, fk::Stage a) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_bfly) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[6 * 4 * 64];
+    uint32_t r0, r1, tw;
+    fk::stage_lane(a, t, &r0, &r1, &tw);
+    const uint64_t a_lo = split[4 * (size_t)tw], a_hi = split[4 * (size_t)tw + 1], b_lo = split[4 * (size_t)tw + 2], b_hi = split[4 * (size_t)tw + 3];
+    JacP p = jrec_get(rec, r1);
+    jac_mul_split(f, p, park, lane, a_lo, a_hi, b_lo, b_hi);
+    jac_park(park, lane, 0, p);
+    p = jrec_get(rec, r0);
+    jac_add(f, p, [&](int v) -> Fp28 { const Fp28 q = valid_unpark(park, lane, v); return v == 1 ? c_neg(q) : q; });
+    jrec_st<1>(rec, r1, 0, p);
+    p = jrec_get(rec, r0);
+    jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    jrec_st<1>(rec, r0, 0, p);
+}
+
+// the inverse transform's [N^-1]: one more split multiplication of every record, in place
+__global__ void __launch_bounds__(64, 2) k_g1ntt_scale(int4* rec, fk::Out a, uint64_t a_lo, uint64_t a_hi, uint64_t b_lo, uint64_t b_hi) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_pt) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[6 * 4 * 64];
+    uint32_t r;
+    uint64_t slot;
+    fk::out_lane(a, t, &r, &slot);
+    JacP p = jrec_get(rec, r);
+    jac_mul_split(f, p, park, lane, a_lo, a_hi, b_lo, b_hi);
+    jrec_st<1>(rec, r, 0, p);
+}
+// record -> wire point and flag, in the order the caller asked for: one inversion per output
+__global__ void __launch_bounds__(64, 2) k_g1ntt_out(const int4* rec, uint64_t* out, uint8_t* out_inf, fk::Out a) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.n_pt) return;
+    F1 f{0};
+    uint32_t r;
+    uint64_t slot;
+    fk::out_lane(a, t, &r, &slot);
+    const JacP p = jrec_get(rec, r);
+    Fp28 ax, ay;
+    const bool pinf = jac_affine(f, p, ax, ay);
+    fp28_to_wire(out + 12 * slot, ax);
+    fp28_to_wire(out + 12 * slot + 6, ay);
+    out_inf[slot] = pinf ? 1 : 0;
+}
+
+// FK20's 2 N products per polynomial: record t <- [fr[t]] setup[bitrev(t mod 2 N)].  The scalars are the size-2N Fr transform in
+// bit-reversed order, so record t holds what the decimation in time wants at position t.  k_g1_mul28's chain on an affine base; no
+// conversion back: the result stays Jacobian.  An infinite setup point gives the identity.
+__global__ void __launch_bounds__(64, 2) k_fk20_mul(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, uint32_t n_pt, uint32_t k1,
+                                                    int4* rec) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_pt) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[2 * 4 * 64];
+    const uint32_t src = fk::bitrev(t & fk::low_mask(k1), k1);
+    JacP p;
+    jac_set_inf(f, p);
+    if (!(setup_inf && setup_inf[src])) {
+        Fp28 x, y;
+        fp28_from_wire(x, setup + 12 * (size_t)src);
+        fp28_from_wire(y, setup + 12 * (size_t)src + 6);
+        valid_park(park, lane, 0, x);
+        valid_park(park, lane, 1, y);
+        const uint64_t sk[4] = {sc[4 * (size_t)t], sc[4 * (size_t)t + 1], sc[4 * (size_t)t + 2], sc[4 * (size_t)t + 3]};
+        jac_mul(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); }, sk, 4);
+    }
+    jrec_st<1>(rec, t, 0, p);
+}
+
 // ---- MSM 1: n wire Fp elements -> Montgomery records (the points' coordinates, converted once per pass)
 __global__ void __launch_bounds__(256) k_msm_points(const uint64_t* w, uint32_t n_fp, int4* rec) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -2825,6 +3004,33 @@ hipError_t msm_final(int which, const void* wsums, uint32_t segs, uint32_t windo
     return hipGetLastError();
 }
 
+hipError_t g1ntt_first(const uint64_t* in, const uint8_t* inf, void* rec, const fk20::First& a, hipStream_t s) {
+    if (!a.n_lane) return hipSuccess;
+    const dim3 g(fk20::grid(a.n_lane)), b(64);
+    if (a.mode == fk20::SRC_REC) hipLaunchKernelGGL(k_g1ntt_first<fk20::SRC_REC>, g, b, 0, s, in, inf, (int4*)rec, a);
+    else hipLaunchKernelGGL(k_g1ntt_first<fk20::SRC_WIRE>, g, b, 0, s, in, inf, (int4*)rec, a);
+    return hipGetLastError();
+}
+hipError_t g1ntt_stage(void* rec, const uint64_t* split, const fk20::Stage& a, hipStream_t s) {
+    if (!a.n_bfly) return hipSuccess;
+    hipLaunchKernelGGL(k_g1ntt_stage, dim3(fk20::grid(a.n_bfly)), dim3(64), 0, s, (int4*)rec, split, a);
+    return hipGetLastError();
+}
+hipError_t g1ntt_out(void* rec, uint64_t* out, uint8_t* out_inf, const fk20::Out& a, const uint64_t* ab, hipStream_t s) {
+    if (!a.n_pt) return hipSuccess;
+    if (a.scale) {
+        hipLaunchKernelGGL(k_g1ntt_scale, dim3(fk20::grid(a.n_pt)), dim3(64), 0, s, (int4*)rec, a, ab[0], ab[1], ab[2], ab[3]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_g1ntt_out, dim3(fk20::grid(a.n_pt)), dim3(64), 0, s, (const int4*)rec, out, out_inf, a);
+    return hipGetLastError();
+}
+hipError_t fk20_mul(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, uint32_t n_pt, uint32_t k1, void* rec, hipStream_t s) {
+    if (!n_pt) return hipSuccess;
+    hipLaunchKernelGGL(k_fk20_mul, dim3(fk20::grid(n_pt)), dim3(64), 0, s, setup, setup_inf, sc, n_pt, k1, (int4*)rec);
+    return hipGetLastError();
+}
 hipError_t coop_fp28_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, hipStream_t s) {
     if (!n) return hipSuccess;
     if (op < 0 || op > 5) return hipErrorInvalidValue;

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "zkp_fk20_plan.hpp"
+
 namespace zkp {
 
 struct CoopState {
@@ -43,6 +45,12 @@ hipError_t msm_accum(int which, bool level0, const uint32_t* keys, const uint32_
                      uint32_t* okeys, void* oj, hipStream_t s);
 hipError_t msm_reduce(int which, const void* buckets, uint32_t n_sums, uint32_t split, uint32_t chunk, uint32_t* okeys, void* oj, hipStream_t s);
 hipError_t msm_final(int which, const void* wsums, uint32_t segs, uint32_t windows, uint32_t c, uint64_t* out, uint8_t* out_inf, hipStream_t s);
+// the G1 NTT's and FK20's group launches (zkp_coop.hip, "the G1 NTT"; driven by zkp_fk20.hip, every index from zkp_fk20_plan.hpp).  rec: the
+// Jacobian records; split: the context's split twiddles (a_lo, a_hi, b_lo, b_hi per entry); ab: the four words of the scaling's split (a.scale: one more launch)
+hipError_t g1ntt_first(const uint64_t* in, const uint8_t* inf, void* rec, const fk20::First& a, hipStream_t s);
+hipError_t g1ntt_stage(void* rec, const uint64_t* split, const fk20::Stage& a, hipStream_t s);
+hipError_t g1ntt_out(void* rec, uint64_t* out, uint8_t* out_inf, const fk20::Out& a, const uint64_t* ab, hipStream_t s);
+hipError_t fk20_mul(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, uint32_t n_pt, uint32_t k1, void* rec, hipStream_t s);
 // one tower operation per record (zkp_tower_op_batch); ab = n a-records followed by n b-records
 hipError_t coop_tower_op(CoopState* st, int op, const uint64_t* ab, size_t n, uint32_t repeat, uint64_t* out, hipStream_t s);
 hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hipEvent_t e0, hipEvent_t e1, float* ms);

@@ -17,6 +17,7 @@
 #include "../../include/zkp_pairings.h"
 #include "../../include/zkp_poly.h"
 #include "../../include/zkp_prove.h"
+#include "../../include/zkp_fk20.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -32,6 +33,8 @@
 #include "zkp_poly_plan.hpp"
 #include "zkp_prove.hpp"
 #include "zkp_prove_plan.hpp"
+#include "zkp_fk20.hpp"
+#include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
 using namespace zkp;
@@ -473,6 +476,10 @@ struct zkp_ctx {
     uint32_t* poly_coset = nullptr;   // the NTT's coset tables (zkp_poly_plan.hpp: COSET_BYTES), built at the first coset call
     void* prove_ws = nullptr;   // grow-only workspace of the QAP quotient and the Groth16 prover (zkp_prove_plan.hpp layout)
     size_t prove_cap = 0;
+    void* fk20_ws = nullptr;    // grow-only workspace of the G1 NTT and of FK20 (zkp_fk20_plan.hpp: Jacobian records, FK20's field elements)
+    size_t fk20_cap = 0;
+    uint64_t* g1ntt_split = nullptr;   // the split twiddles of kzg_dom, entry for entry (-1: none yet): rebuilt when that table grows
+    int g1ntt_split_log2 = -1;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -899,6 +906,8 @@ void zkp_free(zkp_ctx* c) {
     if (c->prove_ws) (void)hipFree(c->prove_ws);
     if (c->kzg_dom) (void)hipFree(c->kzg_dom);
     if (c->poly_coset) (void)hipFree(c->poly_coset);
+    if (c->fk20_ws) (void)hipFree(c->fk20_ws);
+    if (c->g1ntt_split) (void)hipFree(c->g1ntt_split);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
             if (c->hs[i].buf[j]) (void)hipFree(c->hs[i].buf[j]);
@@ -1610,6 +1619,30 @@ int grow_prove(zkp_ctx* c, size_t bytes, void** ws) {
         c->prove_cap = bytes;
     }
     *ws = c->prove_ws;
+    return ZKP_OK;
+}
+int grow_fk20(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->fk20_cap) {
+        if (c->fk20_ws) { HIPCHK(c, hipFree(c->fk20_ws)); c->fk20_ws = nullptr; c->fk20_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->fk20_ws, bytes));
+        zkp_dbg_alloc("ctx.fk20", c->fk20_ws, bytes);
+        c->fk20_cap = bytes;
+    }
+    *ws = c->fk20_ws;
+    return ZKP_OK;
+}
+int g1ntt_tables(zkp_ctx* c, unsigned log2_n, const uint32_t** domain, const uint64_t** split, unsigned* table_log2, hipStream_t s) {
+    if (int rc = kzg_domain(c, log2_n, domain, table_log2, s)) return rc;
+    if (c->g1ntt_split_log2 != (int)*table_log2) {
+        if (c->g1ntt_split) { HIPCHK(c, hipFree(c->g1ntt_split)); c->g1ntt_split = nullptr; c->g1ntt_split_log2 = -1; }
+        HIPCHK(c, hipMalloc((void**)&c->g1ntt_split, zkp::fk20::split_table_bytes(*table_log2)));
+        zkp_dbg_alloc("ctx.g1ntt_split", c->g1ntt_split, zkp::fk20::split_table_bytes(*table_log2));
+        const hipError_t e = zkp::g1ntt_split_build(*domain, *table_log2, c->g1ntt_split, s);
+        if (e != hipSuccess) { (void)hipFree(c->g1ntt_split); c->g1ntt_split = nullptr; }
+        HIPCHK(c, e);
+        c->g1ntt_split_log2 = (int)*table_log2;
+    }
+    *split = c->g1ntt_split;
     return ZKP_OK;
 }
 int* validation_word(zkp_ctx* c) { return c->d_flag + 2; }
@@ -2703,6 +2736,104 @@ int zkp_groth16_prove_batch(zkp_ctx* c, const zkp_r1cs* r, const zkp_groth16_pk*
         (rc = zkp::groth16_prove_dev(c, &d, &dk, (const uint64_t*)dw, (const uint64_t*)drs, n, (uint64_t*)(dout + out_off[0]), (uint8_t*)(dout + out_off[1]),
                                      (uint64_t*)(dout + out_off[2]), (uint8_t*)(dout + out_off[3]), (uint64_t*)(dout + out_off[4]),
                                      (uint8_t*)(dout + out_off[5]), (uint8_t*)(dout + out_off[6]), c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the G1 NTT and the FK20 proofs (zkp_fk20.hip, include/zkp_fk20.h)
+namespace {
+bool g1_ntt_args_bad(const zkp_ctx* c, const void* points, size_t n_vec, unsigned log2_n, int flags, const void* out, const void* out_inf) {
+    return !c || zkp::fk20::g1ntt_args_bad(n_vec, log2_n, flags) || (n_vec && (!points || !out || !out_inf));
+}
+bool fk20_setup_args_bad(const zkp_ctx* c, const void* monomial, unsigned log2_n, const void* out, const void* out_inf) {
+    return !c || zkp::fk20::setup_args_bad(log2_n) || !monomial || !out || !out_inf;
+}
+bool fk20_args_bad(const zkp_ctx* c, const void* setup, const void* coeffs, size_t n, unsigned log2_n, int flags, const void* proof, const void* inf) {
+    return !c || zkp::fk20::fk20_args_bad(n, log2_n, flags) || (n && (!setup || !coeffs || !proof || !inf));
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_g1_ntt_batch_dev(zkp_ctx* c, const void* points, const void* inf, size_t n_vec, unsigned log2_n, int flags, void* out, void* out_inf, void* stream) {
+    if (g1_ntt_args_bad(c, points, n_vec, log2_n, flags, out, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n_vec) return ZKP_OK;
+    if (int rc = validate_on_stream(c, points, (n_vec << log2_n) * 2, S(stream))) return rc;
+    return zkp::g1_ntt_dev(c, (const uint64_t*)points, (const uint8_t*)inf, n_vec, log2_n, flags, (uint64_t*)out, (uint8_t*)out_inf, S(stream));
+}
+// the points in slot 0, their flags in slot 1, the two outputs one after the other in slot 4, then the _dev flavour's driver
+int zkp_g1_ntt_batch(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, size_t n_vec, unsigned log2_n, int flags, uint64_t* out, uint8_t* out_inf) {
+    if (g1_ntt_args_bad(c, points, n_vec, log2_n, flags, out, out_inf)) return ZKP_ERR_ARG;
+    if (!n_vec) return ZKP_OK;
+    const size_t n = n_vec << log2_n, off_i = zkp::fk20::up256(n * 96);
+    HostIO io(c);
+    const void* dp = io.in(0, points, n * 96);
+    const void* di = io.in(1, inf, n);
+    char* dout = (char*)io.slot(4, off_i + n);
+    if (dout) {
+        io.get(out, dout, n * 96);
+        io.get(out_inf, dout + off_i, n);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dp, n * 2)) ||
+        (rc = zkp::g1_ntt_dev(c, (const uint64_t*)dp, (const uint8_t*)di, n_vec, log2_n, flags, (uint64_t*)dout, (uint8_t*)(dout + off_i), c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_kzg_fk20_setup_dev(zkp_ctx* c, const void* monomial_g1, unsigned log2_n, void* out, void* out_inf, void* stream) {
+    if (fk20_setup_args_bad(c, monomial_g1, log2_n, out, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, monomial_g1, ((size_t)1 << log2_n) * 2, S(stream))) return rc;
+    return zkp::fk20_setup_dev(c, (const uint64_t*)monomial_g1, log2_n, (uint64_t*)out, (uint8_t*)out_inf, S(stream));
+}
+int zkp_kzg_fk20_setup(zkp_ctx* c, const uint64_t* monomial_g1, unsigned log2_n, uint64_t* out, uint8_t* out_inf) {
+    if (fk20_setup_args_bad(c, monomial_g1, log2_n, out, out_inf)) return ZKP_ERR_ARG;
+    const size_t N = (size_t)1 << log2_n, off_i = zkp::fk20::up256(2 * N * 96);
+    HostIO io(c);
+    const void* dm = io.in(0, monomial_g1, N * 96);
+    char* dout = (char*)io.slot(4, off_i + 2 * N);
+    if (dout) {
+        io.get(out, dout, 2 * N * 96);
+        io.get(out_inf, dout + off_i, 2 * N);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dm, N * 2)) ||
+        (rc = zkp::fk20_setup_dev(c, (const uint64_t*)dm, log2_n, (uint64_t*)dout, (uint8_t*)(dout + off_i), c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_kzg_fk20_batch_dev(zkp_ctx* c, const void* fk20_setup, const void* fk20_setup_inf, const void* coeffs, size_t n, unsigned log2_n, int flags,
+                           void* out_proof, void* out_inf, void* stream) {
+    if (fk20_args_bad(c, fk20_setup, coeffs, n, log2_n, flags, out_proof, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = validate_on_stream(c, fk20_setup, ((size_t)2 << log2_n) * 2, S(stream))) || (rc = validate_fr_on_stream(c, coeffs, n << log2_n, S(stream)))) return rc;
+    return zkp::fk20_dev(c, (const uint64_t*)fk20_setup, (const uint8_t*)fk20_setup_inf, (const uint64_t*)coeffs, n, log2_n, flags, (uint64_t*)out_proof,
+                         (uint8_t*)out_inf, S(stream));
+}
+// the setup in slot 0, its flags in slot 1, the coefficients in slot 2, the two outputs one after the other in slot 4
+int zkp_kzg_fk20_batch(zkp_ctx* c, const uint64_t* fk20_setup, const uint8_t* fk20_setup_inf, const uint64_t* coeffs, size_t n, unsigned log2_n, int flags,
+                       uint64_t* out_proof, uint8_t* out_inf) {
+    if (fk20_args_bad(c, fk20_setup, coeffs, n, log2_n, flags, out_proof, out_inf)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t N = (size_t)1 << log2_n, off_i = zkp::fk20::up256(n * N * 96);
+    HostIO io(c);
+    const void* ds = io.in(0, fk20_setup, 2 * N * 96);
+    const void* dsi = io.in(1, fk20_setup_inf, 2 * N);
+    const void* dc = io.in(2, coeffs, n * N * 32);
+    char* dout = (char*)io.slot(4, off_i + n * N);
+    if (dout) {
+        io.get(out_proof, dout, n * N * 96);
+        io.get(out_inf, dout + off_i, n * N);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)ds, 2 * N * 2)) || (rc = validate_fr_dev(c, dc, n * N)) ||
+        (rc = zkp::fk20_dev(c, (const uint64_t*)ds, (const uint8_t*)dsi, (const uint64_t*)dc, n, log2_n, flags, (uint64_t*)dout, (uint8_t*)(dout + off_i),
+                            c->stream)))
         return rc;
     return io.finish();
 }

@@ -711,6 +711,100 @@ class PairingEngine:
         self._chk(self._lib.zkp_kzg_open_batch(self._h, _ptr(setup), _ptr(evals), _ptr(z), n, log2_n, flags, _ptr(y), _ptr(proof), _ptr(inf)))
         return y, proof, inf
 
+    # ------------------------------------------------------------------ the G1 NTT and FK20 (include/zkp_fk20.h)
+    def g1_ntt(self, points, log2_n, inverse=False, bitrev=False, inf=None, out=None, out_inf=None):
+        """The NTT of n_vec vectors of N = 2^log2_n G1 points each (zkp_g1_ntt_batch): out[j][i] = sum_k [w^(i k)] points[j][k] with the
+        root of fr_ntt; inverse and bitrev mean what they mean there.  points (n_vec N, 12), inf optional flags (n_vec N,).
+        -> (out (n_vec N, 12), out_inf (n_vec N,)); the identity is (0, 1) with its flag set.  The points are trusted (on the curve, in
+        the subgroup).  Resident torch tensors stay on the GPU (the current stream); out=points, out_inf=inf transforms in place."""
+        log2_n = int(log2_n)
+        flags = (_lib.NTT_INVERSE if inverse else 0) | (_lib.NTT_BITREV if bitrev else 0)
+        if log2_n < 0 or log2_n > 63:
+            raise ValueError("log2_n out of range")
+        if _is_torch(points):
+            import torch
+            self._t_check(points, 12, "points")
+            n = points.numel() // 12
+            if n % (1 << log2_n):
+                raise ValueError("%d points: no whole number of vectors of 2^%d" % (n, log2_n))
+            self._t_bytes(inf, n, "inf")
+            if out is None:
+                out = torch.empty((n, 12), dtype=points.dtype, device=points.device)
+            if out_inf is None:
+                out_inf = torch.empty(n, dtype=torch.uint8, device=points.device)
+            self._t_check(out, 12, "out", rows=n), self._t_bytes(out_inf, n, "out_inf")
+            self._chk(self._lib.zkp_g1_ntt_batch_dev(self._h, self._tp(points), self._tp(inf), n >> log2_n, log2_n, flags, self._tp(out), self._tp(out_inf),
+                                                     self._stream()))
+            return out, out_inf
+        pts = _np(points, 12)
+        n = pts.shape[0]
+        if n % (1 << log2_n):
+            raise ValueError("%d points: no whole number of vectors of 2^%d" % (n, log2_n))
+        inf = _flags(inf, n, "g1_ntt")
+        if out is None:
+            out = np.empty((n, 12), dtype=np.uint64)
+        if out_inf is None:
+            out_inf = np.empty(n, dtype=np.uint8)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous and out.size == n * 12 and
+                isinstance(out_inf, np.ndarray) and out_inf.dtype == np.uint8 and out_inf.flags.c_contiguous and out_inf.size == n):
+            raise ValueError("out / out_inf must be C-contiguous uint64 / uint8 arrays of the input's size")
+        self._chk(self._lib.zkp_g1_ntt_batch(self._h, _ptr(pts), _ptr(inf), n >> log2_n, log2_n, flags, _ptr(out), _ptr(out_inf)))
+        return out, out_inf
+
+    def kzg_fk20_setup(self, monomial_g1, log2_n):
+        """(setup (2N, 12), inf (2N,)) for kzg_fk20, from the monomial setup monomial_g1[k] = [tau^k] g1, k < N = 2^log2_n
+        (zkp_kzg_fk20_setup): computed once per setup.  The points are trusted.  A resident torch tensor stays on the GPU."""
+        log2_n = int(log2_n)
+        if log2_n < 0 or log2_n > 63:
+            raise ValueError("log2_n out of range")
+        big_n = 1 << log2_n
+        if _is_torch(monomial_g1):
+            import torch
+            self._t_check(monomial_g1, 12, "monomial_g1", rows=big_n)
+            out = torch.empty((2 * big_n, 12), dtype=monomial_g1.dtype, device=monomial_g1.device)
+            out_inf = torch.empty(2 * big_n, dtype=torch.uint8, device=monomial_g1.device)
+            self._chk(self._lib.zkp_kzg_fk20_setup_dev(self._h, self._tp(monomial_g1), log2_n, self._tp(out), self._tp(out_inf), self._stream()))
+            return out, out_inf
+        mono = _np(monomial_g1, 12)
+        if mono.shape[0] != big_n:
+            raise ValueError("the monomial setup holds %d points for polynomials of 2^%d" % (mono.shape[0], log2_n))
+        out, out_inf = np.empty((2 * big_n, 12), dtype=np.uint64), np.empty(2 * big_n, dtype=np.uint8)
+        self._chk(self._lib.zkp_kzg_fk20_setup(self._h, _ptr(mono), log2_n, _ptr(out), _ptr(out_inf)))
+        return out, out_inf
+
+    def kzg_fk20(self, fk20_setup, fk20_setup_inf, coeffs, log2_n, bitrev=False):
+        """The KZG proofs of n polynomials at ALL N = 2^log2_n roots of unity (zkp_kzg_fk20_batch): coeffs (n N, 4) in coefficient form,
+        canonical; fk20_setup (2N, 12) and fk20_setup_inf (2N,) from kzg_fk20_setup.  -> (proofs (n N, 12), inf (n N,)): proof m of
+        polynomial j is [(f_j(tau) - f_j(w^m)) / (tau - w^m)] g1, slot m belonging to w^bitrev(m) with bitrev.  The values are fr_ntt of the
+        same coefficients.  Resident torch tensors (all three) stay on the GPU."""
+        log2_n, flags = int(log2_n), _lib.NTT_BITREV if bitrev else 0
+        if log2_n < 0 or log2_n > 62:
+            raise ValueError("log2_n out of range")
+        big_n = 1 << log2_n
+        if _is_torch(coeffs):
+            import torch
+            self._t_check(coeffs, 4, "coeffs")
+            n_el = coeffs.numel() // 4
+            if n_el % big_n:
+                raise ValueError("coeffs hold %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+            self._t_check(fk20_setup, 12, "fk20_setup", rows=2 * big_n), self._t_bytes(fk20_setup_inf, 2 * big_n, "fk20_setup_inf")
+            proof = torch.empty((n_el, 12), dtype=coeffs.dtype, device=coeffs.device)
+            inf = torch.empty(n_el, dtype=torch.uint8, device=coeffs.device)
+            self._chk(self._lib.zkp_kzg_fk20_batch_dev(self._h, self._tp(fk20_setup), self._tp(fk20_setup_inf), self._tp(coeffs), n_el >> log2_n, log2_n, flags,
+                                                       self._tp(proof), self._tp(inf), self._stream()))
+            return proof, inf
+        cf = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        n_el = cf.size // 4
+        if cf.size % 4 or n_el % big_n:
+            raise ValueError("coeffs hold %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+        setup = _np(fk20_setup, 12)
+        if setup.shape[0] != 2 * big_n:
+            raise ValueError("the FK20 setup holds %d points for polynomials of 2^%d" % (setup.shape[0], log2_n))
+        sinf = _flags(fk20_setup_inf, 2 * big_n, "kzg_fk20")
+        proof, inf = np.empty((n_el, 12), dtype=np.uint64), np.empty(n_el, dtype=np.uint8)
+        self._chk(self._lib.zkp_kzg_fk20_batch(self._h, _ptr(setup), _ptr(sinf), _ptr(cf), n_el >> log2_n, log2_n, flags, _ptr(proof), _ptr(inf)))
+        return proof, inf
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

@@ -609,6 +609,69 @@ def kzg_open_batch(lagrange_g1, evals, z, bitrev=True, engine=None):
     return e.kzg_open(setup, ev, z, log2_n, bitrev)
 
 
+def _pow2_points(points, what):
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    big_n = pts.shape[0]
+    log2_n = big_n.bit_length() - 1
+    if big_n < 1 or big_n != 1 << log2_n:
+        raise ValueError("%s: %d points is no power of two" % (what, big_n))
+    return pts, log2_n
+
+
+def g1_ntt(points, log2_n, inverse=False, bitrev=False, inf=None, engine=None):
+    """(out (n, 12), out_inf (n,)): the number-theoretic transform of vectors of 2^log2_n G1 points each over the roots of unity of fr_ntt
+    (zkp_g1_ntt_batch): out[j][i] = sum_k [w^(i k)] points[j][k]; inverse and bitrev as in fr_ntt.  The points are trusted."""
+    return (engine or default_engine()).g1_ntt(points, log2_n, inverse=inverse, bitrev=bitrev, inf=inf)
+
+
+class Fk20Setup:
+    """What kzg_open_domain_batch needs of a setup: the 2N points (and their infinity flags) that zkp_kzg_fk20_setup derives from the
+    monomial setup [tau^k] g1, k < N.  Build it once per setup with kzg_fk20_setup."""
+
+    def __init__(self, points, inf, log2_n):
+        self.points, self.inf, self.log2_n = points, inf, int(log2_n)
+
+    @property
+    def n(self):
+        return 1 << self.log2_n
+
+
+def kzg_fk20_setup(monomial_g1, engine=None):
+    """Fk20Setup of the monomial setup monomial_g1 (N, 12), N a power of two (zkp_kzg_fk20_setup).  The points are trusted: check a
+    ceremony's output once with g1_is_valid."""
+    e = engine or default_engine()
+    mono, log2_n = _pow2_points(monomial_g1, "kzg_fk20_setup")
+    pts, inf = e.kzg_fk20_setup(mono, log2_n)
+    return Fk20Setup(pts, inf, log2_n)
+
+
+def kzg_open_domain_batch(setup, coeffs, bitrev=True, engine=None):
+    """(proofs (n, N, 12), inf (n, N)): polynomial j, given by its N coefficients coeffs[j], opened at EVERY N-th root of unity by the
+    Feist-Khovratovich method (zkp_kzg_fk20_batch): proofs[j][m] = [(f_j(tau) - f_j(w^m)) / (tau - w^m)] g1, slot m belonging to
+    w^bitrev(m) with bitrev, as blobs are stored.  The opened values are fr_ntt(coeffs, bitrev=bitrev).  setup: an Fk20Setup."""
+    e = engine or default_engine()
+    cf = np.ascontiguousarray(coeffs, dtype=np.uint64)
+    if cf.size % (4 * setup.n):
+        raise ValueError("%d coefficients: no whole number of polynomials of %d" % (cf.size // 4, setup.n))
+    n = cf.size // (4 * setup.n)
+    proof, inf = e.kzg_fk20(setup.points, setup.inf, cf.reshape(-1, 4), setup.log2_n, bitrev)
+    return proof.reshape(n, setup.n, 12), inf.reshape(n, setup.n)
+
+
+def kzg_lagrange_setup(monomial_g1, bitrev=False, engine=None):
+    """The Lagrange setup [l_i(tau)] g1 (N, 12) of the N-th roots of unity from the monomial setup [tau^k] g1: the inverse G1 NTT
+    (zkp_g1_ntt_batch); with bitrev slot i holds the point of w^bitrev(i), the order blobs use.  Its output goes straight into kzg_commit_batch / kzg_open_batch.  Raises if a point
+    comes out infinite, which no honest setup gives."""
+    e = engine or default_engine()
+    mono, log2_n = _pow2_points(monomial_g1, "kzg_lagrange_setup")
+    out, inf = e.g1_ntt(mono, log2_n, inverse=True)
+    if np.asarray(inf).any():
+        raise ValueError("kzg_lagrange_setup: an infinite Lagrange point (tau is a root of unity, or the setup is malformed)")
+    if bitrev:      # ZKP_NTT_BITREV orders the INPUT of an inverse transform; here the output side is the evaluation side: N rows, once per setup
+        out = out[[int(format(i, "0%db" % log2_n)[::-1], 2) if log2_n else 0 for i in range(1 << log2_n)]]
+    return np.ascontiguousarray(out)
+
+
 def kzg_verify_blob_batch(setup, evals, commitments, z, proofs, bitrev=True, engine=None, rand=None):
     """True iff proof j opens commitment j at z_j to the value of polynomial j there, the polynomial given by its N = 2^k evaluations
     evals[j] over the N-th roots of unity (bit-reversed order with bitrev, the order blobs are stored in): y = fr_eval(evals, z) on
