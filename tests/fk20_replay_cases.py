@@ -2,6 +2,7 @@
 and test_fk20_cpu.py; not a test module): Case rows in the form of tests/replay_cases.py, and the fixtures the FK20 tests share.  Expected
 values never come from the library under test: every point is [e] g1 for an exponent e known from the construction (tests/fk20_model.py on
 Python integers, the TAU of tests/poly_replay_cases.py), which is one oracle multiplication of the generator (replay_cases.expect_points)."""
+import operator
 import random
 
 import numpy as np
@@ -20,6 +21,27 @@ EXCLUDED = {}
 
 VECTOR_KINDS = ("random", "holes", "identity", "constant", "spike")
 POLY_KINDS = prc.POLY_KINDS + ("ends",)          # "ends": f_1 = .. = f_{N-2} = 0, the empty tail of c
+
+
+class Lazy:
+    """a sequence whose items are made on first use, and once: a replay takes all three sets of a build, a step of a call-order sequence
+    one of them, and every point of a set costs an oracle multiplication"""
+
+    def __init__(self, makers):
+        self._makers, self._made = list(makers), {}
+
+    def __len__(self):
+        return len(self._makers)
+
+    def __getitem__(self, i):
+        i = operator.index(i)
+        if i < 0:
+            i += len(self._makers)
+        if not 0 <= i < len(self._makers):
+            raise IndexError(i)
+        if i not in self._made:
+            self._made[i] = self._makers[i]()
+        return self._made[i]
 
 
 def make_vector(kind, log2_n, flags, rng):
@@ -72,25 +94,20 @@ def proofs_for(polys, log2_n, bitrev, tau=TAU):
 def _ntt_sets(n_vec, log2_n, flags, seed):
     def build():
         rng = random.Random(seed * 419 + n_vec * 11 + log2_n * 5 + flags)
-        sets, exp = [], []
-        for s in range(3):
-            kinds = [VECTOR_KINDS[(2 * s + j) % 5] for j in range(n_vec)]         # A: random holes identity; B: identity constant spike; C: spike random holes
-            pts, inf, out, out_inf = ntt_io([make_vector(k, log2_n, flags, rng) for k in kinds], log2_n, flags)
-            sets.append(dict(points=pts, inf=inf))
-            exp.append((out, out_inf))
-        return sets, exp
+        # A: random holes identity; B: identity constant spike; C: spike random holes
+        vecs = [[make_vector(VECTOR_KINDS[(2 * s + j) % 5], log2_n, flags, rng) for j in range(n_vec)] for s in range(3)]
+        io = Lazy([(lambda v: lambda: ntt_io(v, log2_n, flags))(v) for v in vecs])
+        return (Lazy([(lambda s: lambda: dict(points=io[s][0], inf=io[s][1]))(s) for s in range(3)]),
+                Lazy([(lambda s: lambda: (io[s][2], io[s][3]))(s) for s in range(3)]))
     return rc._cached(("g1-ntt", n_vec, log2_n, flags, seed), build)
 
 
 def _setup_sets(log2_n, seed):
     def build():
         rng = random.Random(seed * 53 + log2_n)
-        sets, exp = [], []
-        for s in range(3):
-            tau = TAU if s == 0 else rng.randrange(2, R)
-            sets.append(dict(monomial=monomial_for(log2_n, tau)))
-            exp.append(fk20_setup_for(log2_n, tau))
-        return sets, exp
+        taus = [TAU if s == 0 else rng.randrange(2, R) for s in range(3)]
+        return (Lazy([(lambda t: lambda: dict(monomial=monomial_for(log2_n, t)))(t) for t in taus]),
+                Lazy([(lambda t: lambda: fk20_setup_for(log2_n, t))(t) for t in taus]))
     return rc._cached(("fk20-setup-sets", log2_n, seed), build)
 
 
@@ -98,13 +115,13 @@ def _fk20_sets(n, log2_n, bitrev, seed):
     def build():
         rng = random.Random(seed * 211 + n * 13 + log2_n * 3 + bitrev)
         big_n = 1 << log2_n
-        setup, sinf = fk20_setup_for(log2_n)
-        sets, exp = [], []
-        for s in range(3):
-            polys = [make_poly(POLY_KINDS[(2 * s + j) % 5] if s else "random", big_n, rng) for j in range(n)]
-            sets.append(dict(setup=setup, setup_inf=sinf, coeffs=fr_rows([v for f in polys for v in f])))
-            exp.append(proofs_for(polys, log2_n, bitrev))
-        return sets, exp
+        polys = [[make_poly(POLY_KINDS[(2 * s + j) % 5] if s else "random", big_n, rng) for j in range(n)] for s in range(3)]
+
+        def inputs(f):
+            setup, sinf = fk20_setup_for(log2_n)
+            return dict(setup=setup, setup_inf=sinf, coeffs=fr_rows([v for p in f for v in p]))
+        return (Lazy([(lambda f: lambda: inputs(f))(f) for f in polys]),
+                Lazy([(lambda f: lambda: proofs_for(f, log2_n, bitrev))(f) for f in polys]))
     return rc._cached(("fk20-sets", n, log2_n, bitrev, seed), build)
 
 

@@ -1,0 +1,243 @@
+"""Inputs for the calls that cut themselves into slices (helper of test_slices_cpu.py and test_gpu_slices.py; not a test module): the G1
+NTT and FK20 (csrc/zkp_fk20.hip) and the KZG opening (csrc/zkp_poly.hip) walk `for (at = 0; at < n; at += slice)` and add an offset made
+from `at` to every operand.  A call large enough to cross a slice boundary is too large to compute item by item on the CPU, so it is
+ASSEMBLED: a small pool of B distinct items (B prime, so no slice length is a multiple of it) with their expected outputs - Python
+integers of poly_model / fk20_model and one oracle multiplication of the generator per point (replay_cases.expect_points), nothing from
+the library under test - and a seeded pseudo-random index sequence idx over the pool; item j of the call is pool item idx[j], inputs and
+expected outputs alike, by numpy indexing.  The last `tail` items of a call, its short last slice, are pool items used nowhere else in it.
+
+The slice conditions.  A sliced entry point is tested by its GPU test only if all of these hold, and test_slices_cpu.py checks them
+without a GPU for every Call made here; the next sliced entry point gets a pool here and the same checks there:
+  1. slice sizes: the slice length the test assumes is what the planning header computes for the exact shape (a few lines of C++ that
+     print it), and it equals the header's documented formula; the shape gives the intended number of slices with a short, non-empty
+     last one.  Whoever changes a slice constant sees the CPU test fail instead of a GPU test that no longer crosses a boundary.
+  2. no shift invariance: for every slice start at > 0 and w = min(64, slice length) items (the slice's own length if it is shorter), the
+     rows [at, at + w) of EVERY input and EVERY expected output array differ from the rows [0, w) and from those of every other start.
+  3. mutations: the expected arrays read as a wrong build would fill them - slice s taken from offset 0, slice s taken from the offset of
+     slice s - 1 - differ from the true expected bytes in EVERY output array of the call (points and flags; y, proofs and flags).
+  4. the pool is consistent on integers by a second route (the inverse transform gives the vector back, the circulant pipeline equals
+     the quotient formula, y in the domain is the evaluation of that slot), and the assembled rows decode to the pool's values.
+Condition 3 on the opening's flags needs identity proofs, which dense random polynomials never give: its pool holds two constant
+polynomials and the zero polynomial next to the dense ones, one of the constants in the tail.  The seeds below are ones for which the
+conditions hold (three flag bytes of a tail can equal the first three of a call by chance): they are properties of the inputs alone, and
+test_slices_cpu.py is their judge - change a seed or a shape, run it."""
+import random
+
+import numpy as np
+
+import fk20_model as fm
+import fk20_replay_cases as frc
+import poly_model as pm
+import poly_replay_cases as prc
+import replay_cases as rc
+from replay_cases import fr_rows
+
+R = pm.R
+TAU = prc.TAU
+SEED = 0x511CE5
+WINDOW = 64
+
+# the shapes: the smallest that the ABI's slice sizes allow (csrc/zkp_fk20_plan.hpp, csrc/zkp_poly_plan.hpp)
+NTT_LOG2 = 3                                     # the first size with two twiddled stages
+NTT_SLICE = (1 << 18) >> NTT_LOG2                # floor(2^18 / N) vectors
+NTT_N_VEC = 2 * NTT_SLICE + 5                    # three slices, the last of 5 vectors: 20 butterflies, a partial wavefront
+FK20_LOG2 = 2
+FK20_SLICE = (1 << 17) >> FK20_LOG2              # floor(2^17 / N) polynomials: a slice holds 2 N records each
+FK20_N = FK20_SLICE + 3
+OPEN_LOG2 = 10
+OPEN_SLICE = (1 << 22) >> OPEN_LOG2              # floor(2^22 / N) polynomials
+OPEN_N = OPEN_SLICE + 3
+
+
+class Call:
+    """one assembled call: n items in slices of `slice` items; inputs / outputs: name -> (array, rows of one item); idx: the pool item
+    of every item (the opening: of its polynomial); pool: whatever the builder keeps of the integers"""
+
+    def __init__(self, n, slice, idx, inputs, outputs, pool):
+        self.n, self.slice, self.idx, self.inputs, self.outputs, self.pool = n, slice, idx, inputs, outputs, pool
+        self.starts = list(range(0, n, slice))
+        self.tail = n - self.starts[-1]
+
+    def arg(self, name):
+        return self.inputs[name][0]
+
+    def want(self, name):
+        return self.outputs[name][0]
+
+
+def rows(arr, per, at, cnt):
+    """the rows of items [at, at + cnt)"""
+    return arr[at * per:(at + cnt) * per]
+
+
+def window(call, at):
+    return min(WINDOW, call.slice, call.n - at)
+
+
+def reading(call, name, how):
+    """the expected array `name` as a build with a wrong offset in slice s > 0 would leave it: 'zero' - every later slice computed from,
+    or written over, offset 0; 'previous' - from the offset of the slice before it"""
+    arr, per = call.outputs[name]
+    out = arr.copy()
+    for s, at in enumerate(call.starts):
+        if s == 0:
+            continue
+        cnt = min(call.slice, call.n - at)
+        src = 0 if how == "zero" else call.starts[s - 1]
+        out[at * per:(at + cnt) * per] = rows(arr, per, src, cnt)
+    return out
+
+
+def first_difference(got, want, per, call):
+    """(item, slice, pool item) of the first item whose rows differ, or None: what a failing byte comparison reports"""
+    got, want = np.ascontiguousarray(got).reshape(call.n, -1), np.ascontiguousarray(want).reshape(call.n, -1)
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, per)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    if not bad.size:
+        return None
+    j = int(bad[0])
+    return dict(item=j, slice=j // call.slice, offset_in_slice=j % call.slice, pool_item=int(call.idx[j]), items_wrong=int(bad.size))
+
+
+def draw(seed, n, tail_ids, n_pool):
+    """idx: the tail ids at the end in their order, everything before them drawn from the other pool items"""
+    body = np.array([j for j in range(n_pool) if j not in tail_ids], dtype=np.int64)
+    idx = body[np.random.RandomState(seed).randint(0, len(body), size=n)]
+    idx[n - len(tail_ids):] = tail_ids
+    return idx
+
+
+def take(arr, n_pool, idx):
+    """pool array (n_pool * per, ...) -> call array (len(idx) * per, ...)"""
+    a = arr.reshape((n_pool, -1))
+    return a[idx].reshape((-1,) + arr.shape[1:])
+
+
+def _distinct(items):
+    assert len({tuple(x) for x in items}) == len(items)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the G1 NTT
+NTT_B = 13
+NTT_TAIL = (8, 9, 10, 11, 12)
+
+
+def ntt_kinds(finite=False):
+    """VECTOR_KINDS cycled; a second all-identity vector would equal the first, so later ones are "holes".  finite: no identity entry in
+    any INPUT (the call with inf = NULL)"""
+    if finite:
+        return [("random", "constant", "spike")[j % 3] for j in range(NTT_B)]
+    kinds = [frc.VECTOR_KINDS[j % 5] for j in range(NTT_B)]
+    return [("holes" if k == "identity" and j >= 5 else k) for j, k in enumerate(kinds)]
+
+
+def ntt_pool(flags, finite=False):
+    def build():
+        rng = random.Random(SEED * 3 + flags + (8 if finite else 0))
+        kinds = ntt_kinds(finite)
+        vecs = [frc.make_vector(k, NTT_LOG2, flags, rng) for k in kinds]
+        _distinct(vecs)
+        outs = [pm.ntt_flags(v, NTT_LOG2, flags) for v in vecs]
+        pts, inf, out, out_inf = frc.ntt_io(vecs, NTT_LOG2, flags)
+        return dict(kinds=kinds, vecs=vecs, outs=outs, points=pts, inf=inf, out=out, out_inf=out_inf)
+    return rc._cached(("slice-ntt-pool", flags, finite), build)
+
+
+def ntt_call(flags, finite=False):
+    p = ntt_pool(flags, finite)
+    idx = draw(SEED + 11 * flags + finite, NTT_N_VEC, NTT_TAIL, NTT_B)
+    per = 1 << NTT_LOG2
+    inputs = dict(points=(take(p["points"], NTT_B, idx), per), inf=(take(p["inf"], NTT_B, idx), per))
+    outputs = dict(out=(take(p["out"], NTT_B, idx), per), out_inf=(take(p["out_inf"], NTT_B, idx), per))
+    return Call(NTT_N_VEC, NTT_SLICE, idx, inputs, outputs, p)
+
+
+# ------------------------------------------------------------------------------------------------------------------- FK20
+FK20_B = 11
+FK20_TAIL = (7, 9, 10)                           # constant, ends, random: identity proofs on both sides of the boundary
+
+
+def fk20_kinds():
+    """POLY_KINDS cycled; a second zero polynomial would equal the first, so it is a constant (every proof the identity as well)"""
+    kinds = [frc.POLY_KINDS[j % 5] for j in range(FK20_B)]
+    return [("constant" if k == "zero" and j >= 5 else k) for j, k in enumerate(kinds)]
+
+
+def fk20_pool(bitrev):
+    def build():
+        rng = random.Random(SEED * 5 + bitrev)
+        kinds = fk20_kinds()
+        polys = [frc.make_poly(k, 1 << FK20_LOG2, rng) for k in kinds]
+        _distinct(polys)
+        exps = [fm.quotient_proofs(f, TAU, FK20_LOG2, bitrev) for f in polys]
+        proof, inf = rc.expect_points(1, [e for x in exps for e in x])
+        return dict(kinds=kinds, polys=polys, exps=exps, coeffs=fr_rows([v for f in polys for v in f]), proof=proof, inf=inf)
+    return rc._cached(("slice-fk20-pool", bitrev), build)
+
+
+def fk20_call(bitrev):
+    p = fk20_pool(bitrev)
+    idx = draw(SEED + 101 + bitrev, FK20_N, FK20_TAIL, FK20_B)
+    per = 1 << FK20_LOG2
+    inputs = dict(coeffs=(take(p["coeffs"], FK20_B, idx), per))
+    outputs = dict(proof=(take(p["proof"], FK20_B, idx), per), inf=(take(p["inf"], FK20_B, idx), per))
+    return Call(FK20_N, FK20_SLICE, idx, inputs, outputs, p)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the opening
+OPEN_B, OPEN_C = 13, 12
+OPEN_POLY_KINDS = ["random"] * OPEN_B
+OPEN_POLY_KINDS[3], OPEN_POLY_KINDS[6], OPEN_POLY_KINDS[11] = "constant", "zero", "constant"
+OPEN_TAIL = (10, 11, 12)                         # the polynomials of the tail: dense, constant, dense ..
+OPEN_Z_KINDS = prc.Z_KINDS + ("outside",) * (OPEN_C - len(prc.Z_KINDS))
+OPEN_TAIL_Z = (4, 0, 2)                          # .. at slotlast, outside, slot0
+IN_DOMAIN_Z = tuple(c for c, k in enumerate(OPEN_Z_KINDS) if k.startswith("slot"))
+
+
+class SlotSetup:
+    """what poly_replay_cases.Setup holds, without an engine: the Lagrange points come from the oracle"""
+
+    def __init__(self, log2_n, bitrev):
+        self.log2_n, self.bitrev, self.n = log2_n, bitrev, 1 << log2_n
+        order = [pm.bit_reverse(i, log2_n) if bitrev else i for i in range(self.n)]
+        dom = pm.domain(log2_n)
+        lag = fm.lagrange_at(TAU, log2_n)
+        natural = rc._cached(("slice-lagrange", log2_n), lambda: rc.expect_points(1, lag)[0])
+        self.order = order
+        self.slot_domain = [dom[i] for i in order]
+        self.lagrange_tau = [lag[i] for i in order]
+        self.lagrange_g1 = np.ascontiguousarray(natural[order])
+
+
+def open_pool(bitrev):
+    def build():
+        rng = random.Random(SEED * 7)            # the same polynomials for both orders; the in-domain points differ
+        st = SlotSetup(OPEN_LOG2, bitrev)
+        polys = [prc.make_poly(k, st.n, rng) for k in OPEN_POLY_KINDS]
+        _distinct(polys)
+        zs = [prc.make_z(k, st, rng) for k in OPEN_Z_KINDS]
+        assert len(set(zs)) == OPEN_C
+        natural = rc._cached(("slice-open-evals",), lambda: [pm.ntt(f, OPEN_LOG2) for f in polys])
+        evals = [[e[i] for i in st.order] for e in natural]
+        f_tau = [prc.horner(f, TAU) for f in polys]
+        y = [[prc.horner(f, z) for z in zs] for f in polys]
+        q = [[(f_tau[p] - y[p][c]) * pow(TAU - zs[c], -1, R) % R for c in range(OPEN_C)] for p in range(OPEN_B)]
+        proof, inf = rc.expect_points(1, [e for x in q for e in x])
+        commit, cinf = rc.expect_points(1, f_tau)
+        return dict(setup=st, polys=polys, zs=zs, evals_int=evals, y_int=y, q=q, f_tau=f_tau, evals=fr_rows([v for e in evals for v in e]), z=fr_rows(zs),
+                    y=fr_rows([v for x in y for v in x]), proof=proof, inf=inf, commit=commit, cinf=cinf)
+    return rc._cached(("slice-open-pool", bitrev), build)
+
+
+def open_call(bitrev):
+    """Call.idx is the polynomial of every opening, Call.iz its point; the evaluations are 128 MiB, so nothing here is cached"""
+    p = open_pool(bitrev)
+    idx = draw(SEED + 211 + bitrev, OPEN_N, OPEN_TAIL, OPEN_B)
+    iz = np.random.RandomState(SEED + 301 + bitrev).randint(0, OPEN_C, size=OPEN_N)
+    iz[OPEN_N - len(OPEN_TAIL_Z):] = OPEN_TAIL_Z
+    pair = idx * OPEN_C + iz
+    inputs = dict(evals=(take(p["evals"], OPEN_B, idx), 1 << OPEN_LOG2), z=(p["z"][iz], 1))
+    outputs = dict(y=(p["y"][pair], 1), proof=(p["proof"][pair], 1), inf=(p["inf"][pair], 1))
+    call = Call(OPEN_N, OPEN_SLICE, idx, inputs, outputs, p)
+    call.iz = iz
+    return call

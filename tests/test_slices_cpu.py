@@ -1,0 +1,230 @@
+"""CPU gate for tests/test_gpu_slices.py: the conditions under which a byte comparison of a sliced call proves that every slice took its
+own offsets (the docstring of tests/slice_pools.py states them).  The slice lengths the GPU tests assume are what the planning headers
+compute for the exact shapes; every shape crosses its boundaries and ends in a short slice; no slice of any input or expected output
+equals another slice's rows; the expected arrays read with a wrong offset differ from the true ones in every output array; the pools
+are consistent on integers by a second route.  No GPU and no library call."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import fk20_model as fm
+import poly_model as pm
+import poly_replay_cases as prc
+import slice_pools as sp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "zkvm_pairings_amd", "csrc")
+R = pm.R
+NTT_FLAGS = (0, pm.INVERSE | pm.BITREV)
+
+PROGRAM = """
+#include <cstdio>
+#include "zkp_fk20_plan.hpp"
+#include "zkp_poly_plan.hpp"
+int main() {
+    using namespace zkp;
+    std::printf("g1ntt %%zu\\n", fk20::slice_vectors((size_t)%d, %du));
+    std::printf("fk20 %%zu\\n", fk20::fk20_layout((size_t)%d, %du).slice);
+    std::printf("open %%zu\\n", poly::open_slice((size_t)%d, %du));
+    std::printf("g1ntt_max %%zu\\n", fk20::slice_vectors((size_t)4, fk20::G1NTT_MAX_LOG2));
+    std::printf("fk20_max %%zu\\n", fk20::fk20_layout((size_t)4, fk20::FK20_MAX_LOG2).slice);
+    std::printf("open_max %%zu\\n", poly::open_slice((size_t)16, poly::NTT_MAX_LOG2));
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def header_slices(tmp_path_factory):
+    d = tmp_path_factory.mktemp("slices")
+    src, exe = str(d / "slices.cpp"), str(d / "slices")
+    with open(src, "w") as f:
+        f.write(PROGRAM % (sp.NTT_N_VEC, sp.NTT_LOG2, sp.FK20_N, sp.FK20_LOG2, sp.OPEN_N, sp.OPEN_LOG2))
+    cc = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", exe, src], capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stdout[-3000:] + cc.stderr[-3000:]
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr[-3000:]
+    return {k: int(v) for k, v in (line.split() for line in out.stdout.split("\n") if line)}
+
+
+@pytest.fixture(scope="module")
+def calls():
+    out = {}
+    for flags in NTT_FLAGS:
+        out["g1_ntt-flags%d" % flags] = sp.ntt_call(flags)
+    out["g1_ntt-finite"] = sp.ntt_call(0, finite=True)
+    for bitrev in (False, True):
+        out["fk20-bitrev%d" % bitrev] = sp.fk20_call(bitrev)
+        out["open-bitrev%d" % bitrev] = sp.open_call(bitrev)
+    return out
+
+
+NAMES = ["g1_ntt-flags0", "g1_ntt-flags3", "g1_ntt-finite", "fk20-bitrev0", "fk20-bitrev1", "open-bitrev0", "open-bitrev1"]
+
+
+# ------------------------------------------------------------------------------------------------------------------- slice sizes and shapes
+def test_slice_lengths_are_the_headers_and_their_documented_formulas(header_slices):
+    h = header_slices
+    assert h["g1ntt"] == sp.NTT_SLICE == (1 << 18) // (1 << sp.NTT_LOG2) == 32768
+    assert h["fk20"] == sp.FK20_SLICE == (1 << 17) // (1 << sp.FK20_LOG2) == 32768
+    assert h["open"] == sp.OPEN_SLICE == (1 << 22) // (1 << sp.OPEN_LOG2) == 4096
+    # at least one vector or polynomial where the floor would be zero or the quotient is small: N = 2^20, 2^19, 2^20
+    assert (h["g1ntt_max"], h["fk20_max"], h["open_max"]) == (1, 1, 4)
+
+
+def test_every_shape_crosses_its_boundaries_and_ends_in_a_short_slice(header_slices, calls):
+    want = {"g1_ntt": (header_slices["g1ntt"], 3, 5), "fk20": (header_slices["fk20"], 2, 3), "open": (header_slices["open"], 2, 3)}
+    for name in NAMES:
+        c = calls[name]
+        slice_len, n_slices, tail = want[name.split("-")[0]]
+        assert c.slice == slice_len and len(c.starts) == n_slices and c.tail == tail and 0 < c.tail < c.slice, name
+        assert c.starts == [s * slice_len for s in range(n_slices)] and c.n == (n_slices - 1) * slice_len + tail, name
+        for arr, per in list(c.inputs.values()) + list(c.outputs.values()):
+            assert arr.shape[0] == c.n * per and arr.flags.c_contiguous, name
+    c = calls["g1_ntt-flags0"]
+    assert c.n << sp.NTT_LOG2 == 524328 and (c.tail << sp.NTT_LOG2) // 2 == 20                   # points; butterflies of the last slice
+    assert calls["fk20-bitrev0"].n << sp.FK20_LOG2 == 131084 and calls["open-bitrev0"].arg("evals").nbytes == 4099 << 15
+
+
+def test_the_tail_is_unique_and_the_pool_size_divides_no_slice(calls):
+    for name in NAMES:
+        c = calls[name]
+        tail = c.idx[c.n - c.tail:]
+        assert len(set(tail.tolist())) == c.tail and not np.isin(c.idx[:c.n - c.tail], tail).any(), name
+        n_pool = int(c.idx.max()) + 1
+        assert n_pool in (11, 13) and c.slice % n_pool and set(c.idx.tolist()) == set(range(n_pool)), name
+        # pseudo-random, not periodic: no shift by a slice, and no small shift, maps the sequence onto itself
+        body = c.idx[:c.n - c.tail]
+        for shift in list(range(1, 64)) + [c.slice]:
+            if shift < len(body):
+                assert (body[shift:] != body[:-shift]).mean() > 0.5, (name, shift)
+
+
+# ------------------------------------------------------------------------------------------------------------------- identity entries and flags
+def test_flags_are_set_on_both_sides_of_every_boundary(calls):
+    for flags in NTT_FLAGS:
+        c = calls["g1_ntt-flags%d" % flags]
+        per = 1 << sp.NTT_LOG2
+        for at in c.starts:
+            w = sp.window(c, at)
+            for name, (arr, _) in (("inf", c.inputs["inf"]), ("out_inf", c.outputs["out_inf"])):
+                win = sp.rows(arr, per, at, w)
+                assert win.any() and not win.all(), (flags, at, name)
+            if at:
+                assert sp.rows(c.arg("inf"), per, at - 64, 64).any() and sp.rows(c.want("out_inf"), per, at - 64, 64).any()
+        assert {"holes", "identity"} <= set(c.pool["kinds"])
+        # an identity entry is the point (0, 1) with its flag, never a stale finite point
+        assert (c.arg("points")[c.arg("inf") == 1] == np.eye(1, 12, 6, dtype=np.uint64)[0]).all()
+    c = calls["g1_ntt-finite"]
+    assert not c.arg("inf").any() and c.want("out_inf").any()
+    for bitrev in (False, True):
+        c = calls["fk20-bitrev%d" % bitrev]
+        per = 1 << sp.FK20_LOG2
+        inf = c.want("inf").reshape(c.n, per)
+        whole = inf.all(axis=1)                  # the zero and the constant polynomials
+        assert whole[:c.slice].any() and whole[c.slice - 64:c.slice].any() and whole[c.slice:].any() and not whole[c.slice:].all()
+        assert set(np.array(c.pool["kinds"])[np.unique(c.idx[whole])]) == {"zero", "constant"}
+
+
+def test_in_domain_points_fall_in_both_slices_and_in_the_tail(calls):
+    for bitrev in (False, True):
+        c = calls["open-bitrev%d" % bitrev]
+        inside = np.isin(c.iz, sp.IN_DOMAIN_Z)
+        first, last = inside[:c.slice], inside[c.slice:]
+        assert first[:64].any() and first[-64:].any() and last.any() and not last.all()
+        for zid in sp.IN_DOMAIN_Z:                                                               # each of the three slots, many times
+            assert (c.iz[:c.slice] == zid).sum() > 100
+        assert (c.iz == 1).any() and sp.OPEN_Z_KINDS[1] == "zero"
+        inf = c.want("inf")
+        assert inf[:c.slice].any() and inf[c.slice:].any() and not inf[c.slice:].all()
+
+
+# ------------------------------------------------------------------------------------------------------------------- no shift invariance
+@pytest.mark.parametrize("name", NAMES)
+def test_no_slice_repeats_the_rows_of_another(calls, name):
+    c = calls[name]
+    arrays = list(c.inputs.items()) + list(c.outputs.items())
+    for at in c.starts[1:]:
+        w = sp.window(c, at)
+        assert w == min(64, c.slice, c.n - at)
+        for other in c.starts:
+            if other == at:
+                continue
+            for what, (arr, per) in arrays:
+                if name == "g1_ntt-finite" and what == "inf":
+                    continue                                                                     # all zero: the call passes inf = NULL
+                assert sp.rows(arr, per, at, w).tobytes() != sp.rows(arr, per, other, w).tobytes(), (name, what, at, other)
+
+
+# ------------------------------------------------------------------------------------------------------------------- mutations
+@pytest.mark.parametrize("how", ["zero", "previous"])
+@pytest.mark.parametrize("name", NAMES)
+def test_a_wrong_offset_in_any_slice_changes_every_output_array(calls, name, how):
+    c = calls[name]
+    assert set(c.outputs) == {"g1_ntt": {"out", "out_inf"}, "fk20": {"proof", "inf"}, "open": {"y", "proof", "inf"}}[name.split("-")[0]]
+    for what, (arr, per) in c.outputs.items():
+        wrong = sp.reading(c, what, how)
+        assert wrong.shape == arr.shape and wrong.tobytes() != arr.tobytes(), (name, what, how)
+        # slice by slice: every slice after the first is wrong on its own, and the first is untouched
+        assert sp.rows(wrong, per, 0, c.slice).tobytes() == sp.rows(arr, per, 0, c.slice).tobytes()
+        for at in c.starts[1:]:
+            cnt = min(c.slice, c.n - at)
+            assert sp.rows(wrong, per, at, cnt).tobytes() != sp.rows(arr, per, at, cnt).tobytes(), (name, what, how, at)
+            assert sp.first_difference(wrong, arr, per, c)["slice"] == 1
+    if len(c.starts) > 2:                        # three slices: the two readings are different mistakes
+        for what in c.outputs:
+            assert sp.reading(c, what, "zero").tobytes() != sp.reading(c, what, "previous").tobytes(), (name, what)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the pools on integers
+def _ints(rows):
+    return [int.from_bytes(r.tobytes(), "little") for r in rows]
+
+
+def test_g1_ntt_pool_the_inverse_transform_gives_the_vector_back():
+    for flags, finite in ((0, False), (pm.INVERSE | pm.BITREV, False), (0, True)):
+        p = sp.ntt_pool(flags, finite)
+        assert len(p["vecs"]) == sp.NTT_B == 13
+        for v, out in zip(p["vecs"], p["outs"]):
+            assert pm.ntt_flags(out, sp.NTT_LOG2, flags ^ pm.INVERSE) == v and len(out) == 8
+        if not (flags & pm.INVERSE):
+            assert p["outs"][0] == pm.ntt_definition(p["vecs"][0], sp.NTT_LOG2, bitrev=bool(flags & pm.BITREV))
+        assert p["inf"].tolist() == [int(e == 0) for v in p["vecs"] for e in v]
+        assert p["out_inf"].tolist() == [int(e == 0) for v in p["outs"] for e in v]
+
+
+def test_fk20_pool_the_circulant_pipeline_equals_the_quotient_formula(calls):
+    for bitrev in (False, True):
+        p = sp.fk20_pool(bitrev)
+        assert len(p["polys"]) == sp.FK20_B == 11
+        for f, e in zip(p["polys"], p["exps"]):
+            assert fm.fk20_proofs(f, sp.TAU, sp.FK20_LOG2, bitrev) == e
+        c = calls["fk20-bitrev%d" % bitrev]
+        for j in (0, 1, c.slice - 1, c.slice, c.n - 1):                                            # the assembled rows are the pool's integers
+            assert _ints(sp.rows(c.arg("coeffs"), 4, j, 1)) == p["polys"][c.idx[j]]
+            assert sp.rows(c.want("inf"), 4, j, 1).tolist() == [int(e == 0) for e in p["exps"][c.idx[j]]]
+
+
+def test_opening_pool_y_is_horner_and_in_the_domain_the_evaluation_of_the_slot(calls):
+    for bitrev in (False, True):
+        p = sp.open_pool(bitrev)
+        st = p["setup"]
+        assert sum(st.lagrange_tau) % R == 1 and st.n == 1024 and sp.OPEN_POLY_KINDS.count("random") == 10
+        slot_of = {"slot0": 0, "slot1": 1, "slotlast": st.n - 1}
+        for b in range(sp.OPEN_B):
+            # a commitment in the slot order of the evaluations: sum f(slot_i) l_i(tau) = f(tau)
+            assert sum(e * l for e, l in zip(p["evals_int"][b], st.lagrange_tau)) % R == p["f_tau"][b]
+            for zid in sp.IN_DOMAIN_Z:
+                m = slot_of[sp.OPEN_Z_KINDS[zid]]
+                assert p["zs"][zid] == st.slot_domain[m] and p["y_int"][b][zid] == p["evals_int"][b][m]
+            for zid in range(sp.OPEN_C):
+                assert (p["q"][b][zid] * (sp.TAU - p["zs"][zid]) + p["y_int"][b][zid]) % R == p["f_tau"][b]
+        c = calls["open-bitrev%d" % bitrev]
+        for j in (0, 1, c.slice - 1, c.slice, c.slice + 1, c.n - 1):
+            f, zed = p["polys"][c.idx[j]], _ints(c.arg("z")[j:j + 1])[0]
+            assert zed == p["zs"][c.iz[j]] and _ints(c.want("y")[j:j + 1])[0] == prc.horner(f, zed)
+            ev = _ints(sp.rows(c.arg("evals"), st.n, j, 1))
+            assert ev == p["evals_int"][c.idx[j]] and ev[5] == prc.horner(f, st.slot_domain[5])
+        assert c.want("inf")[c.n - 3:].tolist() == [0, 1, 0] and sp.OPEN_POLY_KINDS[sp.OPEN_TAIL[1]] == "constant"
