@@ -11,6 +11,7 @@ use core::ptr;
 pub mod poly;
 pub mod prove;
 pub mod fk20;
+pub mod cells;
 
 #[repr(C)]
 pub struct ZkpCtx {

@@ -1,6 +1,6 @@
 """MI355X-native batched BLS12-381 pairing engine behind the zkvm-pairings API shape.
 
-Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h and include/zkp_fk20.h); it raises if
+Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h and include/zkp_cells.h); it raises if
 the library has not been built.  There is no CPU fallback."""
 from . import _lib
 from ._lib import ZkpError
@@ -8,11 +8,13 @@ from ._lib import ZkpError
 _lib.load()
 
 from .engine import KERNEL_AUTO, KERNEL_COOP, KERNEL_THREAD, PairingEngine  # noqa: E402
-from .pairings import (R1CS, Fk20Setup, Fr, G1Affine, G2Affine, Groth16ProvingKey, Groth16VerifyingKey, Gt, KzgSetup, MillerLoopResult, final_exponentiation,  # noqa: E402
+from .pairings import (R1CS, CellSetup, Fk20Setup, Fr, G1Affine, G2Affine, Groth16ProvingKey, Groth16VerifyingKey, Gt, KzgSetup, MillerLoopResult, final_exponentiation,  # noqa: E402
                        groth16_prove_batch, groth16_quotient_batch, groth16_verify_batch, groth16_verify_each, g1_ntt, kzg_commit_batch, kzg_fk20_setup, kzg_lagrange_setup, kzg_open_batch, kzg_open_domain_batch, kzg_verify_batch, kzg_verify_blob_batch, kzg_verify_each, msm,
+                       kzg_cells_setup, kzg_cell_proofs_batch, kzg_cells_and_proofs_batch, kzg_cell_verify_batch, kzg_cell_verify_each,
                        multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
 __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "pairing", "multi_miller_loop", "msm",
            "final_exponentiation", "Fr", "Groth16VerifyingKey", "R1CS", "Groth16ProvingKey", "groth16_prove_batch", "groth16_quotient_batch", "groth16_verify_batch", "groth16_verify_each", "KzgSetup", "kzg_verify_batch", "kzg_verify_each",
-           "kzg_verify_blob_batch", "kzg_commit_batch", "kzg_open_batch", "g1_ntt", "Fk20Setup", "kzg_fk20_setup", "kzg_open_domain_batch", "kzg_lagrange_setup", "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]
+           "kzg_verify_blob_batch", "kzg_commit_batch", "kzg_open_batch", "g1_ntt", "Fk20Setup", "kzg_fk20_setup", "kzg_open_domain_batch", "kzg_lagrange_setup", "CellSetup", "kzg_cells_setup", "kzg_cell_proofs_batch", "kzg_cells_and_proofs_batch",
+           "kzg_cell_verify_batch", "kzg_cell_verify_each", "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

@@ -213,6 +213,18 @@ FK20_SIGNATURES = {
     "zkp_kzg_fk20_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, c_int, c_vp, c_vp, c_vp]),
 }
 
+# name -> (restype, argtypes); MUST list every symbol include/zkp_cells.h declares (the fifth header of the same library)
+CELLS_POINTS_CHECKED, CELLS_VK_CHECKED = 4, 8   # ZKP_CELLS_POINTS_CHECKED / _VK_CHECKED
+c_u = ctypes.c_uint
+CELLS_SIGNATURES = {
+    "zkp_kzg_cells_setup": (c_int, [c_vp, c_vp, c_u, c_u, c_vp, c_vp]),
+    "zkp_kzg_cells_setup_dev": (c_int, [c_vp, c_vp, c_u, c_u, c_vp, c_vp, c_vp]),
+    "zkp_kzg_cells_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_u, c_u, c_u, c_int, c_vp, c_vp]),
+    "zkp_kzg_cells_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_u, c_u, c_u, c_int, c_vp, c_vp, c_vp]),
+    "zkp_kzg_cell_verify_batch": (c_int, [c_vp] * 10 + [c_sz, c_u, c_u, c_int, c_vp, c_vp]),
+    "zkp_kzg_cell_verify_batch_dev": (c_int, [c_vp] * 10 + [c_sz, c_u, c_u, c_int, c_vp, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -239,7 +251,8 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
+                                  list(CELLS_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -2030,6 +2030,80 @@ __global__ void __launch_bounds__(64, 2) k_fk20_mul(const uint64_t* setup, const
     jrec_st<1>(rec, t, 0, p);
 }
 
+// =============================================================================== the KZG cell proofs' multiply-accumulate (zkp_cells.hip drives it;
+// zkp_cells_plan.hpp holds every index).  Slot t of a polynomial is H[t] = sum_{i < l} [c^_i[t]] X_i[t]: the l bases of a slot are summed
+// anyway, so the g = 2^s bases of a lane share ONE chain of 255 doublings.  The bases are affine setup points, converted once and parked in
+// LDS (slots 2 q, 2 q + 1 of base q: 8 KiB per base and workgroup, dynamic, so a launch reserves g x 8 KiB and g = 1 keeps eight
+// workgroups per CU); the scalars are read a byte of each at a time into one register, so a bit test is a shift.  At every bit the lane
+// adds each base whose scalar has the bit by the mixed addition with every exceptional case (jac_madd): zero coefficients leave the
+// accumulator infinite for many bits; two bases of a lane that are equal or opposite (a setup with tau = 1 or tau = -1) under equal scalars
+// make it meet +X (the doubling) and -X (infinity) at the first bit they share; a base flagged infinite (k = 1: all of them) has its
+// bits masked away.  The result stays Jacobian: a partial, or the record when g = l.
+namespace cl = zkp::cells;
+__global__ void __launch_bounds__(64, 2) k_cell_mac(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, int4* part, int4* rec, cl::Mac a) {
+    const uint32_t id = blockIdx.x * 64 + threadIdx.x;
+    if (id >= a.n_lane) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    extern __shared__ int4 park[];           // cl::mac_lds_bytes(a.s)
+    uint32_t j, t, i0;
+    cl::mac_lane(a, id, &j, &t, &i0);
+    const uint32_t g = 1u << a.s;
+    uint32_t live = 0;
+#pragma unroll 1
+    for (uint32_t q = 0; q < g; q++) {
+        const uint32_t src = cl::mac_base(a, t, i0 + q);
+        if (setup_inf && setup_inf[src]) continue;
+        Fp28 x, y;
+        fp28_from_wire(x, setup + 12 * (size_t)src);
+        fp28_from_wire(y, setup + 12 * (size_t)src + 6);
+        valid_park(park, lane, 2 * q, x);
+        valid_park(park, lane, 2 * q + 1, y);
+        live |= 0xffu << (8 * q);
+    }
+    const uint8_t* scb = (const uint8_t*)sc;
+    JacP p;
+    jac_set_inf(f, p);
+    if (live) {
+#pragma unroll 1
+        for (int by = 31; by >= 0; by--) {
+            uint32_t pk = 0;
+#pragma unroll 1
+            for (uint32_t q = 0; q < g; q++) pk |= (uint32_t)scb[32 * cl::mac_scalar(a, j, t, i0 + q) + by] << (8 * q);
+            pk &= live;
+#pragma unroll 1
+            for (int b = 7; b >= 0; b--) {
+                jac_dbl(f, p);
+                if (!((pk >> b) & 0x01010101u)) continue;
+#pragma unroll 1
+                for (uint32_t q = 0; q < g; q++)
+                    if ((pk >> (8 * q + b)) & 1) jac_madd(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, 2 * q + v); });
+            }
+        }
+    }
+    if (a.s == a.log2_l) jrec_st<1>(rec, cl::mac_record(a, j, t), 0, p);
+    else jrec_st<1>(part, id, 0, p);
+}
+// record (j, t) <- the sum of the slot's l / g partials, by the full addition.  Infinite partials occur on ordinary inputs (zero
+// coefficients); equal and opposite ones need strides whose bases AND scalars agree up to sign - equal coefficients under a setup with
+// tau = 1 (every X_i the same) or tau = -1 (X_i alternating in sign) - which tests/test_gpu_cells.py runs.  Equal coefficients alone do not
+// give them: X_i[t] = tau^-i X_0[t]
+__global__ void __launch_bounds__(64, 2) k_cell_sum(const int4* part, int4* rec, cl::Sum a) {
+    const uint32_t id = blockIdx.x * 64 + threadIdx.x;
+    if (id >= a.n_lane) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[3 * 4 * 64];
+    const uint32_t gl = a.log2_l - a.s, first = id << gl;
+    JacP p = jrec_get(part, first);
+#pragma unroll 1
+    for (uint32_t q = 1; q < (1u << gl); q++) {
+        jrec_park<1>(park, lane, part, first + q, 0);
+        jac_add(f, p, [&](int v) -> Fp28 { return valid_unpark(park, lane, v); });
+    }
+    jrec_st<1>(rec, ((id >> a.k1) << a.blk) + (id & fk::low_mask(a.k1)), 0, p);
+}
+
 // ---- MSM 1: n wire Fp elements -> Montgomery records (the points' coordinates, converted once per pass)
 __global__ void __launch_bounds__(256) k_msm_points(const uint64_t* w, uint32_t n_fp, int4* rec) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -3029,6 +3103,16 @@ hipError_t g1ntt_out(void* rec, uint64_t* out, uint8_t* out_inf, const fk20::Out
 hipError_t fk20_mul(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, uint32_t n_pt, uint32_t k1, void* rec, hipStream_t s) {
     if (!n_pt) return hipSuccess;
     hipLaunchKernelGGL(k_fk20_mul, dim3(fk20::grid(n_pt)), dim3(64), 0, s, setup, setup_inf, sc, n_pt, k1, (int4*)rec);
+    return hipGetLastError();
+}
+hipError_t cell_mac(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, void* part, void* rec, const cells::Mac& a, hipStream_t s) {
+    if (!a.n_lane) return hipSuccess;
+    hipLaunchKernelGGL(k_cell_mac, dim3(fk20::grid(a.n_lane)), dim3(64), cells::mac_lds_bytes(a.s), s, setup, setup_inf, sc, (int4*)part, (int4*)rec, a);
+    return hipGetLastError();
+}
+hipError_t cell_sum(const void* part, void* rec, const cells::Sum& a, hipStream_t s) {
+    if (!a.n_lane) return hipSuccess;
+    hipLaunchKernelGGL(k_cell_sum, dim3(fk20::grid(a.n_lane)), dim3(64), 0, s, (const int4*)part, (int4*)rec, a);
     return hipGetLastError();
 }
 hipError_t coop_fp28_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, hipStream_t s) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "zkp_cells_plan.hpp"
 #include "zkp_fk20_plan.hpp"
 
 namespace zkp {
@@ -51,6 +52,10 @@ hipError_t g1ntt_first(const uint64_t* in, const uint8_t* inf, void* rec, const 
 hipError_t g1ntt_stage(void* rec, const uint64_t* split, const fk20::Stage& a, hipStream_t s);
 hipError_t g1ntt_out(void* rec, uint64_t* out, uint8_t* out_inf, const fk20::Out& a, const uint64_t* ab, hipStream_t s);
 hipError_t fk20_mul(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, uint32_t n_pt, uint32_t k1, void* rec, hipStream_t s);
+// the cell proofs' multiply-accumulate and the sum of its partials (zkp_coop.hip, "the KZG cell proofs"; driven by zkp_cells.hip, every index from
+// zkp_cells_plan.hpp).  part: the Jacobian partials (unused when g = l), rec: the blocks of records
+hipError_t cell_mac(const uint64_t* setup, const uint8_t* setup_inf, const uint64_t* sc, void* part, void* rec, const cells::Mac& a, hipStream_t s);
+hipError_t cell_sum(const void* part, void* rec, const cells::Sum& a, hipStream_t s);
 // one tower operation per record (zkp_tower_op_batch); ab = n a-records followed by n b-records
 hipError_t coop_tower_op(CoopState* st, int op, const uint64_t* ab, size_t n, uint32_t repeat, uint64_t* out, hipStream_t s);
 hipError_t coop_time_prog(CoopState* st, int which, size_t n, hipStream_t s, hipEvent_t e0, hipEvent_t e1, float* ms);

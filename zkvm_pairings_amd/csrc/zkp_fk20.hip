@@ -60,6 +60,8 @@ __global__ __launch_bounds__(256) void k_g1ntt_split(const uint32_t* __restrict_
         if (int rc__ = ctxop::fail((c), (what), (call))) return rc__; \
     } while (0)
 
+}  // namespace
+
 // the twiddled stages 1 .. k - 1 of the transforms of `at`
 int run_stages(zkp_ctx* c, void* rec, const uint64_t* split, unsigned table_log2, const fk20::Span& at, bool inverse, hipStream_t s) {
     for (uint32_t p = 1; p < at.k; p++) {
@@ -90,6 +92,7 @@ fk20::Out out_of(const fk20::Span& at, bool perm, bool scale) {
     o.n_pt = at.n_vec << at.k;
     return o;
 }
+namespace {
 // (a_lo, a_hi, b_lo, b_hi) of 2^-k mod r
 void split_of_inverse(unsigned k, uint64_t* ab) {
     uint32_t s[NW], a[4], b[4];

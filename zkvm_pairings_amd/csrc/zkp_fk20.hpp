@@ -16,6 +16,10 @@ int g1ntt_tables(zkp_ctx* c, unsigned log2_n, const uint32_t** domain, const uin
 
 // split[i] <- the split of domain[i], i < 2^log2_n
 hipError_t g1ntt_split_build(const uint32_t* domain, unsigned log2_n, uint64_t* split, hipStream_t s);
+// the launch descriptors of a transform and its twiddled stages 1 .. k - 1, shared with the cell proofs (zkp_cells.hip)
+int run_stages(zkp_ctx* c, void* rec, const uint64_t* split, unsigned table_log2, const fk20::Span& at, bool inverse, hipStream_t s);
+fk20::First first_of(const fk20::Span& at, uint32_t mode, bool perm, uint32_t src_off);
+fk20::Out out_of(const fk20::Span& at, bool perm, bool scale);
 // the three calls on device pointers, asynchronous on s, arguments already checked: they grow the context's workspaces first, then only launch
 int g1_ntt_dev(zkp_ctx* c, const uint64_t* points, const uint8_t* inf, size_t n_vec, unsigned log2_n, int flags, uint64_t* out, uint8_t* out_inf, hipStream_t s);
 int fk20_setup_dev(zkp_ctx* c, const uint64_t* monomial, unsigned log2_n, uint64_t* out, uint8_t* out_inf, hipStream_t s);

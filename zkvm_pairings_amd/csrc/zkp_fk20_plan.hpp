@@ -111,21 +111,32 @@ ZKP_FK20_HD void stage_lane(const Stage& s, uint32_t t, uint32_t* r0, uint32_t* 
 }
 
 // ---- the first stage (bit 0, twiddle one): where position e of vector j comes from -------------------------------------------------------
-enum { SRC_WIRE = 0, SRC_SETUP = 1, SRC_REC = 2 };
+enum { SRC_WIRE = 0, SRC_SETUP = 1, SRC_REC = 2, SRC_CELLS = 3 };
 struct First {
     Span at;                 // where the records go
     uint32_t mode = SRC_WIRE;
     uint32_t perm = 0;       // position e takes input bitrev(e)
     uint32_t src_off = 0;    // SRC_REC: first record of the source vector inside its block
+    uint32_t src_len = 0;    // SRC_REC: inputs from src_len on are the identity, whatever their records hold (0: every input is a record).
+                             // PRECONDITION: perm set and src_len >= 2^(k - 1) (or k = 0), so that input A of every butterfly - bitrev of an
+                             // even position, below 2^(k - 1) - is a record: k_g1ntt_first<SRC_REC> reads A without testing it
+    uint32_t log2_l = 0;     // SRC_CELLS: the cell size; vector j is stride j
     uint32_t n_lane = 0;     // n_vec << (k - 1) butterflies, or n_vec points for k = 0 (a copy)
 };
 constexpr int64_t SRC_INFINITY = -1;
 // SRC_WIRE: the index of the wire point; SRC_SETUP: the index of the monomial point of position e of (s_{N-2}, .., s_0, inf x (N + 1)),
 // k = log2(2 N); SRC_REC: the record.  SRC_INFINITY: the identity
+// SRC_CELLS (the cell proofs' setup, zkp_cells_plan.hpp): the index of the monomial point of position pe of vector i < l,
+// (s_{N-l-1-i}, s_{N-2l-1-i}, .., k - 1 points with the index stepping down by l, then k + 1 identities), k1 = log2(2 k) >= 1
+ZKP_FK20_HD int64_t cells_setup_source(uint32_t log2_l, uint32_t k1, uint32_t i, uint32_t pe) {
+    const uint32_t k = 1u << (k1 - 1);
+    return pe + 2 <= k ? (int64_t)(((uint64_t)(k - 1 - pe) << log2_l) - 1 - i) : SRC_INFINITY;
+}
 ZKP_FK20_HD int64_t first_source(const First& a, uint32_t j, uint32_t e) {
     const uint32_t k = a.at.k, pe = a.perm ? bitrev(e, k) : e;
-    if (a.mode == SRC_REC) return (int64_t)((j << a.at.vs_log2) + a.src_off + pe);
+    if (a.mode == SRC_REC) return a.src_len && pe >= a.src_len ? SRC_INFINITY : (int64_t)((j << a.at.vs_log2) + a.src_off + pe);
     if (a.mode == SRC_WIRE) return (int64_t)(((uint64_t)j << k) + pe);
+    if (a.mode == SRC_CELLS) return cells_setup_source(a.log2_l, k, j, pe);
     const uint32_t n = 1u << (k - 1);                 // SRC_SETUP: k >= 1
     return pe + 2 <= n ? (int64_t)(n - 2 - pe) : SRC_INFINITY;
 }

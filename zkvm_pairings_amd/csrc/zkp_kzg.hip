@@ -443,6 +443,23 @@ hipError_t fr_eval(void* ws, const uint32_t* table, unsigned table_log2, const u
     return hipGetLastError();
 }
 
+hipError_t kzg_flag_init(int* flag, int* all_ok, int n_zero, hipStream_t s) {
+    hipLaunchKernelGGL(k_kzg_init, dim3(1), dim3(1), 0, s, flag, all_ok, n_zero);
+    return hipGetLastError();
+}
+hipError_t kzg_flag_status(const uint8_t* st, size_t n, int* flag, hipStream_t s) {
+    hipLaunchKernelGGL(k_kzg_status, dim3(blocks(n)), dim3(256), 0, s, st, n, flag);
+    return hipGetLastError();
+}
+hipError_t kzg_g2_side(const uint64_t* g2, const uint64_t* tau_g2, uint64_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_kzg_g2, dim3(1), dim3(64), 0, s, g2, tau_g2, out);
+    return hipGetLastError();
+}
+hipError_t kzg_flag_finish(const int* flag, int* all_ok, hipStream_t s) {
+    hipLaunchKernelGGL(k_kzg_finish, dim3(1), dim3(1), 0, s, flag, all_ok);
+    return hipGetLastError();
+}
+
 int kzg_check_dev(zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const uint64_t* rand, int flags, int* all_ok, hipStream_t s) {
     const size_t n = b->n;
     int rc;

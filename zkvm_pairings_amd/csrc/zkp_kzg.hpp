@@ -21,6 +21,12 @@ hipError_t fr_invert(void* ws, const uint64_t* a, size_t n, uint64_t* out, hipSt
 // ws: kzg::eval_layout(n_poly, log2_n).total bytes; n_poly >= 1
 hipError_t fr_eval(void* ws, const uint32_t* table, unsigned table_log2, const uint64_t* evals, const uint64_t* z, size_t n_poly, unsigned log2_n, int flags,
                    uint64_t* out, hipStream_t s);
+// the verifier's small launches, shared with the cell verifier (zkp_cells.hip): flag[0] = 1, flag[1] = 0 (n_zero: *all_ok = 1 instead);
+// any non-zero status byte clears flag[0]; out = -g2 | tau_g2, the G2 side of the two pairs; *all_ok = flag[0] && flag[1]
+hipError_t kzg_flag_init(int* flag, int* all_ok, int n_zero, hipStream_t s);
+hipError_t kzg_flag_status(const uint8_t* st, size_t n, int* flag, hipStream_t s);
+hipError_t kzg_g2_side(const uint64_t* g2, const uint64_t* tau_g2, uint64_t* out, hipStream_t s);
+hipError_t kzg_flag_finish(const int* flag, int* all_ok, hipStream_t s);
 // the verifier on device pointers: *all_ok (device int32), asynchronous on s
 int kzg_check_dev(zkp_ctx* c, const zkp_kzg_vk* vk, const zkp_kzg_batch* b, const uint64_t* rand, int flags, int* all_ok, hipStream_t s);
 

@@ -18,6 +18,7 @@
 #include "../../include/zkp_poly.h"
 #include "../../include/zkp_prove.h"
 #include "../../include/zkp_fk20.h"
+#include "../../include/zkp_cells.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -34,6 +35,7 @@
 #include "zkp_prove.hpp"
 #include "zkp_prove_plan.hpp"
 #include "zkp_fk20.hpp"
+#include "zkp_cells.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -2834,6 +2836,144 @@ int zkp_kzg_fk20_batch(zkp_ctx* c, const uint64_t* fk20_setup, const uint8_t* fk
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)ds, 2 * N * 2)) || (rc = validate_fr_dev(c, dc, n * N)) ||
         (rc = zkp::fk20_dev(c, (const uint64_t*)ds, (const uint8_t*)dsi, (const uint64_t*)dc, n, log2_n, flags, (uint64_t*)dout, (uint8_t*)(dout + off_i),
                             c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the KZG cell proofs (zkp_cells.hip, include/zkp_cells.h)
+namespace {
+bool cells_setup_args_bad(const zkp_ctx* c, const void* monomial, unsigned log2_n, unsigned log2_l, const void* out, const void* out_inf) {
+    return !c || zkp::cells::setup_args_bad(log2_n, log2_l) || !monomial || !out || !out_inf;
+}
+zkp::CellBatch cell_batch_of(const void* monomial, const void* g2, const void* tau_l_g2, const void* cm, const void* inf_c, const void* index, const void* values,
+                             const void* proofs, const void* inf_proof, size_t n, unsigned log2_d, unsigned log2_l, const void* rand) {
+    zkp::CellBatch b;
+    b.monomial = (const uint64_t*)monomial;
+    b.g2 = (const uint64_t*)g2;
+    b.tau_l_g2 = (const uint64_t*)tau_l_g2;
+    b.c = (const uint64_t*)cm;
+    b.values = (const uint64_t*)values;
+    b.proof = (const uint64_t*)proofs;
+    b.rand = (const uint64_t*)rand;
+    b.inf_c = (const uint8_t*)inf_c;
+    b.inf_proof = (const uint8_t*)inf_proof;
+    b.index = (const uint32_t*)index;
+    b.n = n;
+    b.log2_d = log2_d;
+    b.log2_l = log2_l;
+    return b;
+}
+bool cell_verify_args_bad(const zkp_ctx* c, const zkp::CellBatch& b, int flags, const void* out_ok) {
+    if (!c || !out_ok || zkp::cells::verify_args_bad(b.n, b.log2_d, b.log2_l, flags)) return true;
+    if (!b.n) return false;
+    return !b.monomial || !b.g2 || !b.tau_l_g2 || !b.c || !b.index || !b.values || !b.proof || !b.rand;
+}
+// validation mode: v(pointer, Fp count) over every coordinate array of the setup and the batch
+template <class V>
+int cell_validate(const zkp::CellBatch& b, V&& v) {
+    int rc;
+    if ((rc = v(b.c, b.n * 2)) || (rc = v(b.proof, b.n * 2)) || (rc = v(b.monomial, ((size_t)2 << b.log2_l))) || (rc = v(b.g2, 4)) || (rc = v(b.tau_l_g2, 4))) return rc;
+    return ZKP_OK;
+}
+bool cells_args_bad(const zkp_ctx* c, const void* setup, const void* coeffs, size_t n, unsigned log2_n, unsigned log2_l, unsigned log2_ext, int flags,
+                    const void* proof, const void* inf) {
+    return !c || zkp::cells::cells_args_bad(n, log2_n, log2_l, log2_ext, flags) || (n && (!setup || !coeffs || !proof || !inf));
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_kzg_cells_setup_dev(zkp_ctx* c, const void* monomial_g1, unsigned log2_n, unsigned log2_l, void* out, void* out_inf, void* stream) {
+    if (cells_setup_args_bad(c, monomial_g1, log2_n, log2_l, out, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, monomial_g1, ((size_t)1 << log2_n) * 2, S(stream))) return rc;
+    return zkp::cells_setup_dev(c, (const uint64_t*)monomial_g1, log2_n, log2_l, (uint64_t*)out, (uint8_t*)out_inf, S(stream));
+}
+int zkp_kzg_cells_setup(zkp_ctx* c, const uint64_t* monomial_g1, unsigned log2_n, unsigned log2_l, uint64_t* out, uint8_t* out_inf) {
+    if (cells_setup_args_bad(c, monomial_g1, log2_n, log2_l, out, out_inf)) return ZKP_ERR_ARG;
+    const size_t N = (size_t)1 << log2_n, off_i = zkp::fk20::up256(2 * N * 96);
+    HostIO io(c);
+    const void* dm = io.in(0, monomial_g1, N * 96);
+    char* dout = (char*)io.slot(4, off_i + 2 * N);
+    if (dout) {
+        io.get(out, dout, 2 * N * 96);
+        io.get(out_inf, dout + off_i, 2 * N);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dm, N * 2)) ||
+        (rc = zkp::cells_setup_dev(c, (const uint64_t*)dm, log2_n, log2_l, (uint64_t*)dout, (uint8_t*)(dout + off_i), c->stream)))
+        return rc;
+    return io.finish();
+}
+int zkp_kzg_cells_batch_dev(zkp_ctx* c, const void* cells_setup, const void* cells_setup_inf, const void* coeffs, size_t n, unsigned log2_n, unsigned log2_l,
+                            unsigned log2_ext, int flags, void* out_proof, void* out_inf, void* stream) {
+    if (cells_args_bad(c, cells_setup, coeffs, n, log2_n, log2_l, log2_ext, flags, out_proof, out_inf)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    int rc;
+    if ((rc = validate_on_stream(c, cells_setup, ((size_t)2 << log2_n) * 2, S(stream))) || (rc = validate_fr_on_stream(c, coeffs, n << log2_n, S(stream)))) return rc;
+    return zkp::cells_dev(c, (const uint64_t*)cells_setup, (const uint8_t*)cells_setup_inf, (const uint64_t*)coeffs, n, log2_n, log2_l, log2_ext, flags,
+                          (uint64_t*)out_proof, (uint8_t*)out_inf, S(stream));
+}
+// the setup in slot 0, its flags in slot 1, the coefficients in slot 2, the two outputs one after the other in slot 4
+int zkp_kzg_cells_batch(zkp_ctx* c, const uint64_t* cells_setup, const uint8_t* cells_setup_inf, const uint64_t* coeffs, size_t n, unsigned log2_n,
+                        unsigned log2_l, unsigned log2_ext, int flags, uint64_t* out_proof, uint8_t* out_inf) {
+    if (cells_args_bad(c, cells_setup, coeffs, n, log2_n, log2_l, log2_ext, flags, out_proof, out_inf)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t N = (size_t)1 << log2_n, nm = n << (log2_n - log2_l + log2_ext), off_i = zkp::fk20::up256(nm * 96);
+    HostIO io(c);
+    const void* ds = io.in(0, cells_setup, 2 * N * 96);
+    const void* dsi = io.in(1, cells_setup_inf, 2 * N);
+    const void* dc = io.in(2, coeffs, n * N * 32);
+    char* dout = (char*)io.slot(4, off_i + nm);
+    if (dout) {
+        io.get(out_proof, dout, nm * 96);
+        io.get(out_inf, dout + off_i, nm);
+    }
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)ds, 2 * N * 2)) || (rc = validate_fr_dev(c, dc, n * N)) ||
+        (rc = zkp::cells_dev(c, (const uint64_t*)ds, (const uint8_t*)dsi, (const uint64_t*)dc, n, log2_n, log2_l, log2_ext, flags, (uint64_t*)dout,
+                             (uint8_t*)(dout + off_i), c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_kzg_cell_verify_batch_dev(zkp_ctx* c, const void* monomial_g1_l, const void* g2, const void* tau_l_g2, const void* commitments, const void* inf_c,
+                                  const void* cell_index, const void* values, const void* proofs, const void* inf_proof, size_t n, unsigned log2_d,
+                                  unsigned log2_l, int flags, const void* rand, void* out_ok, void* stream) {
+    const zkp::CellBatch b = cell_batch_of(monomial_g1_l, g2, tau_l_g2, commitments, inf_c, cell_index, values, proofs, inf_proof, n, log2_d, log2_l, rand);
+    if (cell_verify_args_bad(c, b, flags, out_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (n)
+        if (int rc = cell_validate(b, [&](const void* d, size_t n_fp) { return validate_on_stream(c, d, n_fp, S(stream)); })) return rc;
+    return zkp::cell_check_dev(c, b, flags, (int*)out_ok, S(stream));
+}
+// the ten arrays one after the other in slot 0 (256-byte aligned), then the same driver as the _dev flavour
+int zkp_kzg_cell_verify_batch(zkp_ctx* c, const uint64_t* monomial_g1_l, const uint64_t* g2, const uint64_t* tau_l_g2, const uint64_t* commitments,
+                              const uint8_t* inf_c, const uint32_t* cell_index, const uint64_t* values, const uint64_t* proofs, const uint8_t* inf_proof, size_t n,
+                              unsigned log2_d, unsigned log2_l, int flags, const uint64_t* rand, int* out_ok) {
+    zkp::CellBatch d = cell_batch_of(monomial_g1_l, g2, tau_l_g2, commitments, inf_c, cell_index, values, proofs, inf_proof, n, log2_d, log2_l, rand);
+    if (cell_verify_args_bad(c, d, flags, out_ok)) return ZKP_ERR_ARG;
+    if (!n) { *out_ok = 1; return ZKP_OK; }
+    const size_t l = (size_t)1 << log2_l;
+    const void* src[10] = {d.c, d.inf_c, d.proof, d.inf_proof, d.index, d.values, d.monomial, d.g2, d.tau_l_g2, d.rand};
+    const size_t bytes[10] = {n * 96, n, n * 96, n, n * 4, n * l * 32, l * 96, 192, 192, n * 16};
+    const void* dev_of[10];
+    size_t off[10], total = 0;
+    for (int i = 0; i < 10; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    char* dev = (char*)io.slot(0, total);
+    for (int i = 0; i < 10; i++) dev_of[i] = io.put(dev + off[i], src[i], bytes[i]);
+    d = cell_batch_of(dev_of[6], dev_of[7], dev_of[8], dev_of[0], dev_of[1], dev_of[4], dev_of[5], dev_of[2], dev_of[3], n, log2_d, log2_l, dev_of[9]);
+    io.get(out_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = cell_validate(d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
+        (rc = zkp::cell_check_dev(c, d, flags, c->d_flag + 1, c->stream)))
         return rc;
     return io.finish();
 }

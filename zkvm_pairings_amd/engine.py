@@ -805,6 +805,118 @@ class PairingEngine:
         self._chk(self._lib.zkp_kzg_fk20_batch(self._h, _ptr(setup), _ptr(sinf), _ptr(cf), n_el >> log2_n, log2_n, flags, _ptr(proof), _ptr(inf)))
         return proof, inf
 
+    # ------------------------------------------------------------------ the KZG cell proofs (include/zkp_cells.h)
+    @staticmethod
+    def _cell_shape(log2_n, log2_l, log2_ext=0):
+        log2_n, log2_l, log2_ext = int(log2_n), int(log2_l), int(log2_ext)
+        if not (0 <= log2_l <= log2_n <= 62 and log2_ext in (0, 1)):
+            raise ValueError("cells: log2_l <= log2_n and log2_ext in (0, 1) expected, got %d, %d, %d" % (log2_l, log2_n, log2_ext))
+        return log2_n, log2_l, log2_ext
+
+    def kzg_cells_setup(self, monomial_g1, log2_n, log2_l):
+        """(setup (2N, 12), inf (2N,)) for kzg_cells with cells of l = 2^log2_l values, from the monomial setup monomial_g1[k] = [tau^k] g1,
+        k < N = 2^log2_n (zkp_kzg_cells_setup): l vectors of 2 N / l points, computed once per setup and cell size.  The points are
+        trusted.  A resident torch tensor stays on the GPU."""
+        log2_n, log2_l, _ = self._cell_shape(log2_n, log2_l)
+        big_n = 1 << log2_n
+        if _is_torch(monomial_g1):
+            import torch
+            self._t_check(monomial_g1, 12, "monomial_g1", rows=big_n)
+            out = torch.empty((2 * big_n, 12), dtype=monomial_g1.dtype, device=monomial_g1.device)
+            out_inf = torch.empty(2 * big_n, dtype=torch.uint8, device=monomial_g1.device)
+            self._chk(self._lib.zkp_kzg_cells_setup_dev(self._h, self._tp(monomial_g1), log2_n, log2_l, self._tp(out), self._tp(out_inf), self._stream()))
+            return out, out_inf
+        mono = _np(monomial_g1, 12)
+        if mono.shape[0] != big_n:
+            raise ValueError("the monomial setup holds %d points for polynomials of 2^%d" % (mono.shape[0], log2_n))
+        out, out_inf = np.empty((2 * big_n, 12), dtype=np.uint64), np.empty(2 * big_n, dtype=np.uint8)
+        self._chk(self._lib.zkp_kzg_cells_setup(self._h, _ptr(mono), log2_n, log2_l, _ptr(out), _ptr(out_inf)))
+        return out, out_inf
+
+    def kzg_cells(self, cells_setup, cells_setup_inf, coeffs, log2_n, log2_l, log2_ext=1, bitrev=False):
+        """The KZG cell proofs of n polynomials (zkp_kzg_cells_batch): coeffs (n N, 4) in coefficient form, canonical; cells_setup (2N, 12)
+        and cells_setup_inf (2N,) from kzg_cells_setup with the same log2_l.  -> (proofs (n M, 12), inf (n M,)), M = 2^log2_ext N / l:
+        proof m of polynomial j opens it on the coset w_D^m' H_l, m' = bitrev_M(m) with bitrev.  The cells' values are fr_ntt of the
+        coefficients zero-padded to 2^log2_ext N.  Resident torch tensors (all three) stay on the GPU."""
+        log2_n, log2_l, log2_ext = self._cell_shape(log2_n, log2_l, log2_ext)
+        flags, big_n, log2_m = _lib.NTT_BITREV if bitrev else 0, 1 << log2_n, log2_n - log2_l + log2_ext
+        if _is_torch(coeffs):
+            import torch
+            self._t_check(coeffs, 4, "coeffs")
+            n_el = coeffs.numel() // 4
+            if n_el % big_n:
+                raise ValueError("coeffs hold %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+            n = n_el >> log2_n
+            self._t_check(cells_setup, 12, "cells_setup", rows=2 * big_n), self._t_bytes(cells_setup_inf, 2 * big_n, "cells_setup_inf")
+            proof = torch.empty((n << log2_m, 12), dtype=coeffs.dtype, device=coeffs.device)
+            inf = torch.empty(n << log2_m, dtype=torch.uint8, device=coeffs.device)
+            self._chk(self._lib.zkp_kzg_cells_batch_dev(self._h, self._tp(cells_setup), self._tp(cells_setup_inf), self._tp(coeffs), n, log2_n, log2_l, log2_ext,
+                                                        flags, self._tp(proof), self._tp(inf), self._stream()))
+            return proof, inf
+        cf = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        n_el = cf.size // 4
+        if cf.size % 4 or n_el % big_n:
+            raise ValueError("coeffs hold %d elements: no whole number of polynomials of 2^%d" % (n_el, log2_n))
+        n = n_el >> log2_n
+        setup = _np(cells_setup, 12)
+        if setup.shape[0] != 2 * big_n:
+            raise ValueError("the cell setup holds %d points for polynomials of 2^%d" % (setup.shape[0], log2_n))
+        sinf = _flags(cells_setup_inf, 2 * big_n, "kzg_cells")
+        proof, inf = np.empty((n << log2_m, 12), dtype=np.uint64), np.empty(n << log2_m, dtype=np.uint8)
+        self._chk(self._lib.zkp_kzg_cells_batch(self._h, _ptr(setup), _ptr(sinf), _ptr(cf), n, log2_n, log2_l, log2_ext, flags, _ptr(proof), _ptr(inf)))
+        return proof, inf
+
+    def kzg_cell_verify(self, monomial_g1_l, g2, tau_l_g2, c, cell_index, values, proof, log2_d, log2_l, *, bitrev=False, inf_c=None, inf_proof=None, rand=None,
+                        points_checked=False, vk_checked=False):
+        """n cells against one setup as ONE check (zkp_kzg_cell_verify_batch): monomial_g1_l (l, 12) = [tau^i] g1, g2 / tau_l_g2 (24,) with
+        tau_l_g2 = [tau^l] g2; commitments c and proofs (n, 12), cell_index (n,) 32-bit, values (n l, 4).  True iff the random combination
+        holds, every point is valid (unless points_checked / vk_checked), every value is below r, every index below 2^(log2_d - log2_l)
+        and no (a_j, b_j) is zero.  rand (n, 2) uint64, by default fresh from os.urandom (rlc_random) - never a seeded generator.  Host
+        arrays return a bool; resident torch tensors (all of them) an int32 tensor (1,) without synchronising."""
+        log2_d, log2_l = int(log2_d), int(log2_l)
+        if not 0 <= log2_l <= log2_d <= 62:
+            raise ValueError("cells: 0 <= log2_l <= log2_d expected")
+        l = 1 << log2_l
+        n = (c.numel() if _is_torch(c) else np.asarray(c).size) // 12
+        if n == 0:
+            return True
+        if rand is None:
+            rand = self.rlc_random(n)
+        flags = (_lib.NTT_BITREV if bitrev else 0) | (_lib.CELLS_POINTS_CHECKED if points_checked else 0) | (_lib.CELLS_VK_CHECKED if vk_checked else 0)
+        if _is_torch(c):
+            import torch
+            dev = torch.device("cuda", self.device)
+            for name, x, w, rows in (("monomial_g1_l", monomial_g1_l, 12, l), ("g2", g2, 24, 1), ("tau_l_g2", tau_l_g2, 24, 1), ("c", c, 12, n),
+                                     ("values", values, 4, n * l), ("proof", proof, 12, n)):
+                self._t_check(x, w, name, rows=rows)
+                if x.numel() != rows * w:
+                    raise ValueError("%s holds %d elements, %d expected" % (name, x.numel() // w, rows))
+            self._t_check(cell_index, None, "cell_index", rows=n, dtypes=(torch.int32, torch.uint32))
+            self._t_bytes(inf_c, n, "inf_c"), self._t_bytes(inf_proof, n, "inf_proof")
+            if not _is_torch(rand):
+                rand = torch.from_numpy(np.ascontiguousarray(rand, dtype=np.uint64).reshape(-1).view(np.int64)).to(dev)
+            self._t_check(rand, 2, "rand", rows=n)
+            all_ok = torch.empty(1, dtype=torch.int32, device=dev)
+            self._chk(self._lib.zkp_kzg_cell_verify_batch_dev(self._h, self._tp(monomial_g1_l), self._tp(g2), self._tp(tau_l_g2), self._tp(c), self._tp(inf_c),
+                                                              self._tp(cell_index), self._tp(values), self._tp(proof), self._tp(inf_proof), n, log2_d, log2_l,
+                                                              flags, self._tp(rand), self._tp(all_ok), self._stream()))
+            return all_ok
+        arrs = {}
+        for name, x, w, rows in (("monomial_g1_l", monomial_g1_l, 12, l), ("g2", g2, 24, 1), ("tau_l_g2", tau_l_g2, 24, 1), ("c", c, 12, n),
+                                 ("values", values, 4, n * l), ("proof", proof, 12, n), ("rand", rand, 2, n)):
+            arrs[name] = _np(x, w)
+            if arrs[name].shape[0] != rows:
+                raise ValueError("%s holds %d elements, %d expected" % (name, arrs[name].shape[0], rows))
+        idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+        if idx.size != n:
+            raise ValueError("cell_index holds %d indices for %d cells" % (idx.size, n))
+        ic, ip = _flags(inf_c, n, "inf_c"), _flags(inf_proof, n, "inf_proof")
+        res = ctypes.c_int(0)
+        self._chk(self._lib.zkp_kzg_cell_verify_batch(self._h, _ptr(arrs["monomial_g1_l"]), _ptr(arrs["g2"]), _ptr(arrs["tau_l_g2"]), _ptr(arrs["c"]), _ptr(ic),
+                                                      _ptr(idx), _ptr(arrs["values"]), _ptr(arrs["proof"]), _ptr(ip), n, log2_d, log2_l, flags,
+                                                      _ptr(arrs["rand"]), ctypes.byref(res)))
+        return bool(res.value)
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

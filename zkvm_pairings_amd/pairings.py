@@ -658,6 +658,144 @@ def kzg_open_domain_batch(setup, coeffs, bitrev=True, engine=None):
     return proof.reshape(n, setup.n, 12), inf.reshape(n, setup.n)
 
 
+class CellSetup:
+    """What kzg_cell_proofs_batch needs of a setup for cells of l = 2^log2_l values: the 2N points (l vectors of 2 N / l, and their infinity
+    flags) that zkp_kzg_cells_setup derives from the monomial setup [tau^k] g1, k < N.  Build it once per setup and cell size with
+    kzg_cells_setup."""
+
+    def __init__(self, points, inf, log2_n, log2_l):
+        self.points, self.inf, self.log2_n, self.log2_l = points, inf, int(log2_n), int(log2_l)
+
+    @property
+    def n(self):
+        return 1 << self.log2_n
+
+    @property
+    def l(self):
+        return 1 << self.log2_l
+
+
+def kzg_cells_setup(monomial_g1, log2_l, engine=None):
+    """CellSetup of the monomial setup monomial_g1 (N, 12), N a power of two, for cells of 2^log2_l values (zkp_kzg_cells_setup).  The
+    points are trusted: check a ceremony's output once with g1_is_valid."""
+    e = engine or default_engine()
+    mono, log2_n = _pow2_points(monomial_g1, "kzg_cells_setup")
+    pts, inf = e.kzg_cells_setup(mono, log2_n, log2_l)
+    return CellSetup(pts, inf, log2_n, log2_l)
+
+
+def _cell_coeffs(setup, coeffs):
+    cf = np.ascontiguousarray(coeffs, dtype=np.uint64)
+    if cf.size % (4 * setup.n):
+        raise ValueError("%d coefficients: no whole number of polynomials of %d" % (cf.size // 4, setup.n))
+    return cf.reshape(-1, setup.n, 4)
+
+
+def kzg_cell_proofs_batch(setup, coeffs, log2_ext=1, bitrev=True, engine=None):
+    """(proofs (n, M, 12), inf (n, M)): polynomial j, given by its N coefficients coeffs[j], opened on every coset of l points of its
+    domain of D = 2^log2_ext N points by the Feist-Khovratovich multi-proof method (zkp_kzg_cells_batch), M = D / l: proofs[j][m] =
+    [q(tau)] g1 with q = (f_j - I) / (X^l - c_m^l), c_m = w_D^m' and m' = bitrev_M(m) with bitrev, as blobs are stored.  setup: a
+    CellSetup."""
+    e = engine or default_engine()
+    cf = _cell_coeffs(setup, coeffs)
+    proof, inf = e.kzg_cells(setup.points, setup.inf, cf.reshape(-1, 4), setup.log2_n, setup.log2_l, log2_ext, bitrev)
+    return proof.reshape(cf.shape[0], -1, 12), inf.reshape(cf.shape[0], -1)
+
+
+def kzg_cells_and_proofs_batch(setup, coeffs, log2_ext=1, bitrev=True, engine=None):
+    """(cells (n, M, l, 4), proofs (n, M, 12), inf (n, M)): kzg_cell_proofs_batch together with the cells themselves - fr_ntt of the
+    coefficients zero-padded to D = 2^log2_ext N, cut into rows of l.  With bitrev (the order blobs are stored in) cell m holds the
+    values on the coset of proof m; without it the transform's natural order interleaves the cosets, and the rows are gathered."""
+    e = engine or default_engine()
+    cf = _cell_coeffs(setup, coeffs)
+    n, big_n, l = cf.shape[0], setup.n, setup.l
+    big_d = big_n << log2_ext
+    big_m = big_d // l
+    padded = np.zeros((n, big_d, 4), dtype=np.uint64)
+    padded[:, :big_n] = cf
+    ev = e.fr_ntt(padded, setup.log2_n + log2_ext, bitrev=bitrev).reshape(n, big_d, 4) if n else padded
+    if bitrev:
+        cells = ev.reshape(n, big_m, l, 4)
+    else:           # value u of cell m is f(w_D^(m + M u))
+        cells = np.ascontiguousarray(ev.reshape(n, l, big_m, 4).transpose(0, 2, 1, 3))
+    proof, inf = kzg_cell_proofs_batch(setup, cf, log2_ext, bitrev, e)
+    return cells, proof, inf
+
+
+def _cell_arrays(commitments, cell_index, values, proofs, log2_l):
+    c, p = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 12) for x in (commitments, proofs))
+    idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 1 << log2_l, 4)
+    if not (c.shape[0] == p.shape[0] == idx.shape[0] == v.shape[0]):
+        raise ValueError("commitments, cell indices, cells and proofs differ in number")
+    return c, idx, v, p
+
+
+def kzg_cell_verify_batch(monomial_g1_l, g2, tau_l_g2, commitments, cell_index, values, proofs, log2_d, bitrev=True, engine=None, rand=None, inf_c=None,
+                          inf_proof=None, points_checked=False, vk_checked=False):
+    """True iff every one of the n cells (C_j, m_j, values_j, pi_j) holds against the setup (zkp_kzg_cell_verify_batch: one random
+    combination, one MSM call, one final exponentiation; a batch with a false cell passes with probability <= 2^-128).  monomial_g1_l
+    (l, 12) = [tau^i] g1, tau_l_g2 = [tau^l] g2; commitments / proofs (n, 12), cell_index (n,), values (n, l, 4), each below r; the
+    domain has 2^log2_d points.  kzg_cell_verify_each finds the bad cell when this returns False."""
+    e = engine or default_engine()
+    mono, log2_l = _pow2_points(monomial_g1_l, "kzg_cell_verify_batch")
+    c, idx, v, p = _cell_arrays(commitments, cell_index, values, proofs, log2_l)
+    return e.kzg_cell_verify(mono, g2, tau_l_g2, c, idx, v.reshape(-1, 4), p, log2_d, log2_l, bitrev=bitrev, inf_c=inf_c, inf_proof=inf_proof, rand=rand,
+                             points_checked=points_checked, vk_checked=vk_checked)
+
+
+def kzg_cell_verify_each(monomial_g1_l, g2, tau_l_g2, commitments, cell_index, values, proofs, log2_d, bitrev=True, engine=None, inf_c=None, inf_proof=None):
+    """bool array (n,): cell j holds.  The per-cell path, composed only of calls that do not know cells: the interpolant's coefficients
+    on Python integers (Lagrange's formula on the coset - no transform), -[I_j(tau)] g1 + [c_j^l] pi_j through msm (n sums of l + 1
+    terms), C_j added by g1_add, then pairing_check with k = 2 on (C_j - [I_j(tau)] g1 + [c_j^l] pi_j, -g2), (pi_j, [tau^l] g2), ANDed
+    with is_valid of every point, with values < r and with cell_index < M."""
+    e = engine or default_engine()
+    mono, log2_l = _pow2_points(monomial_g1_l, "kzg_cell_verify_each")
+    c, idx, v, p = _cell_arrays(commitments, cell_index, values, proofs, log2_l)
+    n, l, r = c.shape[0], 1 << log2_l, synthetic.R_ORDER
+    log2_m = int(log2_d) - log2_l
+    ok = np.ones(n, dtype=bool)
+    if n == 0:
+        return ok
+    g2, tau_l_g2 = (np.ascontiguousarray(x, dtype=np.uint64).reshape(24) for x in (g2, tau_l_g2))
+    ic = np.zeros(n, dtype=np.uint8) if inf_c is None else np.ascontiguousarray(inf_c, dtype=np.uint8).reshape(n)
+    ip = np.zeros(n, dtype=np.uint8) if inf_proof is None else np.ascontiguousarray(inf_proof, dtype=np.uint8).reshape(n)
+    ok &= not (e.g1_is_valid(mono).any() or e.g2_is_valid(np.stack([g2, tau_l_g2])).any())
+    ok &= (e.g1_is_valid(c, ic) == 0) & (e.g1_is_valid(p, ip) == 0)
+    ok &= synthetic.below_r(v.reshape(-1, 4)).reshape(n, l).all(axis=1) & (idx < (1 << log2_m))
+    w_d, w_l = synthetic.fr_root_of_unity(int(log2_d)), synthetic.fr_root_of_unity(log2_l)
+    sc = np.zeros((n, l + 1, 4), dtype=np.uint64)
+    for j in range(n):
+        m = int(idx[j]) & ((1 << log2_m) - 1)
+        shift = pow(w_d, synthetic.bit_reverse(m, log2_m) if bitrev else m, r)
+        pts = [shift * pow(w_l, synthetic.bit_reverse(u, log2_l) if bitrev else u, r) % r for u in range(l)]
+        coef = [0] * l                   # sum_u v_u prod_{t != u} (X - x_t) / (x_u - x_t)
+        for u, val in enumerate(synthetic._ints(v[j])):
+            num, den = [1], 1
+            for t, x in enumerate(pts):
+                if t != u:
+                    num = [(a - x * b) % r for a, b in zip([0] + num, num + [0])]
+                    den = den * (pts[u] - x) % r
+            scale = val % r * pow(den, -1, r) % r
+            coef = [(a + scale * b) % r for a, b in zip(coef, num)]
+        sc[j, :l] = synthetic._rows([-a % r for a in coef])
+        sc[j, l] = synthetic._rows([pow(shift, l, r)])[0]
+    pts = np.empty((n, l + 1, 12), dtype=np.uint64)
+    pts[:, :l], pts[:, l] = mono, p
+    inf = np.zeros((n, l + 1), dtype=np.uint8)
+    inf[:, l] = ip
+    s, s_inf = e.g1_msm(pts.reshape(-1, 12), sc.reshape(-1, 4), n, inf.reshape(-1))
+    lhs, lhs_inf = e.g1_add(c, s, ic, s_inf)
+    g1 = np.empty((n, 2, 12), dtype=np.uint64)
+    q2 = np.empty((n, 2, 24), dtype=np.uint64)
+    g1[:, 0], g1[:, 1] = lhs, p
+    q2[:, 0], q2[:, 1] = _g2_neg_array(g2), tau_l_g2
+    i1 = np.zeros((n, 2), dtype=np.uint8)
+    i1[:, 0], i1[:, 1] = lhs_inf, ip
+    per, _ = e.pairing_check(g1.reshape(-1, 12), q2.reshape(-1, 24), 2, i1.reshape(-1), np.zeros(2 * n, dtype=np.uint8))
+    return ok & (np.asarray(per).reshape(-1) != 0)
+
+
 def kzg_lagrange_setup(monomial_g1, bitrev=False, engine=None):
     """The Lagrange setup [l_i(tau)] g1 (N, 12) of the N-th roots of unity from the monomial setup [tau^k] g1: the inverse G1 NTT
     (zkp_g1_ntt_batch); with bitrev slot i holds the point of w^bitrev(i), the order blobs use.  Its output goes straight into kzg_commit_batch / kzg_open_batch.  Raises if a point

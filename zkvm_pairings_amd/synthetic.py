@@ -330,3 +330,24 @@ def kzg_blob_instance(seed, n, log2_n, bitrev=True, bad=(), engine=None):
         pexp.append((pt - yj) * pow(tau - z[j], -1, r) % r)
     setup, (cp, _), (pp, _) = _kzg_points(engine, tau, cexp, pexp)
     return setup, ew, cp, zw, _rows(y), pp
+
+
+def kzg_cells_instance(seed, n, log2_n, log2_l, bad=(), engine=None):
+    """n random polynomials of N = 2^log2_n coefficients with what the cell proofs need of a setup whose secret tau is derived from the
+    seed: the monomial setup [tau^k] G1, k < N (its first l = 2^log2_l points are the verifier's), G2 and [tau^l] G2, and the commitments
+    [f_j(tau)] G1 - the exponents on Python integers.  The polynomials listed in `bad` get C + G1.
+    -> (monomial_g1 (N, 12), g2 (24,), tau_l_g2 (24,), coeffs (n, N, 4), commitments (n, 12))."""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    r, big_n = R_ORDER, 1 << log2_n
+    (tau,) = _ints(scalars(seed ^ 0x7A2, 1))
+    cw = scalars(seed ^ 0x11, n * big_n).reshape(n, big_n, 4)
+    powers = [1] * big_n
+    for k in range(1, big_n):
+        powers[k] = powers[k - 1] * tau % r
+    bad = set(int(i) for i in bad)
+    cexp = [(sum(c * p for c, p in zip(_ints(cw[j]), powers)) + (1 if j in bad else 0)) % r for j in range(n)]
+    g1s, _ = engine.g1_mul(G1_GENERATOR, _rows(powers + cexp))
+    tg2, _ = engine.g2_mul(G2_GENERATOR, _rows([pow(tau, 1 << log2_l, r)]))
+    return g1s[:big_n].copy(), G2_GENERATOR.copy(), tg2[0].copy(), cw, g1s[big_n:].copy()
