@@ -231,6 +231,11 @@ def test_round_trip_through_the_batch_verifier_and_the_per_cell_path(eng, helper
     v2 = vals.copy()
     v2[2, 0] = fr_rows([R])[0]
     assert verify(c, idx, v2, prf) is False and not each(c, idx, v2, prf)[2]
+    same = int.from_bytes(vals[2, 0].tobytes(), "little") + R                          # the true value's residue, another input: only the canonical check sees it
+    assert same < 2 ** 256
+    v3 = vals.copy()
+    v3[2, 0] = fr_rows([same])[0]
+    assert verify(c, idx, v3, prf) is False and verify(c, idx, v3, prf, points_checked=True, vk_checked=True) is False and not each(c, idx, v3, prf)[2]
     i2 = idx.copy()
     i2[1] += big_m
     assert verify(c, i2, vals, prf) is False and not each(c, i2, vals, prf)[1]
