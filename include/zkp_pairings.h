@@ -363,6 +363,7 @@ int zkp_kzg_verify_batch_dev(zkp_ctx* ctx, const zkp_kzg_vk* vk, const zkp_kzg_b
 /* the Groth16 producer side - the Fr sparse product, the QAP quotient, the batched prover - is declared in zkp_prove.h, a third header */
 /* the group-transform layer - the batched NTT over G1 points and the FK20 proofs at every domain point - is declared in zkp_fk20.h, a fourth header */
 /* the cell layer - FK20 multi-proofs on cosets of the extended domain and their batch verifier - is declared in zkp_cells.h, a fifth header */
+/* the recovery layer - erased blobs back from any half of their cells - is declared in zkp_recover.h, a sixth header */
 
 /* ---- uncompressed point byte codec (big-endian field elements, reference src/fp.rs:165-207 with the range
  * check done CORRECTLY - upstream's Fp::from_bytes accepts exactly the non-canonical values).

@@ -12,6 +12,7 @@ pub mod poly;
 pub mod prove;
 pub mod fk20;
 pub mod cells;
+pub mod recover;
 
 #[repr(C)]
 pub struct ZkpCtx {

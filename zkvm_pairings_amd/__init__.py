@@ -11,10 +11,12 @@ from .engine import KERNEL_AUTO, KERNEL_COOP, KERNEL_THREAD, PairingEngine  # no
 from .pairings import (R1CS, CellSetup, Fk20Setup, Fr, G1Affine, G2Affine, Groth16ProvingKey, Groth16VerifyingKey, Gt, KzgSetup, MillerLoopResult, final_exponentiation,  # noqa: E402
                        groth16_prove_batch, groth16_quotient_batch, groth16_verify_batch, groth16_verify_each, g1_ntt, kzg_commit_batch, kzg_fk20_setup, kzg_lagrange_setup, kzg_open_batch, kzg_open_domain_batch, kzg_verify_batch, kzg_verify_blob_batch, kzg_verify_each, msm,
                        kzg_cells_setup, kzg_cell_proofs_batch, kzg_cells_and_proofs_batch, kzg_cell_verify_batch, kzg_cell_verify_each,
+                       recover_polynomials_batch, recover_cells_and_kzg_proofs_batch,
                        multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
 __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "pairing", "multi_miller_loop", "msm",
            "final_exponentiation", "Fr", "Groth16VerifyingKey", "R1CS", "Groth16ProvingKey", "groth16_prove_batch", "groth16_quotient_batch", "groth16_verify_batch", "groth16_verify_each", "KzgSetup", "kzg_verify_batch", "kzg_verify_each",
            "kzg_verify_blob_batch", "kzg_commit_batch", "kzg_open_batch", "g1_ntt", "Fk20Setup", "kzg_fk20_setup", "kzg_open_domain_batch", "kzg_lagrange_setup", "CellSetup", "kzg_cells_setup", "kzg_cell_proofs_batch", "kzg_cells_and_proofs_batch",
-           "kzg_cell_verify_batch", "kzg_cell_verify_each", "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]
+           "kzg_cell_verify_batch", "kzg_cell_verify_each", "recover_polynomials_batch", "recover_cells_and_kzg_proofs_batch",
+           "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

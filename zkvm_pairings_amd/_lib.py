@@ -225,6 +225,12 @@ CELLS_SIGNATURES = {
     "zkp_kzg_cell_verify_batch_dev": (c_int, [c_vp] * 10 + [c_sz, c_u, c_u, c_int, c_vp, c_vp, c_vp]),
 }
 
+# name -> (restype, argtypes); MUST list every symbol include/zkp_recover.h declares (the sixth header of the same library)
+RECOVER_SIGNATURES = {
+    "zkp_das_recover_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_u, c_u, c_int, c_vp, c_vp]),
+    "zkp_das_recover_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_u, c_u, c_int, c_vp, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -252,7 +258,7 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
-                                  list(CELLS_SIGNATURES.items())):
+                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -19,6 +19,7 @@
 #include "../../include/zkp_prove.h"
 #include "../../include/zkp_fk20.h"
 #include "../../include/zkp_cells.h"
+#include "../../include/zkp_recover.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -36,6 +37,7 @@
 #include "zkp_prove_plan.hpp"
 #include "zkp_fk20.hpp"
 #include "zkp_cells.hpp"
+#include "zkp_recover.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -2975,6 +2977,55 @@ int zkp_kzg_cell_verify_batch(zkp_ctx* c, const uint64_t* monomial_g1_l, const u
     if ((rc = io.status()) || (rc = cell_validate(d, [&](const void* p, size_t n_fp) { return validate_dev(c, (const uint64_t*)p, n_fp); })) ||
         (rc = zkp::cell_check_dev(c, d, flags, c->d_flag + 1, c->stream)))
         return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the cell recovery (zkp_recover.hip, include/zkp_recover.h)
+namespace {
+bool recover_args_bad(const zkp_ctx* c, const void* values, const void* present, size_t n, unsigned log2_n, unsigned log2_l, int flags, const void* coeffs,
+                      const void* ok) {
+    return !c || zkp::rec::args_bad(n, log2_n, log2_l, flags) || (n && (!values || !present || !coeffs || !ok));
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_das_recover_batch_dev(zkp_ctx* c, const void* values, const void* present, size_t n, unsigned log2_n, unsigned log2_l, int flags, void* out_coeffs,
+                              void* out_ok, void* stream) {
+    if (recover_args_bad(c, values, present, n, log2_n, log2_l, flags, out_coeffs, out_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (!n) return ZKP_OK;
+    if (c->validate)
+        HIPCHK(c, zkp::rec_check_present((const uint64_t*)values, (const uint8_t*)present, n << (log2_n + 1 - log2_l), log2_l, c->d_flag + 2, S(stream)));
+    return zkp::recover_dev(c, (const uint64_t*)values, (const uint8_t*)present, n, log2_n, log2_l, flags, (uint64_t*)out_coeffs, (int32_t*)out_ok, S(stream));
+}
+// the values in slot 0, the mask in slot 1, the two outputs one after the other in slot 4
+int zkp_das_recover_batch(zkp_ctx* c, const uint64_t* values, const uint8_t* present, size_t n, unsigned log2_n, unsigned log2_l, int flags,
+                          uint64_t* out_coeffs, int32_t* out_ok) {
+    if (recover_args_bad(c, values, present, n, log2_n, log2_l, flags, out_coeffs, out_ok)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    const size_t rows = n << (log2_n + 1 - log2_l), off_ok = zkp::kzg::align256((n << log2_n) * 32);
+    HostIO io(c);
+    const void* dv = io.in(0, values, (rows << log2_l) * 32);
+    const void* dp = io.in(1, present, rows);
+    char* dout = (char*)io.slot(4, off_ok + n * sizeof(int32_t));
+    if (dout) {
+        io.get(out_coeffs, dout, (n << log2_n) * 32);
+        io.get(out_ok, dout + off_ok, n * sizeof(int32_t));
+    }
+    int rc;
+    if ((rc = io.status())) return rc;
+    if (c->validate) {
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+        HIPCHK(c, zkp::rec_check_present((const uint64_t*)dv, (const uint8_t*)dp, rows, log2_l, c->d_flag, c->stream));
+        int bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bad) { c->err = "input limbs >= r"; return ZKP_ERR_NONCANONICAL; }
+    }
+    if ((rc = zkp::recover_dev(c, (const uint64_t*)dv, (const uint8_t*)dp, n, log2_n, log2_l, flags, (uint64_t*)dout, (int32_t*)(dout + off_ok), c->stream))) return rc;
     return io.finish();
 }
 

@@ -917,6 +917,43 @@ class PairingEngine:
                                                       _ptr(arrs["rand"]), ctypes.byref(res)))
         return bool(res.value)
 
+    # ------------------------------------------------------------------ the cell recovery (include/zkp_recover.h)
+    def das_recover(self, values, present, log2_n, log2_l, bitrev=False):
+        """Erased blobs back from half their cells (zkp_das_recover_batch): values (n M l, 4), the extended blobs in cell order with
+        D = 2 N = 2^(log2_n + 1) points and M = D / l cells of l = 2^log2_l values each - the order of the cells and of the values inside a
+        cell follows bitrev exactly as in kzg_cells and kzg_cell_verify -, present (n M,) bytes, non-zero where the cell was received; the
+        bytes of a missing cell are never interpreted.  -> (coeffs (n N, 4), ok (n,) int32): blob j in coefficient form, canonical, and
+        ok[j] = 1 iff at least M / 2 of its cells are present and consistent with a polynomial of degree below N (too few: a zero row).
+        Resident torch tensors (both) stay on the GPU."""
+        log2_n, log2_l, _ = self._cell_shape(log2_n, log2_l)
+        flags, log2_m = _lib.NTT_BITREV if bitrev else 0, log2_n + 1 - log2_l
+        if _is_torch(values):
+            import torch
+            self._t_check(values, 4, "values")
+            n_el = values.numel() // 4
+            if n_el % (2 << log2_n):
+                raise ValueError("values hold %d elements: no whole number of extended blobs of 2^%d" % (n_el, log2_n + 1))
+            n = n_el >> (log2_n + 1)
+            if present is None:
+                raise ValueError("das_recover: present is required")
+            self._t_bytes(present, n << log2_m, "present")
+            coeffs = torch.empty((n << log2_n, 4), dtype=values.dtype, device=values.device)
+            ok = torch.empty(n, dtype=torch.int32, device=values.device)
+            self._chk(self._lib.zkp_das_recover_batch_dev(self._h, self._tp(values), self._tp(present), n, log2_n, log2_l, flags, self._tp(coeffs), self._tp(ok),
+                                                          self._stream()))
+            return coeffs, ok
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        n_el = v.size // 4
+        if v.size % 4 or n_el % (2 << log2_n):
+            raise ValueError("values hold %d elements: no whole number of extended blobs of 2^%d" % (n_el, log2_n + 1))
+        n = n_el >> (log2_n + 1)
+        if present is None:
+            raise ValueError("das_recover: present is required")
+        pr = _flags(present, n << log2_m, "das_recover")
+        coeffs, ok = np.empty((n << log2_n, 4), dtype=np.uint64), np.empty(n, dtype=np.int32)
+        self._chk(self._lib.zkp_das_recover_batch(self._h, _ptr(v), _ptr(pr), n, log2_n, log2_l, flags, _ptr(coeffs), _ptr(ok)))
+        return coeffs, ok
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

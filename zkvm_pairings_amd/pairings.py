@@ -722,6 +722,44 @@ def kzg_cells_and_proofs_batch(setup, coeffs, log2_ext=1, bitrev=True, engine=No
     return cells, proof, inf
 
 
+def recover_polynomials_batch(cell_indices, cells, log2_n, log2_l, bitrev=True, engine=None):
+    """(coeffs (n, N, 4), ok (n,) int32): blob j back from the cells a client holds of it (zkp_das_recover_batch) - cell_indices[j] the
+    distinct indices m < M = 2 N / l it received, cells[j] their values, (len(cell_indices[j]), l, 4), in the same order; N = 2^log2_n,
+    l = 2^log2_l, the order of the cells and of the values inside a cell by bitrev as kzg_cells_and_proofs_batch leaves them.  The cells
+    are scattered into the dense n x M x l layout and the mask is built from the indices.  ok[j] = 1 iff blob j had at least M / 2 cells
+    and they are consistent with a polynomial of degree below N; with too few cells the row is zero, with inconsistent ones unspecified."""
+    e = engine or default_engine()
+    log2_n, log2_l = int(log2_n), int(log2_l)
+    if not 0 <= log2_l <= log2_n:
+        raise ValueError("recover_polynomials_batch: 0 <= log2_l <= log2_n expected")
+    n, big_n, l = len(cell_indices), 1 << log2_n, 1 << log2_l
+    big_m = 2 * big_n // l
+    if len(cells) != n:
+        raise ValueError("%d index lists for %d lists of cells" % (n, len(cells)))
+    values, present = np.zeros((n, big_m, l, 4), dtype=np.uint64), np.zeros((n, big_m), dtype=np.uint8)
+    for j in range(n):
+        idx = np.ascontiguousarray(cell_indices[j], dtype=np.int64).reshape(-1)
+        v = np.ascontiguousarray(cells[j], dtype=np.uint64).reshape(-1, l, 4)
+        if v.shape[0] != idx.size:
+            raise ValueError("blob %d: %d indices for %d cells" % (j, idx.size, v.shape[0]))
+        if idx.size and (idx.min() < 0 or idx.max() >= big_m or np.unique(idx).size != idx.size):
+            raise ValueError("blob %d: cell indices must be distinct and below %d" % (j, big_m))
+        values[j, idx], present[j, idx] = v, 1
+    coeffs, ok = e.das_recover(values.reshape(-1, 4), present.reshape(-1), log2_n, log2_l, bitrev)
+    return coeffs.reshape(n, big_n, 4), ok
+
+
+def recover_cells_and_kzg_proofs_batch(setup, cell_indices, cells, bitrev=True, engine=None):
+    """(cells (n, M, l, 4), proofs (n, M, 12), inf (n, M), ok (n,)): every cell and every cell proof of n blobs from any half of their
+    cells - recover_polynomials_batch, then kzg_cells_and_proofs_batch on the recovered coefficients (extension 2).  setup: a CellSetup.
+    A blob that cannot be recovered is REPORTED, not raised: ok[j] = 0, and its cells and proofs are those of the row the recovery left
+    (all zero, hence identity proofs, when fewer than M / 2 cells came; meaningless when the cells were inconsistent) - check ok first."""
+    e = engine or default_engine()
+    coeffs, ok = recover_polynomials_batch(cell_indices, cells, setup.log2_n, setup.log2_l, bitrev, e)
+    out_cells, proof, inf = kzg_cells_and_proofs_batch(setup, coeffs, 1, bitrev, e)
+    return out_cells, proof, inf, ok
+
+
 def _cell_arrays(commitments, cell_index, values, proofs, log2_l):
     c, p = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 12) for x in (commitments, proofs))
     idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)

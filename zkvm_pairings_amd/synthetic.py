@@ -351,3 +351,28 @@ def kzg_cells_instance(seed, n, log2_n, log2_l, bad=(), engine=None):
     g1s, _ = engine.g1_mul(G1_GENERATOR, _rows(powers + cexp))
     tg2, _ = engine.g2_mul(G2_GENERATOR, _rows([pow(tau, 1 << log2_l, r)]))
     return g1s[:big_n].copy(), G2_GENERATOR.copy(), tg2[0].copy(), cw, g1s[big_n:].copy()
+
+
+def das_recover_instance(seed, n, log2_n, log2_l, bitrev=True, keep=None, engine=None):
+    """n random blobs of N = 2^log2_n coefficients, extended to D = 2 N points, cut into M = D / l cells of l = 2^log2_l values (in the
+    order bitrev names) and erased: every blob keeps `keep` cells drawn from the seed (M / 2 by default: a random half), the rows of the
+    others are filled with 0xff bytes.  The cells come from the engine's fr_ntt.
+    -> (values (n, M, l, 4), present (n, M) uint8, coeffs (n, N, 4): what das_recover must return)."""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    big_n, l = 1 << log2_n, 1 << log2_l
+    big_d = 2 * big_n
+    big_m = big_d // l
+    keep = big_m // 2 if keep is None else int(keep)
+    cw = scalars(seed ^ 0xDA5, n * big_n).reshape(n, big_n, 4)
+    padded = np.zeros((n, big_d, 4), dtype=np.uint64)
+    padded[:, :big_n] = cw
+    ev = engine.fr_ntt(padded.reshape(-1, 4), log2_n + 1, bitrev=bitrev).reshape(n, big_d, 4) if n else padded
+    values = ev.reshape(n, big_m, l, 4).copy() if bitrev else np.ascontiguousarray(ev.reshape(n, l, big_m, 4).transpose(0, 2, 1, 3))
+    rng = np.random.RandomState((seed ^ 0xE7A5) & 0x7FFFFFFF)
+    present = np.zeros((n, big_m), dtype=np.uint8)
+    for j in range(n):
+        present[j, rng.permutation(big_m)[:keep]] = 1
+    values[present == 0] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    return values, present, cw
