@@ -33,13 +33,22 @@ static void __syncthreads() { pthread_barrier_wait(&g_bar); }
 
 using namespace zkp;
 template <class F> static void launch(unsigned grid, unsigned block, F f) {
-    for (unsigned b = 0; b < grid; b++) {
-        pthread_barrier_init(&g_bar, nullptr, block);
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < block; t++) th.emplace_back([=] { threadIdx.x = t; blockIdx.x = b; blockDim.x = block; f(); });
-        for (auto& x : th) x.join();
-        pthread_barrier_destroy(&g_bar);
-    }
+    // the lanes' threads live for the whole launch (starting 256 of them per workgroup is most of a small workgroup's time); the barrier
+    // behind a workgroup keeps a fast lane of the next one out of the `__shared__` arrays that a slow lane of this one still reads
+    pthread_barrier_init(&g_bar, nullptr, block);
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < block; t++)
+        th.emplace_back([=] {
+            threadIdx.x = t;
+            blockDim.x = block;
+            for (unsigned b = 0; b < grid; b++) {
+                blockIdx.x = b;
+                f();
+                pthread_barrier_wait(&g_bar);
+            }
+        });
+    for (auto& x : th) x.join();
+    pthread_barrier_destroy(&g_bar);
 }
 int main(int argc, char** argv) {
     if (argc < 7) return 2;

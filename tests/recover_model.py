@@ -59,10 +59,24 @@ def vanishing(missing, mu):
 def recover(values, present, log2_n, log2_l, bitrev):
     """values: M rows of l integers (the row of a missing cell is never looked at: it may be None), present: M flags.
     -> (the N coefficients, ok) exactly as zkp_das_recover_batch leaves them for a consistent or an underdetermined blob"""
+    n, l, k, _, _, _ = sizes(log2_n, log2_l)
+    cols = decode(values, present, log2_n, log2_l, bitrev)
+    if cols is None:
+        return [0] * n, 0
+    f = [0] * n
+    for i, p in enumerate(cols):
+        for t in range(k):
+            f[i + l * t] = p[t]
+    return f, 0 if any(any(p[k:]) for p in cols) else 1
+
+
+def decode(values, present, log2_n, log2_l, bitrev):
+    """the l decoded columns p (M entries each: p_t is f_{i + l t} for t < M / 2, the tail behind it is zero iff the cells are consistent),
+    or None when fewer than M / 2 cells are present"""
     n, l, k, _, big_m, mu = sizes(log2_n, log2_l)
     assert len(values) == len(present) == big_m
     if sum(1 for p in present if p) < k:
-        return [0] * n, 0
+        return None
     mp = [pm.bit_reverse(m, mu) if bitrev else m for m in range(big_m)]
     z = vanishing([mp[m] for m in range(big_m) if not present[m]], mu)
     zr, zs = pm.ntt(z, mu), pm.ntt(z, mu, coset=True)
@@ -72,15 +86,11 @@ def recover(values, present, log2_n, log2_l, bitrev):
         if present[m]:
             for i, v in enumerate(cm.interpolant_coefficients(values[m], m, log2_n, log2_l, 1, bitrev)):
                 cols[i][mp[m]] = v * zr[mp[m]] % R
-    f, ok = [0] * n, 1
-    for i, col in enumerate(cols):
+    out = []
+    for col in cols:
         q = pm.ntt(col, mu, inverse=True)
-        p = pm.ntt([a * b % R for a, b in zip(pm.ntt(q, mu, coset=True), zs_inv)], mu, inverse=True, coset=True)
-        if any(p[k:]):
-            ok = 0
-        for t in range(k):
-            f[i + l * t] = p[t]
-    return f, ok
+        out.append(pm.ntt([a * b % R for a, b in zip(pm.ntt(q, mu, coset=True), zs_inv)], mu, inverse=True, coset=True))
+    return out
 
 
 def interpolant_of_half(values, present, log2_n, log2_l, bitrev):

@@ -7,6 +7,7 @@
 // of its mu stages exactly once in the order of its decimation.
 //   recover_plan_check            the walk; prints "recover plan_check ok: <cases> cases"
 //   recover_plan_check shapes     reads "n log2_n log2_l" lines, prints "n log2_n log2_l slice cols groups" for each
+//   recover_plan_check tiles      reads "log2_n log2_l" lines, prints "log2_n log2_l mu cl cols groups" as the column kernel receives them
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -125,6 +126,15 @@ int main(int argc, char** argv) {
             if (rec::args_bad(n, log2_n, log2_l, 0) || !n) return 2;
             const rec::Shape s = rec::shape_of(log2_n, log2_l);
             printf("%lu %u %u %zu %u %u\n", n, log2_n, log2_l, rec::layout(n, log2_n, log2_l, 0).slice, s.cols, s.groups);
+        }
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "tiles")) {
+        unsigned log2_n, log2_l;
+        while (scanf("%u %u", &log2_n, &log2_l) == 2) {
+            if (rec::args_bad(1, log2_n, log2_l, 0)) return 2;
+            const rec::Column a = rec::column_of(log2_n, log2_l, 0, log2_n + 1);
+            printf("%u %u %u %u %u %u\n", log2_n, log2_l, a.mu, a.cl, a.cols, a.groups);
         }
         return 0;
     }

@@ -2,7 +2,8 @@
 header) against the DEFINITION - the cells as evaluations on cosets, erase, recover, equal to f; the underdetermined and the corrupted
 cases against Lagrange's formula; the planner (csrc/zkp_recover_plan.hpp) walked to the ABI maxima under ASan and UBSan
 (tests/recover_plan_check.cpp, a child process); the two kernels' own text on host threads under the same sanitizers
-(tests/recover_kernel_host.cpp) against the model's bytes; the new header, the ctypes table and the Rust file against one another; the
+(tests/recover_kernel_host.cpp) against the model's bytes at every column size, and on single-coefficient forgeries
+(tests/recover_forgeries.py: every column, every tail position) and on mask bytes other than 1; the new header, the ctypes table and the Rust file against one another; the
 replay table against the header; the new kernels' registers."""
 import ctypes
 import os
@@ -10,6 +11,7 @@ import random
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 import cells_model as cm
@@ -111,6 +113,106 @@ def test_the_instances_of_the_gpu_tests_are_what_they_claim():
         assert [w[1].tolist() for w in want][1].count(0) == 1            # set B holds the blob with too few cells
 
 
+@pytest.mark.parametrize("bitrev", [False, True])
+@pytest.mark.parametrize("log2_n,log2_l", rs.CPU_SHAPES)
+def test_model_on_single_coefficient_forgeries(log2_n, log2_l, bitrev):
+    """f + a X^(i0 + l t0), k <= t0 < M, with k + s cells present (tests/recover_forgeries.py): s = 0 is the other interpolant; t0 < k + s
+    leaves ONE non-zero tail entry, column i0 at t0, and f below it; t0 >= k + s wraps into the tail entries below k + s of column i0 alone"""
+    import recover_forgeries as rf
+    rng = random.Random(0xF06 + 16 * log2_n + log2_l + bitrev)
+    n, l, k, _, big_m, _ = rm.sizes(log2_n, log2_l)
+    f = [rng.randrange(R) for _ in range(n)]
+    cells = rm.cells_of(f, log2_n, log2_l, bitrev)
+    assert rf.forge([[0] * l] * big_m, 1, n - 1, log2_n, log2_l, bitrev) == rm.cells_of([0] * (n - 1) + [1], log2_n, log2_l, bitrev)
+    lagrange = 0
+    for s in sorted({0, 1, 2, k} & set(range(k + 1))):
+        for i0, t0, e in rf.tail_exps(log2_n, log2_l):
+            present = rf.keep_cells(big_m, k + s, rng)
+            bad = rf.forge(cells, 1 + rng.randrange(R - 1), e, log2_n, log2_l, bitrev)
+            cols = rm.decode(erased(bad, present), present, log2_n, log2_l, bitrev)
+            tail = {(i, t) for i in range(l) for t in range(k, big_m) if cols[i][t]}
+            got, ok = rm.recover(erased(bad, present), present, log2_n, log2_l, bitrev)
+            if s == 0:
+                assert not tail and ok == 1 and got != f, (s, i0, t0)
+                if lagrange < 2:                                         # Lagrange's formula is cubic: twice per shape
+                    assert got == rm.interpolant_of_half(bad, present, log2_n, log2_l, bitrev)
+                    lagrange += 1
+            elif t0 < k + s:
+                assert tail == {(i0, t0)} and ok == 0 and got == f, (s, i0, t0)
+            else:
+                assert tail and {i for i, _ in tail} == {i0} and ok == 0, (s, i0, t0)
+                assert all(got[i + l * t] == f[i + l * t] for i in range(l) if i != i0 for t in range(k)), (s, i0, t0)
+                # the decode has degree below k + s: s tail entries to wrap into (Y^t0 modulo the present cells' vanishing polynomial,
+                # whose coefficients are symmetric functions of roots of unity: some of them may vanish)
+                assert all(t < k + s for _, t in tail), (s, i0, t0)
+
+
+def test_the_forgery_instances_are_what_they_claim():
+    """tests/recover_forgeries.py: the gathered monomials against the transform, the fast canonical test against the slow one, the sweeps'
+    cover of every tail position, the edge lanes' coefficients against the planner's tile, the instances of the contracts"""
+    import recover_forgeries as rf
+    import recover_replay_cases as rrc
+    from replay_cases import fr_rows
+    for (log2_n, log2_l), bitrev in [((4, 2), False), ((4, 2), True), ((5, 0), True), ((3, 3), False), ((3, 3), True), ((6, 3), True)]:
+        n = 1 << log2_n
+        exps = [0, 1, n - 1, n, 2 * n - 1, n + 3]
+        got = rf.monomial_cells(exps, log2_n, log2_l, bitrev)
+        for j, e in enumerate(exps):
+            f = [1 if d == e else 0 for d in range(2 * n)]                # as a polynomial of degree below D: its D evaluations, cut into cells
+            ev = pm.ntt(f, log2_n + 1, bitrev=bitrev)
+            l, big_m = 1 << log2_l, 2 * n >> log2_l
+            cells = [ev[l * m:l * m + l] for m in range(big_m)] if bitrev else [[ev[m + big_m * u] for u in range(l)] for m in range(big_m)]
+            assert got[j].tobytes() == fr_rows([v for row in cells for v in row]).tobytes(), (log2_n, log2_l, bitrev, e)
+            assert cells == rf.monomial_rows(e, log2_n, log2_l, bitrev)
+            if e < n:
+                assert cells == rm.cells_of(f[:n], log2_n, log2_l, bitrev)
+    edge = fr_rows([0, R - 1, R, R + 1, (1 << 256) - 1, R - (1 << 64), R + (1 << 64), R - (1 << 192), R + (1 << 192)])
+    for j in range(len(edge)):
+        assert rf.canonical(edge[j]) == rrc.below_r(edge[j]) == (j in (0, 1, 5, 7)), j
+    assert not rf.canonical(edge) and rf.canonical(edge[[0, 1, 5, 7]]) and not rf.canonical(np.full((3, 4), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64))
+    for log2_n, log2_l, cols in rs.FORGERY_SWEEPS:
+        n, l, k, _, big_m, mu = rm.sizes(log2_n, log2_l)
+        tails = rf.tail_exps(log2_n, log2_l, cols)
+        assert {(i0, t0) for i0, t0, _ in tails} == {(i0, t0) for i0 in (cols or range(l)) for t0 in range(k, big_m)}      # no tail position left out
+        assert all(e == i0 + l * t0 and n <= e < 2 * n for i0, t0, e in tails) and (0, k, n) in tails
+        twins = rf.twin_exps(log2_n, log2_l)
+        assert n - 1 in twins and max(twins) == n - 1 and len([e for e in twins if e % 8 == 5 * (e // 8) % 8]) >= n // 8
+        # the edge lanes: elements q + 256 u of the tile the planner describes (c = e mod 2^cl, p = e >> cl), in every workgroup
+        cl, c_wg = 10 - mu, min(l, 1 << (10 - mu))
+        for g in range(l // c_wg):
+            for e in (0, 255, 256, 511, 512, 767, 768, 1023):
+                c, t = e & ((1 << cl) - 1), pm.bit_reverse(e >> cl, mu)
+                if c < c_wg and t < k:
+                    assert g * c_wg + c + l * t in rf.edge_lane_exps(log2_n, log2_l)
+        assert rf.edge_lane_exps(log2_n, log2_l) and set(rf.edge_lane_exps(log2_n, log2_l)) <= set(twins)
+    assert rs.FORGERY_SWEEPS[3][2] == (0, 7, 8, 63)                        # PeerDAS: 8 columns per workgroup, 64 columns
+    inst = rf.sweep(6, 3, True)
+    n_f, n_t = 64, len(rf.twin_exps(6, 3))
+    assert inst["ok"].size == n_f + n_t and inst["ok"].sum() == n_t and len(inst["free"]) == n_f and inst["present"].all()
+    assert (inst["ok"] == (inst["exps"] < 64)).all() and sorted(inst["exps"][inst["free"]].tolist()) == list(range(64, 128))
+    assert np.count_nonzero(np.diff(inst["ok"])) >= 8                      # good blobs stand between forged ones
+    co = inst["coeffs"].reshape(n_f + n_t, 64, 4)
+    for j in np.nonzero(inst["ok"])[0]:
+        assert co[j].sum() == 1 and co[j, inst["exps"][j], 0] == 1
+    # the contracts
+    small = rrc.instance(("random-half", "few", "one"), *rs.SMALL, True, 0x3A5)
+    other = rf.other_mask_bytes(small)
+    assert other["present"].tobytes() != small["present"].tobytes() and other["values"] is small["values"] and set(other["present"].tolist()) == {0, 1, 2, 0x80, 0xFF}
+    mixed = rf.mixed_instance(*rs.SMALL, True)
+    assert mixed["ok"].tolist() == [0, 1, 0, 0, 1, 0, 1, 0] and mixed["free"] == [2, 5]
+    assert not mixed["coeffs"].reshape(8, -1)[[0, 3, 7]].any() and mixed["coeffs"].reshape(8, -1)[[1, 4, 6]].any(axis=1).all()
+    st = rf.structured_instance(*rs.SMALL, False)
+    n_co, _, k, _, big_m, _ = rm.sizes(*rs.SMALL)
+    zero = [j for j, name in enumerate(st["labels"]) if name.startswith("zero")]
+    assert len(zero) == 8 and st["ok"][zero].tolist() == [1] * 5 + [0] + [1] * 2 and not st["coeffs"].reshape(-1, n_co * 4)[zero].any() and not st["free"]
+    assert st["present"].reshape(-1, big_m)[zero[-2:]].sum(axis=1).tolist() == [k, k]
+    assert len(rf.STRUCTURED) == 19 and max(rf.STRUCTURED) == R - 1 and len(set(rf.STRUCTURED)) == 19 and all(v < R for v in rf.STRUCTURED)
+    lim = rf.limit_instance(*rs.LIMIT, rs.LIMIT_MISSING, True)
+    gone = (lim["present"].reshape(-1, 1024) == 0).sum(axis=1).tolist()
+    assert gone == list(rs.LIMIT_MISSING) + [512, 512] and lim["ok"].tolist() == [1 if g <= 512 else 0 for g in gone] and not lim["free"]
+    assert {1024 - g for g in gone} >= {1024, 1023, 769, 768, 767, 683, 513, 512, 511}
+
+
 # ------------------------------------------------------------------------------------------------------------------- the planner
 def _clean(out):
     assert out.returncode == 0 and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stdout[-3000:] + out.stderr[-3000:]
@@ -154,6 +256,22 @@ def test_the_shapes_of_the_gpu_tests_reach_what_they_claim(plan_exe):
     assert by[(rs.SLICE_LOG2_N, rs.SLICE_LOG2_L)][0] == rs.SLICE_LEN == (1 << 21) >> (rs.SLICE_LOG2_N + 1)
     with open(HEADER) as f:
         assert "floor(2^21 / D)" in f.read()
+    # every column size: the table states mu, cl, the columns of a workgroup and the workgroups of a blob; the planner confirms each row
+    want = list(rs.EVERY_MU) + [(6, 3, 4, 6, 8, 1), (10, 2, 9, 1, 2, 2), (10, 1, 10, 0, 1, 2), (12, 6, 7, 3, 8, 8), (4, 2, 3, 7, 4, 1), (10, 10, 1, 9, 512, 2)]
+    assert [w[:2] for w in want[len(rs.EVERY_MU):]] == [s[:2] for s in rs.FORGERY_SWEEPS] + [rs.SMALL, rs.FORGERY_HOST_GROUPS]
+    assert rs.LIMIT == (10, 1) and set(rs.FORGERY_ERASED) == {(6, 3), rs.SMALL}
+    out = subprocess.run([plan_exe, "tiles"], input="".join("%d %d\n" % w[:2] for w in want), capture_output=True, text=True, timeout=900)
+    _clean(out)
+    assert [tuple(int(x) for x in line.split()) for line in out.stdout.split("\n") if line] == want
+    assert len(set(rs.EVERY_MU)) == len(rs.EVERY_MU) and {w[2] for w in rs.EVERY_MU} == set(range(1, 11))
+    for log2_n, log2_l, mu, cl, cols, groups in rs.EVERY_MU:
+        assert mu == log2_n + 1 - log2_l and cl == 10 - mu and log2_n + 1 <= 13, (log2_n, log2_l)
+    for mu in range(1, 11):
+        rows = [w for w in rs.EVERY_MU if w[2] == mu]
+        assert {w[1] for w in rows} == {0, 1, 3, 11 - mu}, mu                          # l = 1, 2, 8 and 2^(cl + 1)
+        assert any(w[5] >= 2 and w[4] == 1 << w[3] for w in rows), mu                  # two workgroups or more, every column slot taken
+        assert mu == 10 or any(w[4] < 1 << w[3] for w in rows), mu                     # idle column slots (M = 1024: the tile is ONE column)
+    assert {w[2] for w in rs.EVERY_MU if w[3] in (1, 2) and w[5] >= 2} == {8, 9}      # M = 256 and M = 512 with more than one workgroup
 
 
 def test_the_sliced_call_of_the_gpu_test_crosses_a_slice_boundary():
@@ -187,8 +305,8 @@ def kernel_exe(tmp_path_factory):
 @pytest.mark.parametrize("bitrev", [False, True])
 @pytest.mark.parametrize("log2_n,log2_l,n", rs.KERNEL_HOST_SHAPES)
 def test_kernels_on_host_threads_equal_the_model(kernel_exe, tmp_path, log2_n, log2_l, n, bitrev):
-    """k_rec_vanish, k_rec_zinv and k_rec_column as written in zkp_recover.hip, one host thread per lane: M = 2, 8 and 128 with l = 1 and
-    l = 4; what the driver's borrowed transform computes in between (the cells' inverse transforms, Z on the roots and on the coset)
+    """k_rec_vanish, k_rec_zinv and k_rec_column as written in zkp_recover.hip, one host thread per lane: every M = 2^mu, mu = 1 .. 10, with l = 1
+    and l = 4 (every round schedule of column_transform, every count of column slots); what the driver's borrowed transform computes in between (the cells' inverse transforms, Z on the roots and on the coset)
     comes from the model.  The third blob of a case has too few cells, missing cells hold bytes above r"""
     import recover_replay_cases as rrc
     n_co, l, k, _, big_m, mu = rm.sizes(log2_n, log2_l)
@@ -243,6 +361,57 @@ def test_the_column_kernel_flags_inconsistent_cells_on_host_threads(kernel_exe, 
     at = 32 * big_m
     assert raw[at:at + 4] == (1).to_bytes(4, "little") and raw[-4:] == (0).to_bytes(4, "little")
     assert all(v < R for v in pm.from_bytes(raw[2 * at + 4:-4]))
+
+
+def _kernels_on_host_threads(kernel_exe, tmp_path, inst, log2_n, log2_l, bitrev, what):
+    """an instance through the three kernels on host threads: the flags k_rec_vanish leaves (enough cells), then rows and flags as the
+    instance states them"""
+    import recover_forgeries as rf
+    data, enough = rf.kernel_host_input(inst, log2_n, log2_l, bitrev)
+    n = inst["ok"].size
+    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
+    fin.write_bytes(data)
+    out = subprocess.run([kernel_exe, str(fin), str(fout), str(log2_n), str(log2_l), str(n), str(int(bitrev))], capture_output=True, text=True, timeout=900)
+    _clean(out)
+    ok_vanish, co, ok = rf.kernel_host_output(fout.read_bytes(), n, log2_n, log2_l)
+    assert ok_vanish.tolist() == enough.tolist(), what
+    rf.check(co, ok, inst, what)
+
+
+@pytest.mark.parametrize("bitrev", [False, True])
+@pytest.mark.parametrize("log2_n,log2_l", rs.FORGERY_ERASED + [rs.FORGERY_HOST_GROUPS])
+def test_the_column_kernel_flags_every_single_coefficient_forgery_on_host_threads(kernel_exe, tmp_path, log2_n, log2_l, bitrev):
+    """X^(i0 + l t0) for EVERY column i0 and EVERY tail position t0 with all cells present - one non-zero element of the decoded tails, in
+    one lane of one workgroup - between monomials below N, which come back as unit rows with ok = 1 (X^(N-1) accepted, X^N refused: the
+    boundary of the tail); then the same sweep on a random polynomial with a random factor and the last cell missing.  (4, 2) and (6, 3)
+    have one workgroup per blob, (10, 10) two: there a forgery of the second workgroup's columns is one the first never sees"""
+    import recover_forgeries as rf
+    cols = (0, 511, 512, 1023) if (log2_n, log2_l) == rs.FORGERY_HOST_GROUPS else None
+    inst = rf.sweep(log2_n, log2_l, bitrev, cols)
+    if cols:                                                             # 4 forgeries; of the twins the first 12 beside them
+        keep = sorted(inst["free"] + np.nonzero(inst["ok"])[0][:12].tolist())
+        n_co, d = 1 << log2_n, 2 << log2_n
+        inst = dict(values=inst["values"].reshape(-1, d, 4)[keep].reshape(-1, 4), present=inst["present"].reshape(-1, 2)[keep].reshape(-1),
+                    coeffs=inst["coeffs"].reshape(-1, n_co, 4)[keep].reshape(-1, 4), ok=inst["ok"][keep], free=[keep.index(j) for j in inst["free"]],
+                    labels=[inst["labels"][j] for j in keep])
+        assert len(inst["free"]) == 4 and inst["ok"].tolist().count(1) == 12
+    _kernels_on_host_threads(kernel_exe, tmp_path, inst, log2_n, log2_l, bitrev, "all cells present")
+    if not cols:
+        _kernels_on_host_threads(kernel_exe, tmp_path, rf.erased_sweep(log2_n, log2_l, bitrev, "one"), log2_n, log2_l, bitrev, "the last cell missing")
+
+
+@pytest.mark.parametrize("bitrev", [False, True])
+def test_any_non_zero_mask_byte_is_a_present_cell_on_host_threads(kernel_exe, tmp_path, bitrev):
+    """present[j][m] = 2, 0x80 or 0xFF where it was 1: the three kernels, which each read the mask, leave what they left - the count of a
+    blob with too few cells is a count of CELLS, not a sum of bytes"""
+    import recover_forgeries as rf
+    import recover_replay_cases as rrc
+    inst = rrc.instance(("few", "random-half", "one", "few", "none", "half-bad"), *rs.SMALL, bitrev, 0x3A5)
+    assert inst["ok"].tolist() == [0, 1, 1, 0, 1, 1]
+    other = rf.other_mask_bytes(inst)
+    n, big_m = 6, 2 << (rs.SMALL[0] - rs.SMALL[1])
+    assert (other["present"].reshape(n, big_m).astype(np.int64).sum(axis=1)[[0, 3]] >= big_m // 2).all()      # a sum of bytes would call them enough
+    _kernels_on_host_threads(kernel_exe, tmp_path, other, *rs.SMALL, bitrev, "mask bytes")
 
 
 # ------------------------------------------------------------------------------------------------------------------- the boundary
