@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A CPU model of the gfx950 instruction subset that tools/coopasm.py emits - the gate for the generated inline-asm blocks.
 
-It executes the text of a generated block (straight-line code: no branches) on a group of lanes: 32-bit VGPRs per lane, SGPRs,
+It executes the text of a generated block (scalar branches and loops included) on a group of lanes: 32-bit VGPRs per lane, SGPRs,
 EXEC, an LDS byte image, DPP quad permutations.  Two things a GPU run would only show as wrong numbers are errors here:
 a DPP read from a lane that EXEC has switched off, and a read of a register nothing has written.
 
@@ -94,7 +94,8 @@ class Emu:
         self.v.setdefault(int(m.group(1)), [None] * self.n)[lane] = val & M32
 
     # ---- execution
-    def run(self, lines, max_steps=10_000_000):
+    def run(self, lines, max_steps=10_000_000, watch=None):
+        """watch: {label: function(emu)} - called whenever execution passes the label (looping code: once per pass)"""
         prog = [self._sub(l).strip() for l in lines]
         prog = [l for l in prog if l]
         labels = {l[:-1]: i for i, l in enumerate(prog) if l.endswith(":")}
@@ -103,6 +104,8 @@ class Emu:
             line = prog[pc]
             pc += 1
             if line.endswith(":"):
+                if watch and line[:-1] in watch:
+                    watch[line[:-1]](self)
                 continue
             n += 1
             assert n < max_steps, "runaway loop"

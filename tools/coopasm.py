@@ -21,6 +21,8 @@ The arithmetic is one level of Karatsuba over the limb halves: a_lo b_lo and a_h
 folded in by additions only (mod 2^64: the true column values fit), then acc_reduce.  The columns, the m_i and the balanced limbs
 are EXACTLY those of acc_mul + acc_reduce, so tools/coopgen.py's emulator stays the gate.
 
+generate_miller1() strings the same term and tail into the whole Miller loop of one-pair checks (k_miller1) -> csrc/zkp_miller1.inc.
+
 Reference anchors (what the step computes): Fp12::mul_by_014 src/fp12.rs:99-111, Fp12::square :173-184, Fp12 Mul :193-210.
 """
 import os
@@ -600,6 +602,326 @@ def write_ksq(f, vb=6):
     return g
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# k_miller1: the Miller loop of ONE-pair checks as one block.  Lane mapping, LDS image (30 slots, 4 constants), limb arithmetic
+# and order of operations are those of prog_miller(1, False) on the step interpreter - the stored limbs are the same - but
+# nothing is interpreted and no step stands between two MULACC bodies:
+#   * an iteration is straight-line code: line product (6 terms), tail, stores; accumulator squaring (7 terms), tail, stores;
+#     an addition iteration runs the line product twice.  Which terms negate or double is known here, so the header bits,
+#     their branches and the (never used) second operands of term() are gone;
+#   * the operand addresses of the 13 terms are the same in every iteration: one row of (A1, B1) per term, as byte offsets
+#     inside a lane group, sits in the PADDING of the LDS image (a group's 30 slots are padded to 36: six records per group
+#     and plane hold the 12 x 8 bytes of a row).  A term fetches the next row with one ds_read_b64 and adds the group base:
+#     the loop has no VMEM access of its own, so no wait of the arithmetic ever meets a line load;
+#   * the six 64-byte line records of a check are fetched by its twelve lanes, half a record each (two global_load_dwordx4
+#     into eight landing registers), for line step s + 1 as soon as step s has left the landing registers: the loads have a
+#     whole line product and (in a plain iteration) a squaring to arrive.  At the start of line product s + 1 they are waited
+#     for and written to the six line slots of the image (two ds_write_b128 per lane);
+#   * the result and companion stores are generate()'s; the conjugation, weak normalisation and the twelve state records of
+#     finish_output(f.conj(), to_wire=False, ST_F) follow the last line product from the result registers.
+# Registers: the 156 of the MULACC block (E + 2, vz and F + 1, which the interpreter's block needs for second operands and
+# store words, hold lane constants here), v0..v7 for the landing records and three more lane constants: 167 in all.
+M1_NEG, M1_DA, M1_CONJ = 0, 13, 31        # flag word: bit M1_NEG + term = negate A, M1_DA + term = double A, M1_CONJ = negate the output
+
+
+def miller1_tables():
+    """the two MULACC steps of an iteration of prog_miller(1, False) as per-lane rows: rows[term][lane in group] = (A1, B1)
+    byte offsets of the records inside the group's slots, flags[lane in group], the terms that negate / double somewhere"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import coopgen as cg
+    steps = cg.prog_miller(1, False).steps
+    gl, line, sq = steps[2], steps[3], steps[6]
+    assert gl["op"] == cg.OP_GLOAD and [d for d, _ in gl["lanes"]] == list(range(24, 30)) and [i for _, i in gl["lanes"]] == [(0, c) for c in range(6)]
+    assert line["op"] == cg.OP_MULACC and line["T"] == 6 and sq["op"] == cg.OP_MULACC and sq["T"] == 7
+    rows, flags, neg_any, da_any = [], [0] * 12, [], []
+    for st in (line, sq):
+        assert not st["epi"] and st["sd"] == list(range(12, 24)) and [ln["dst"] for ln in st["lanes"]] == list(range(12))
+        for t in range(st["T"]):
+            ti, row = len(rows), []
+            for lig, ln in enumerate(st["lanes"]):
+                if t >= len(ln["terms"]):
+                    row.append(None)           # the lane has no such term: EXEC leaves it out
+                    continue
+                a1, a2, asub, b1, b2, bsub, neg, da = ln["terms"][t]
+                assert a2 == cg.ZERO and b2 == cg.ZERO and not asub and not bsub and a1 < 30 and b1 < 30
+                row.append((16 * a1, 16 * b1))
+                flags[lig] |= (int(neg) << (M1_NEG + ti)) | (int(da) << (M1_DA + ti))
+            neg_any.append(any((flags[l] >> (M1_NEG + ti)) & 1 for l in range(12)))
+            da_any.append(any((flags[l] >> (M1_DA + ti)) & 1 for l in range(12)))
+            rows.append(row)
+    # the one term that some lanes lack: the seventh of the squaring, lanes 6..11
+    assert [[r is None for r in row] for row in rows] == [[False] * 12] * 12 + [[False] * 6 + [True] * 6]
+    # finish_output(f.conj(), ..): state element j = lane j's coefficient, negated for the second Fp6 half
+    lin, gs = steps[-2], steps[-1]
+    assert lin["op"] == cg.OP_LIN and gs["op"] == cg.OP_GSTORE and gs["kind"] == cg.K_STATE and not lin["vred"]
+    for j, ((dst, terms), (src, elem)) in enumerate(zip(lin["lanes"], gs["lanes"])):
+        assert terms == [(j, 1 if j < 6 else -1)] and src == dst and elem == cg.ST_F + j
+        flags[j] |= int(j >= 6) << M1_CONJ
+    return rows, flags, neg_any, da_any
+
+
+def generate_miller1(bits=None, S=30, SC=4, vb=8):
+    """bits: add flag per iteration ([line product, (second line product), squaring]; one more line product ends the loop) - the
+    Miller loop's own unless a test shortens it"""
+    rows, flags, neg_any, da_any = miller1_tables()
+    if bits is None:
+        import coopgen as cg
+        bits = cg.miller_bits()
+    NIT = len(bits)
+    assert 0 < NIT <= 64
+    SG = S + ((4 - S % 8) + 8) % 8
+    PS = SC + 5 * SG
+    assert SG - S >= 6 and len(rows) <= 20, "a row of the operand table takes the six padding records of one group in one plane"
+    g = Asm(vb)
+    g.S, g.SC, g.SG, g.PS, g.rows, g.flags, g.bits = S, SC, SG, PS, rows, flags, list(bits)
+    g.row_off = [16 * ((r // 5) * PS + SC + (r % 5) * SG + S) for r in range(len(rows))]       # LDS byte address of row r (+ 8 x lane in group)
+    g.n_line_steps = NIT + sum(bits) + 1
+    # lane constants (inputs): table address 8 x lane in group; group base; flag word; the lane's result slot; byte offset of
+    # the lane's half record in a line step; its landing address in the line slots; byte offset of its state record
+    g.vtab, g.vgb, g.vdst = g.E + 2, g.vz, g.F + 1
+    g.L = 0
+    g.voff, g.vland, g.vst = g.vend, g.vend + 1, g.vend + 2
+    g.vtop = g.vend + 3
+    assert g.L + 8 <= vb and g.vtop <= 168
+    sLB, sIt, sAdd, sBits, sEX = g.sRT, g.sT, g.sN, g.sFR, g.sEX
+    sM6 = g.send
+    sLeft = g.send + 2
+    g.send += 4
+    out, T2 = g.A[0], g.B[0]
+    LINE0, SQ0, NT = 0, 6, (6, 7)
+
+    def st_rec(src, addr, off=0):
+        g.e("ds_write_b128 v%d, v[%d:%d] offset:%d" % (addr, src, src + 3, off))
+        g.e("ds_write_b128 v%d, v[%d:%d] offset:%d" % (addr, src + 4, src + 7, off + PS * 16))
+        g.e("ds_write_b128 v%d, v[%d:%d] offset:%d" % (addr, src + 8, src + 11, off + PS * 32))
+        g.e("ds_write_b64 v%d, v[%d:%d] offset:%d" % (addr, src + 12, src + 13, off + PS * 48))
+
+    def rd_rec(dst, addr):
+        g.e("ds_read_b128 v[%d:%d], v%d" % (dst, dst + 3, addr))
+        g.e("ds_read_b128 v[%d:%d], v%d offset:%d" % (dst + 4, dst + 7, addr, PS * 16))
+        g.e("ds_read_b128 v[%d:%d], v%d offset:%d" % (dst + 8, dst + 11, addr, PS * 32))
+        g.e("ds_read_b64 v[%d:%d], v%d offset:%d" % (dst + 12, dst + 13, addr, PS * 48))
+
+    def fetch_row(r):
+        g.e("ds_read_b64 v[%d:%d], v%d offset:%d" % (g.E, g.E + 1, g.vtab, g.row_off[r]))
+
+    def operands(p):
+        """the row in E (arrived) -> the operand records into set p"""
+        g.e("v_add_u32 v%d, v%d, v%d" % (g.E, g.E, g.vgb))
+        g.e("v_add_u32 v%d, v%d, v%d" % (g.E + 1, g.E + 1, g.vgb))
+        rd_rec(g.A[p], g.E)
+        rd_rec(g.B[p], g.E + 1)
+
+    def issue_loads():
+        g.e("s_mov_b64 exec, %[act]")
+        g.e("global_load_dwordx4 v[%d:%d], v%d, s[%d:%d]" % (g.L, g.L + 3, g.voff, sLB, sLB + 1))
+        g.e("global_load_dwordx4 v[%d:%d], v%d, s[%d:%d] offset:16" % (g.L + 4, g.L + 7, g.voff, sLB, sLB + 1))
+        g.e("s_mov_b64 exec, s[%d:%d]" % (sEX, sEX + 1))
+
+    def term1(p, ti, t, nt, after_mid, narrow):
+        """term t of nt (number ti of the iteration) on operand set p: term() with the operand forming decided here.
+        narrow: some lanes have no such term - EXEC leaves them out of the arithmetic (they add nothing)"""
+        A, B, D = g.A[p], g.B[p], g.D
+
+        def lanes(some):
+            if narrow:
+                g.e("s_mov_b64 exec, s[%d:%d]" % ((sM6, sM6 + 1) if some else (sEX, sEX + 1)))
+
+        g.e("s_waitcnt lgkmcnt(0)")
+        lanes(True)
+        if neg_any[ti]:
+            g.e("v_bfe_i32 v%d, v%d, %d, 1" % (g.vm, g.F, M1_NEG + ti))
+            g.e("v_sub_u32 v%d, 0, v%d" % (g.vc, g.vm))
+            for i in range(NL):
+                g.e("v_xad_u32 v%d, v%d, v%d, v%d" % (A + i, A + i, g.vm, g.vc))
+        if da_any[ti]:
+            g.e("v_bfe_u32 v%d, v%d, %d, 1" % (g.vm, g.F, M1_DA + ti))
+            for i in range(NL):
+                g.e("v_lshlrev_b32 v%d, v%d, v%d" % (A + i, g.vm, A + i))
+        if t + 1 < nt:
+            operands(1 - p)
+        for i in range(NH):
+            g.e("v_sub_u32 v%d, v%d, v%d" % (D + i, A + NH + i, A + i))
+        for i in range(NH):
+            g.e("v_sub_u32 v%d, v%d, v%d" % (D + NH + i, B + i, B + NH + i))
+        touched = set()
+
+        def acc(reg_key, dst, a, b):
+            add = dst
+            if t == 0 and reg_key not in touched:
+                add = None
+                touched.add(reg_key)
+            g.mad(dst, vreg(a), vreg(b), add)
+
+        for j in range(NH):
+            for i in range(NH):
+                acc(("m", i + j), g.MID[i + j], D + i, D + NH + j)
+        lanes(False)
+        after_mid()
+        lanes(True)
+        for j in range(NH):
+            for i in range(NH):
+                acc(("a", i + j), g.ACC[i + j], A + i, B + j)
+                acc(("a", NL + i + j), g.ACC[NL + i + j], A + NH + i, B + NH + j)
+        lanes(False)
+
+    def body(first_ti, nt, tag, next_row):
+        """a MULACC body whose first operands were requested by the caller: terms, tail, result and companion stores"""
+        for t in range(nt):
+            ti = first_ti + t
+            narrow = any(r is None for r in rows[ti])
+            assert not narrow or t + 1 == nt        # (such a term requests no operands)
+            term1(t & 1, ti, t, nt, (lambda r=ti + 2: fetch_row(r)) if t + 2 < nt else (next_row if t + 1 == nt else (lambda: None)), narrow)
+        tail(g, out)
+        g.e("s_and_b64 exec, %%[act], s[%d:%d]" % (sEX, sEX + 1))
+        st_rec(out, g.vdst)
+        g.e("s_mov_b64 exec, s[%d:%d]" % (sEX, sEX + 1))
+        # companion slot: generate()'s form (even lane x0 + x1, odd lane x0 - x1, the partner's value by DPP)
+        g.e("v_bfe_u32 v%d, v%d, 4, 1" % (g.vm, g.vdst))
+        g.e("v_sub_u32 v%d, 0, v%d" % (g.vc, g.vm))
+        for i in range(NL):
+            g.e("v_xad_u32 v%d, v%d, v%d, v%d" % (T2 + i, out + i, g.vc, g.vm))
+        g.e("s_nop 1")
+        for i in range(NL):
+            g.e("v_add_u32_dpp v%d, v%d, v%d quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" % (T2 + i, out + i, T2 + i))
+        g.e("s_and_b64 exec, %%[act], s[%d:%d]" % (sEX, sEX + 1))
+        st_rec(T2, g.vdst, 16 * 12)
+        g.e("s_mov_b64 exec, s[%d:%d]" % (sEX, sEX + 1))
+        g.e(".Lm1_done_%s_%%=:" % tag)       # (tools/asmemu.py watches these labels: tests compare every body with the step model)
+
+    # ---- entry: masks, counters, the first line step's records, the first row of the table
+    g.e("s_mov_b64 s[%d:%d], exec" % (sEX, sEX + 1))
+    m6 = sum(0x3f << (12 * grp) for grp in range(5))
+    g.e("s_mov_b32 s%d, 0x%x" % (sM6, m6 & 0xffffffff))
+    g.e("s_mov_b32 s%d, 0x%x" % (sM6 + 1, m6 >> 32))
+    g.e("s_and_b64 s[%d:%d], s[%d:%d], s[%d:%d]" % (sM6, sM6 + 1, sM6, sM6 + 1, sEX, sEX + 1))
+    g.e("s_mov_b64 s[%d:%d], %%[lines]" % (sLB, sLB + 1))
+    g.e("s_mov_b32 s%d, %d" % (sLeft, g.n_line_steps - 1))
+    g.e("s_mov_b32 s%d, 0" % sIt)
+    mask = sum(int(b) << i for i, b in enumerate(bits))
+    g.e("s_mov_b32 s%d, 0x%x" % (sBits, mask & 0xffffffff))
+    g.e("s_mov_b32 s%d, 0x%x" % (sBits + 1, mask >> 32))
+    issue_loads()
+    fetch_row(LINE0)
+    # ---- f = 1 and its companions: lane 0 of a group holds ONE (constant record 1), lanes 0 and 1 the companions ONE, the rest ZERO (record 0)
+    g.e("v_sub_u32 v%d, v%d, v%d" % (g.vm, g.vdst, g.vgb))
+    g.e("v_mov_b32 v%d, 16" % g.vc)
+    g.e("v_mov_b32 v%d, 0" % g.D)
+    g.e("v_cmp_ne_u32_e32 vcc, 0, v%d" % g.vm)
+    g.e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (g.D + 1, g.vc, g.D))
+    g.e("v_lshrrev_b32 v%d, 5, v%d" % (g.vm, g.vm))
+    g.e("v_cmp_ne_u32_e32 vcc, 0, v%d" % g.vm)
+    g.e("v_cndmask_b32 v%d, v%d, v%d, vcc" % (g.D + 2, g.vc, g.D))
+    rd_rec(out, g.D + 1)
+    rd_rec(T2, g.D + 2)
+    g.e("s_waitcnt lgkmcnt(0)")
+    st_rec(out, g.vdst)
+    st_rec(T2, g.vdst, 16 * 12)
+    # ---- iteration: add flag (the last pass, behind the iterations, is the closing line product)
+    g.e(".Lm1_iter_%=:")
+    g.e("s_mov_b32 s%d, 0" % sAdd)
+    g.e("s_cmp_ge_u32 s%d, %d" % (sIt, NIT))
+    g.e("s_cbranch_scc1 .Lm1_line_%=")
+    g.e("s_cmp_lt_u32 s%d, 32" % sIt)
+    g.e("s_cbranch_scc1 .Lm1_lo_%=")
+    g.e("s_bitcmp1_b32 s%d, s%d" % (sBits + 1, sIt))
+    g.e("s_branch .Lm1_bit_%=")
+    g.e(".Lm1_lo_%=:")
+    g.e("s_bitcmp1_b32 s%d, s%d" % (sBits, sIt))
+    g.e(".Lm1_bit_%=:")
+    g.e("s_cbranch_scc0 .Lm1_line_%=")
+    g.e("s_mov_b32 s%d, 1" % sAdd)
+    # ---- line product: the records of this step leave the landing registers, the next step's are requested
+    g.e(".Lm1_line_%=:")
+    g.e("s_waitcnt vmcnt(0) lgkmcnt(0)")        # the line records; the first row of the table, the stores of the body before
+    g.e("ds_write_b128 v%d, v[%d:%d]" % (g.vland, g.L, g.L + 3))
+    g.e("ds_write_b128 v%d, v[%d:%d] offset:%d" % (g.vland, g.L + 4, g.L + 7, PS * 16))
+    operands(0)
+    fetch_row(LINE0 + 1)
+    g.e("s_cmp_eq_u32 s%d, 0" % sLeft)
+    g.e("s_cbranch_scc1 .Lm1_noload_%=")
+    g.e("s_add_u32 s%d, s%d, -1" % (sLeft, sLeft))
+    g.e("s_add_u32 s%d, s%d, %%[stride]" % (sLB, sLB))
+    g.e("s_addc_u32 s%d, s%d, 0" % (sLB + 1, sLB + 1))
+    g.e("s_waitcnt lgkmcnt(9)")                 # the two landing writes are through: their registers are free
+    g.e("s_nop 4")                              # (a scalar write, then a vector memory access that reads the register)
+    issue_loads()
+    g.e(".Lm1_noload_%=:")
+
+    def next_of_line():
+        # a second line product follows (addition iteration), or the squaring, or (behind the closing product) nothing
+        g.e("s_cmp_eq_u32 s%d, 1" % sAdd)
+        g.e("s_cbranch_scc1 .Lm1_nl_%=")
+        fetch_row(SQ0)
+        g.e("s_branch .Lm1_nd_%=")
+        g.e(".Lm1_nl_%=:")
+        fetch_row(LINE0)
+        g.e(".Lm1_nd_%=:")
+
+    body(LINE0, NT[0], "l", next_of_line)
+    g.e("s_cmp_eq_u32 s%d, 1" % sAdd)
+    g.e("s_cbranch_scc0 .Lm1_single_%=")
+    g.e("s_mov_b32 s%d, 0" % sAdd)
+    g.e("s_branch .Lm1_line_%=")
+    g.e(".Lm1_single_%=:")
+    g.e("s_cmp_ge_u32 s%d, %d" % (sIt, NIT))
+    g.e("s_cbranch_scc1 .Lm1_finish_%=")
+    # ---- accumulator squaring
+    g.e("s_waitcnt lgkmcnt(0)")
+    operands(0)
+    fetch_row(SQ0 + 1)
+    body(SQ0, NT[1], "s", lambda: fetch_row(LINE0))
+    g.e("s_add_u32 s%d, s%d, 1" % (sIt, sIt))
+    g.e("s_branch .Lm1_iter_%=")
+    # ---- finish_output(f.conj(), to_wire=False, ST_F): conjugate, weak normalisation, the lane's state record
+    g.e(".Lm1_finish_%=:")
+    D = g.D
+    g.e("v_bfe_i32 v%d, v%d, %d, 1" % (g.vm, g.F, M1_CONJ))
+    g.e("v_sub_u32 v%d, 0, v%d" % (g.vc, g.vm))
+    for i in range(NL):
+        g.e("v_xad_u32 v%d, v%d, v%d, v%d" % (out + i, out + i, g.vm, g.vc))
+    for i in range(NL - 1):
+        g.e("v_add_u32 v%d, 0x8000000, v%d" % (D + i, out + i))
+        g.e("v_ashrrev_i32 v%d, 28, v%d" % (D + i, D + i))
+        g.e("v_bfe_i32 v%d, v%d, 0, 28" % (out + i, out + i))
+    for i in range(1, NL):
+        g.e("v_add_u32 v%d, v%d, v%d" % (out + i, out + i, D + i - 1))
+    assert T2 == out + NL
+    g.e("v_mov_b32 v%d, 0" % T2)
+    g.e("v_mov_b32 v%d, 0" % (T2 + 1))
+    g.e("s_mov_b64 exec, %[act]")
+    for q in range(4):
+        g.e("global_store_dwordx4 v%d, v[%d:%d], %%[state] offset:%d" % (g.vst, out + 4 * q, out + 4 * q + 3, 16 * q))
+    g.e("s_mov_b64 exec, s[%d:%d]" % (sEX, sEX + 1))
+    g.e("s_waitcnt vmcnt(0) lgkmcnt(0)")
+    return g
+
+
+def write_miller1_inc(path, vb=8):
+    g = generate_miller1(vb=vb)
+    ins = {"vtab": g.vtab, "vgb": g.vgb, "flags": g.F, "vdst": g.vdst, "voff": g.voff, "vland": g.vland, "vst": g.vst}
+    vclob = [v for v in range(0, g.vtop) if v not in ins.values()]
+    with open(path, "w") as f:
+        f.write("// GENERATED by tools/coopasm.py - do not edit.  The Miller loop of one-pair checks (k_miller1) as one hand-scheduled inline-asm block.\n")
+        f.write("// %d instructions; VGPRs v0..v%d, SGPRs s%d..s%d.\n" % (sum(1 for l in g.lines if not l.endswith(":")), g.vtop - 1, g.sb, g.send - 1))
+        f.write("#pragma once\n")
+        f.write("#define ZKP_MILLER1_S %d\n#define ZKP_MILLER1_SC %d\n#define ZKP_MILLER1_PS %d\n" % (g.S, g.SC, g.PS))
+        f.write("#define ZKP_MILLER1_LINE_SLOT 24\n#define ZKP_MILLER1_ROWS %d\n#define ZKP_MILLER1_LINE_STEPS %d\n" % (len(g.rows), g.n_line_steps))
+        # the operand table: row r = 12 lanes x (A1, B1) byte offsets inside the group; it lives in the padding records of plane r / 5, group r % 5
+        f.write("#define ZKP_MILLER1_TABLE " + ", ".join("%d, %d" % (e if e else (0, 0)) for row in g.rows for e in row) + "\n")
+        f.write("#define ZKP_MILLER1_FLAGS " + ", ".join("0x%xu" % x for x in g.flags) + "\n")
+        f.write("#define ZKP_MILLER1_ASM \\\n")
+        for l in g.lines:
+            f.write('    "%s\\n\\t" \\\n' % l)
+        f.write('    ""\n')
+        f.write("// lane constants: table address, group base, flag word, result slot, line offset, landing address, state offset\n")
+        f.write("#define ZKP_MILLER1_INS(vtab, vgb, flags, vdst, voff, vland, vst) " + ", ".join('"{v%d}"(%s)' % (r, nm) for nm, r in ins.items()) + "\n")
+        f.write("#define ZKP_MILLER1_CLOBBERS " + ", ".join('"v%d"' % v for v in vclob) + ", " + ", ".join('"s%d"' % s for s in range(g.sb, g.send)) + ', "vcc", "scc", "memory"\n')
+    return g
+
+
 def write_inc(path, vb=8):
     g, out = generate(vb)
     outs = list(range(out, out + NL))
@@ -626,3 +948,6 @@ if __name__ == "__main__":
     g = write_inc(path)
     n = sum(1 for l in g.lines if not l.endswith(":"))
     print("wrote %s: %d instructions, v%d..v%d" % (path, n, g.vb, g.vend - 1))
+    path1 = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(path), "zkp_miller1.inc")
+    g1 = write_miller1_inc(path1)
+    print("wrote %s: %d instructions, v0..v%d" % (path1, sum(1 for l in g1.lines if not l.endswith(":")), g1.vtop - 1))

@@ -13,6 +13,8 @@
 //                  the optional epilogue (alpha r + beta E, renormalised) and the companion store
 //                  (x0 + x1 / x0 - x1 of the lane pair's Fp2 coefficient, so that later steps fetch their
 //                  operand forms ready-made) ride on the MULACC step.
+//   k_miller1      the Miller loop of one-pair checks (program miller1_state) as ONE asm block on k_coop's lanes and LDS image: no
+//                  interpreter, operand addresses from a table in the image's padding, line records requested one line step ahead.
 //   k_batch_inv    batched Fp inversions (Montgomery's trick, up to 32 values per lane, division steps): the single inversion
 //                  of the final exponentiation and the six per x-power chain of the decompression.
 //   k_ksq          the 63 cyclotomic squarings of an x-power chain in Karabina's compressed form: four lanes per check (one Fp2
@@ -39,6 +41,7 @@
 #include "zkp_coop_prog.inc"
 #include "zkp_fp28.hpp"
 #include "zkp_coop_mulacc.inc"   // the MULACC step of k_coop and the squaring of k_ksq as hand-scheduled asm blocks (tools/coopasm.py)
+#include "zkp_miller1.inc"       // the Miller loop of one-pair checks (k_miller1) as one asm block (tools/coopasm.py generate_miller1)
 #include "zkp_prep_dbl.inc"      // the doubling / addition steps of k_prep_lines as hand-allocated asm blocks (tools/prepasm.py)
 #include "zkp_valid_steps.inc"   // the Jacobian doubling / mixed addition of the subgroup checks as asm blocks (tools/validasm.py)
 
@@ -369,6 +372,55 @@ __global__ void __launch_bounds__(64, COOP_WAVES) k_coop(CoopArgs A) {
         }
         pc++;
     }
+}
+
+// =============================================================================== the Miller loop of one-pair checks, uninterpreted
+// k_miller1 computes what k_coop<30,4> computes on the program miller1_state (tools/coopgen.py prog_miller(1, False)): same lanes, same
+// LDS image, same limbs in every slot and state record.  The whole loop is ONE asm block (tools/coopasm.py generate_miller1): an iteration
+// is straight-line code (line product, squaring), its operand addresses come from a table that sits in the padding of the LDS image, and
+// the six line records of a step are requested one line step ahead - half a record per lane, into eight landing registers - so that the
+// line product and the squaring in between hide their latency; the interpreter's GLOAD step (two dependent memory waits in the
+// wavefront's only instruction stream, then a staging copy through fourteen registers) is gone.  ZKP_COOP_MILLER1=0 selects the
+// interpreter again (cross-check, A/B).
+__device__ __constant__ const uint32_t K_M1_TABLE[ZKP_MILLER1_ROWS * LIG * 2] = {ZKP_MILLER1_TABLE};
+__device__ __constant__ const uint32_t K_M1_FLAGS[LIG] = {ZKP_MILLER1_FLAGS};
+
+__global__ void __launch_bounds__(64, COOP_WAVES) k_miller1(CoopArgs A) {
+    extern __shared__ int4 lds[];
+    constexpr int S = ZKP_COOP_WIDE_NSLOT, SC = ZKP_COOP_WIDE_NCONST, SG = coop_group_stride(S), PS = SC + GROUPS * SG;
+    static_assert(S == ZKP_MILLER1_S && SC == ZKP_MILLER1_SC && PS == ZKP_MILLER1_PS && NLINES == ZKP_MILLER1_LINE_STEPS && NL == 14 && LIG == 12,
+                  "the generated block is for the <30, 4> image of the Miller programs");
+    static_assert(SG - S >= 6 && ZKP_MILLER1_ROWS <= 4 * GROUPS, "a table row takes the six padding records of one group in one plane");
+    const uint32_t n_checks = eff_n(A.n_checks, A.nd);     // also the stride of the line buffer (k_prep_lines takes the same)
+    if (blockIdx.x * GROUPS >= n_checks) return;
+    const int lane = threadIdx.x;
+    for (int i = lane; i < (int)A.nconst * 4; i += 64) lds[(i & 3) * PS + (i >> 2)] = A.consts[i];
+    // operand table: row r = twelve lanes x (A1, B1) in the padding records of plane r / 5, group r % 5
+    uint32_t* const lds32 = (uint32_t*)lds;
+    for (int i = lane; i < ZKP_MILLER1_ROWS * LIG * 2; i += 64) {
+        const int r = i / (LIG * 2), w = i - r * (LIG * 2);
+        lds32[4 * ((r / GROUPS) * PS + SC + (r % GROUPS) * SG + S) + w] = K_M1_TABLE[i];
+    }
+    __syncthreads();
+    if (lane >= GROUPS * LIG) return;      // as in k_coop: lanes 60..63 own nothing
+    const int grp = (lane * 43) >> 9, lig = lane - grp * LIG;
+    const uint32_t check = blockIdx.x * GROUPS + grp;
+    const unsigned long long act_lanes = __ballot(check < n_checks);
+    const uint32_t half = lig & 1, coef = lig >> 1;        // the lane fetches half a record of line coefficient `coef`
+    const uint32_t vgb = 16u * (SC + grp * SG), vdst = vgb + 16u * lig, vtab = 8u * lig, flags = K_M1_FLAGS[lig];
+    const uint32_t voff = (coef * n_checks + check) * 64u + half * 32u;
+    const uint32_t vland = vgb + 16u * (ZKP_MILLER1_LINE_SLOT + coef) + half * (2u * PS * 16u);
+    const uint32_t vst = ((lig + A.st_off) * A.nc + check) * 64u;
+    const uint32_t stride = 6u * 64u * n_checks;           // bytes per line step (k = 1)
+    constexpr uint32_t PL[NL] = {ZKP28_P_LIMBS};
+    asm volatile(ZKP_MILLER1_ASM
+                 :
+                 : ZKP_MILLER1_INS(vtab, vgb, flags, vdst, voff, vland, vst),
+                   [lines] "s"(A.lines), [state] "s"(A.state), [stride] "s"(stride), [act] "s"(act_lanes),
+                   [p0] "s"(PL[0]), [p1] "s"(PL[1]), [p2] "s"(PL[2]), [p3] "s"(PL[3]), [p4] "s"(PL[4]), [p5] "s"(PL[5]), [p6] "s"(PL[6]),
+                   [p7] "s"(PL[7]), [p8] "s"(PL[8]), [p9] "s"(PL[9]), [p10] "s"(PL[10]), [p11] "s"(PL[11]), [p12] "s"(PL[12]),
+                   [p13] "s"(PL[13]), [pinv] "s"(ZKP28_PINV)
+                 : ZKP_MILLER1_CLOBBERS);
 }
 
 // =============================================================================== thread-level Fp28 helpers
@@ -2335,6 +2387,7 @@ struct CoopDev {
     struct ProfEv { int cls; hipEvent_t a, b; };
     std::vector<ProfEv>* prof;     // null: not profiling
     bool prof_phase_c;
+    bool miller1;                  // ZKP_COOP_MILLER1 (default 1): one-pair Miller loops that end in the state record run on k_miller1
     const uint32_t* n_dev;         // for the duration of one coop_pairing call: the device-resident check count (or null)
 };
 
@@ -2442,6 +2495,7 @@ hipError_t coop_init(CoopState* st, const hipDeviceProp_t& prop) {
     d->inv_fermat = env_l("ZKP_COOP_INV_FERMAT", 0) != 0;
     d->cus = prop.multiProcessorCount;
     d->prime = (int)env_l("ZKP_COOP_PRIME", 1);
+    d->miller1 = env_l("ZKP_COOP_MILLER1", 1) != 0;
     for (int i = 0; i < MAX_PIPES; i++) d->pipe[i].owner = d;
     for (int i = 0; i < d->kn.n_pipes; i++) {
         if ((e = hipStreamCreateWithFlags(&d->pipe[i].stream, hipStreamNonBlocking)) != hipSuccess) return e;
@@ -2508,7 +2562,7 @@ static hipError_t prime(const CoopDev* d, hipStream_t s, size_t blocks, int cls)
 }
 
 static hipError_t run_prog(CoopDev* d, CoopPipe* pp, int prog, uint32_t n_checks, uint32_t nc, uint32_t k, const uint64_t* wire_in,
-                           uint64_t* wire_out, uint8_t* ok, int* all_ok, uint32_t st_off = 0, uint32_t chk_off = 0) {
+                           uint64_t* wire_out, uint8_t* ok, int* all_ok, uint32_t st_off = 0, uint32_t chk_off = 0, bool miller1 = false) {
     hipStream_t s = pp->stream;
     CoopArgs a;
     a.hdr = d->progs[prog].hdr;
@@ -2540,7 +2594,11 @@ static hipError_t run_prog(CoopDev* d, CoopPipe* pp, int prog, uint32_t n_checks
     const size_t lds_bytes = coop_lds_bytes(coop_cfg_slots(cfg), coop_cfg_consts(cfg));
     unsigned blocks = (n_checks + GROUPS - 1) / GROUPS;
     ProfScope prof(d, s, cfg == 1 ? PROF_MILLER : cfg == 2 ? PROF_C_DEEP : d->prof_phase_c ? PROF_C_PLAIN : PROF_FEXP_A);
-    if (cfg == 2)
+    if (miller1) {   // the program's own kernel: same image, same arguments (k_miller1 addresses lines and state with 32-bit byte offsets)
+        if (prog != ZKP_PROG_MILLER1_STATE || cfg != 1 || (uint64_t)n_checks * 6 * 64 * NLINES >> 32 || (uint64_t)(LIG + st_off) * nc * 64 >> 32)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_miller1, dim3(blocks), dim3(64), lds_bytes, s, a);
+    } else if (cfg == 2)
         hipLaunchKernelGGL((k_coop<ZKP_COOP_DEEP_NSLOT, ZKP_COOP_DEEP_NCONST>), dim3(blocks), dim3(64), lds_bytes, s, a);
     else if (cfg == 1)
         hipLaunchKernelGGL((k_coop<ZKP_COOP_WIDE_NSLOT, ZKP_COOP_WIDE_NCONST>), dim3(blocks), dim3(64), lds_bytes, s, a);
@@ -2602,7 +2660,10 @@ static hipError_t miller_on_pipe(CoopDev* d, CoopPipe* pp, const uint64_t* g1, c
     hipError_t e;
     if (k <= MAX_GROUP) {
         if ((e = prep(pp, g1, g2, i1, i2, base, n, (uint32_t)k, 0, (uint32_t)k, fused)) != hipSuccess) return e;
-        return run_prog(d, pp, miller_prog(k, wire_out != nullptr), n, nc, (uint32_t)k, nullptr, wire_out, nullptr, nullptr);
+        // one pair per check, result in the state record (the fused pairing path): k_miller1, unless the knob or the 32-bit byte
+        // offsets of that kernel (a line buffer, or the twelve Miller elements of a state buffer, beyond 4 GB) say the interpreter
+        const bool m1 = d->miller1 && k == 1 && !wire_out && !((uint64_t)n * 6 * 64 * NLINES >> 32) && !((uint64_t)LIG * nc * 64 >> 32);
+        return run_prog(d, pp, miller_prog(k, wire_out != nullptr), n, nc, (uint32_t)k, nullptr, wire_out, nullptr, nullptr, 0, 0, m1);
     }
     const size_t MS = d->kn.max_stream;
     if (k <= MS) {               // one accumulator for all k pairs
