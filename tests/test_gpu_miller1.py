@@ -74,9 +74,10 @@ def _both(monkeypatch, fn, chunk=None):
     return res
 
 
-@pytest.mark.parametrize("n", (1, 5, 6, 64, 321))
+@pytest.mark.parametrize("n", (1, 4, 5, 6, 59, 60, 61, 64, 321))
 def test_fused_pass_equals_the_interpreter_and_the_oracle(monkeypatch, pairs, n):
-    """one check; one full wavefront; one wavefront and one lane group; 64; 321 in chunks of 320 (two pipelines, the second chunk of one check)"""
+    """one check; four (a lane group without a check in the only wavefront); one full wavefront; one wavefront and one lane group; 59
+    (the last wavefront one check short), 60 (full), 61 (one over); 64; 321 in chunks of 320 (two pipelines, the second chunk of one check)"""
     g1, g2, want = pairs
     new, old = _both(monkeypatch, lambda e: _gt_check(e, g1[:n], g2[:n]), chunk=320 if n == 321 else None)
     assert np.array_equal(new[0], old[0]) and np.array_equal(new[1], old[1]) and new[2] == old[2]
@@ -99,6 +100,51 @@ def test_infinities_inside_a_wavefront(monkeypatch, pairs):
             assert np.array_equal(new[0][c], one) and new[1][c] == 1
         else:
             assert np.array_equal(new[0][c], want[c]) and new[1][c] == 0
+
+
+def test_infinities_at_the_ends_of_a_launch_and_in_a_whole_wavefront(monkeypatch, pairs):
+    """64 checks, thirteen wavefronts, the last with four checks: an infinity flag on check 0, on check 63 (the last check of the partial
+    wavefront) and on all five checks of the third wavefront (10..14, G1 and G2 flags mixed, one check with both): identity and ok byte 1
+    there, every other check untouched"""
+    g1, g2, want = pairs
+    i1, i2 = np.zeros(64, dtype=np.uint8), np.zeros(64, dtype=np.uint8)
+    i1[0], i2[63] = 1, 1
+    i1[[10, 12, 14]] = 1
+    i2[[11, 13, 14]] = 1
+    flagged = (0, 10, 11, 12, 13, 14, 63)
+    new, old = _both(monkeypatch, lambda e: _gt_check(e, g1[:64], g2[:64], i1, i2))
+    assert np.array_equal(new[0], old[0]) and np.array_equal(new[1], old[1]) and new[2] == old[2] == 0
+    one = o.fp12_one()
+    for c in range(64):
+        if c in flagged:
+            assert np.array_equal(new[0][c], one) and new[1][c] == 1, c
+        else:
+            assert np.array_equal(new[0][c], want[c]) and new[1][c] == 0, c
+
+
+def test_one_engine_on_a_large_a_small_and_the_large_batch_again(monkeypatch, pairs):
+    """64 checks, then 6, then the 64 again on ONE engine: during the second call the line buffer and the state buffer still hold the
+    records of the first beyond check 5 (and the stride of the line buffer differs).  The third result is the first, the second is a
+    fresh engine's, both are the oracle's - on the new kernel and on the interpreter"""
+    g1, g2, want = pairs
+    got = []
+    for knob in ("1", "0"):
+        e = _engine(monkeypatch, knob)
+        try:
+            runs = [_gt_check(e, g1[:n], g2[:n]) for n in (64, 6, 64)]
+        finally:
+            e.close()
+        e = _engine(monkeypatch, knob)
+        try:
+            fresh = _gt_check(e, g1[:6], g2[:6])
+        finally:
+            e.close()
+        for a, b in ((runs[2], runs[0]), (runs[1], fresh)):
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2] == 0, knob
+        assert np.array_equal(runs[0][0], want[:64]) and np.array_equal(runs[1][0], want[:6]) and not runs[0][1].any() and not runs[1][1].any(), knob
+        got.append(runs)
+    for a, b in zip(*got):
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 def test_g2_point_off_the_twist(monkeypatch, pairs):

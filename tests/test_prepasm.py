@@ -355,8 +355,8 @@ def test_no_generated_block_loads_exec_with_an_absolute_mask():
     """the lane-role masks of every asm block stay INSIDE the EXEC the block was entered with - checked on the checked-in includes,
     i.e. on the text the compiler sees (the callers keep all 64 lanes alive today; nothing may depend on that)"""
     csrc = os.path.join(ROOT, "zkvm_pairings_amd", "csrc")
-    n = sum(_exec_discipline(os.path.join(csrc, f)) for f in ("zkp_prep_dbl.inc", "zkp_valid_steps.inc", "zkp_coop_mulacc.inc"))
-    assert n > 200
+    n = sum(_exec_discipline(os.path.join(csrc, f)) for f in ("zkp_prep_dbl.inc", "zkp_valid_steps.inc", "zkp_coop_mulacc.inc", "zkp_miller1.inc"))
+    assert n > 218          # (the eighteen EXEC writes of k_miller1's block among them)
 
 
 def test_doubling_step_on_half_a_wavefront_leaves_the_other_half_alone():

@@ -846,7 +846,8 @@ def generate_miller1(bits=None, S=30, SC=4, vb=8):
     g.e("s_add_u32 s%d, s%d, %%[stride]" % (sLB, sLB))
     g.e("s_addc_u32 s%d, s%d, 0" % (sLB + 1, sLB + 1))
     g.e("s_waitcnt lgkmcnt(9)")                 # the two landing writes are through: their registers are free
-    g.e("s_nop 4")                              # (a scalar write, then a vector memory access that reads the register)
+    g.e("s_nop 4")                              # (a scalar write, then a vector memory access that reads the register: a courtesy -
+    #                                             the manual asks for the five states behind a VALU write only)
     issue_loads()
     g.e(".Lm1_noload_%=:")
 

@@ -42,6 +42,7 @@
 #include "zkp_fp28.hpp"
 #include "zkp_coop_mulacc.inc"   // the MULACC step of k_coop and the squaring of k_ksq as hand-scheduled asm blocks (tools/coopasm.py)
 #include "zkp_miller1.inc"       // the Miller loop of one-pair checks (k_miller1) as one asm block (tools/coopasm.py generate_miller1)
+#include "zkp_miller1_lanes.hpp" // its lane constants and the 4 GB test of its 32-bit offsets (tests/miller1_plan_check.cpp walks them)
 #include "zkp_prep_dbl.inc"      // the doubling / addition steps of k_prep_lines as hand-allocated asm blocks (tools/prepasm.py)
 #include "zkp_valid_steps.inc"   // the Jacobian doubling / mixed addition of the subgroup checks as asm blocks (tools/validasm.py)
 
@@ -391,6 +392,8 @@ __global__ void __launch_bounds__(64, COOP_WAVES) k_miller1(CoopArgs A) {
     static_assert(S == ZKP_MILLER1_S && SC == ZKP_MILLER1_SC && PS == ZKP_MILLER1_PS && NLINES == ZKP_MILLER1_LINE_STEPS && NL == 14 && LIG == 12,
                   "the generated block is for the <30, 4> image of the Miller programs");
     static_assert(SG - S >= 6 && ZKP_MILLER1_ROWS <= 4 * GROUPS, "a table row takes the six padding records of one group in one plane");
+    static_assert(zkp::m1::SG == SG && zkp::m1::GROUPS == GROUPS && zkp::m1::LIG == LIG && zkp::m1::LINE_STEPS == NLINES,
+                  "zkp_miller1_lanes.hpp describes this kernel's lanes");
     const uint32_t n_checks = eff_n(A.n_checks, A.nd);     // also the stride of the line buffer (k_prep_lines takes the same)
     if (blockIdx.x * GROUPS >= n_checks) return;
     const int lane = threadIdx.x;
@@ -403,19 +406,15 @@ __global__ void __launch_bounds__(64, COOP_WAVES) k_miller1(CoopArgs A) {
     }
     __syncthreads();
     if (lane >= GROUPS * LIG) return;      // as in k_coop: lanes 60..63 own nothing
-    const int grp = (lane * 43) >> 9, lig = lane - grp * LIG;
-    const uint32_t check = blockIdx.x * GROUPS + grp;
-    const unsigned long long act_lanes = __ballot(check < n_checks);
-    const uint32_t half = lig & 1, coef = lig >> 1;        // the lane fetches half a record of line coefficient `coef`
-    const uint32_t vgb = 16u * (SC + grp * SG), vdst = vgb + 16u * lig, vtab = 8u * lig, flags = K_M1_FLAGS[lig];
-    const uint32_t voff = (coef * n_checks + check) * 64u + half * 32u;
-    const uint32_t vland = vgb + 16u * (ZKP_MILLER1_LINE_SLOT + coef) + half * (2u * PS * 16u);
-    const uint32_t vst = ((lig + A.st_off) * A.nc + check) * 64u;
-    const uint32_t stride = 6u * 64u * n_checks;           // bytes per line step (k = 1)
+    // the lane constants (zkp_miller1_lanes.hpp: the same text runs on the host, under sanitizers, and feeds the emulated wavefront)
+    const zkp::m1::Lanes c = zkp::m1::lanes(lane, blockIdx.x, n_checks, A.nc, A.st_off);
+    const unsigned long long act_lanes = __ballot(c.check < n_checks);
+    const uint32_t flags = K_M1_FLAGS[c.lig];
+    const uint32_t stride = zkp::m1::stride(n_checks);     // bytes per line step (k = 1)
     constexpr uint32_t PL[NL] = {ZKP28_P_LIMBS};
     asm volatile(ZKP_MILLER1_ASM
                  :
-                 : ZKP_MILLER1_INS(vtab, vgb, flags, vdst, voff, vland, vst),
+                 : ZKP_MILLER1_INS(c.vtab, c.vgb, flags, c.vdst, c.voff, c.vland, c.vst),
                    [lines] "s"(A.lines), [state] "s"(A.state), [stride] "s"(stride), [act] "s"(act_lanes),
                    [p0] "s"(PL[0]), [p1] "s"(PL[1]), [p2] "s"(PL[2]), [p3] "s"(PL[3]), [p4] "s"(PL[4]), [p5] "s"(PL[5]), [p6] "s"(PL[6]),
                    [p7] "s"(PL[7]), [p8] "s"(PL[8]), [p9] "s"(PL[9]), [p10] "s"(PL[10]), [p11] "s"(PL[11]), [p12] "s"(PL[12]),
@@ -2595,7 +2594,7 @@ static hipError_t run_prog(CoopDev* d, CoopPipe* pp, int prog, uint32_t n_checks
     unsigned blocks = (n_checks + GROUPS - 1) / GROUPS;
     ProfScope prof(d, s, cfg == 1 ? PROF_MILLER : cfg == 2 ? PROF_C_DEEP : d->prof_phase_c ? PROF_C_PLAIN : PROF_FEXP_A);
     if (miller1) {   // the program's own kernel: same image, same arguments (k_miller1 addresses lines and state with 32-bit byte offsets)
-        if (prog != ZKP_PROG_MILLER1_STATE || cfg != 1 || (uint64_t)n_checks * 6 * 64 * NLINES >> 32 || (uint64_t)(LIG + st_off) * nc * 64 >> 32)
+        if (prog != ZKP_PROG_MILLER1_STATE || cfg != 1 || !zkp::m1::eligible(n_checks, nc, st_off))
             return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_miller1, dim3(blocks), dim3(64), lds_bytes, s, a);
     } else if (cfg == 2)
@@ -2662,7 +2661,7 @@ static hipError_t miller_on_pipe(CoopDev* d, CoopPipe* pp, const uint64_t* g1, c
         if ((e = prep(pp, g1, g2, i1, i2, base, n, (uint32_t)k, 0, (uint32_t)k, fused)) != hipSuccess) return e;
         // one pair per check, result in the state record (the fused pairing path): k_miller1, unless the knob or the 32-bit byte
         // offsets of that kernel (a line buffer, or the twelve Miller elements of a state buffer, beyond 4 GB) say the interpreter
-        const bool m1 = d->miller1 && k == 1 && !wire_out && !((uint64_t)n * 6 * 64 * NLINES >> 32) && !((uint64_t)LIG * nc * 64 >> 32);
+        const bool m1 = d->miller1 && k == 1 && !wire_out && zkp::m1::eligible(n, nc, 0);
         return run_prog(d, pp, miller_prog(k, wire_out != nullptr), n, nc, (uint32_t)k, nullptr, wire_out, nullptr, nullptr, 0, 0, m1);
     }
     const size_t MS = d->kn.max_stream;
