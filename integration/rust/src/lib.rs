@@ -13,6 +13,7 @@ pub mod prove;
 pub mod fk20;
 pub mod cells;
 pub mod recover;
+pub mod bls;
 
 #[repr(C)]
 pub struct ZkpCtx {

@@ -59,6 +59,146 @@ def consts():
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- hash-to-G2 (RFC 9380, zkp_bls.hip)
+H2C_A = (0, 240)                  # E': y^2 = x^3 + 240 i x + 1012 (1 + i)
+H2C_B = (1012, 1012)
+H2C_Z = (P - 2, P - 1)            # -(2 + i)
+H2C_KERNEL_X = (P - 6, 6)         # -6 + 6 i: the abscissa of the 3-isogeny's kernel
+
+
+def f2_sqrt(a):
+    """a square root in Fp2 (p = 3 mod 4), or None"""
+    if a == (0, 0):
+        return a
+    a0, a1 = a
+    if a1 == 0:
+        s = m.fp_sqrt(a0)
+        if s is not None:
+            return (s, 0)
+        s = m.fp_sqrt(-a0 % P)
+        return None if s is None else (0, s)
+    n = m.fp_sqrt((a0 * a0 + a1 * a1) % P)
+    if n is None:
+        return None
+    for t in ((a0 + n) * (P + 1) // 2 % P, (a0 - n) * (P + 1) // 2 % P):
+        c = m.fp_sqrt(t)
+        if c is not None:
+            r = (c, a1 * m.fp_inv(2 * c % P) % P)
+            return r if m.f2_sqr(r) == a else None
+    return None
+
+
+def f2_cbrt(t):
+    """a cube root in Fp2, or None: t^alpha with 3 alpha = 1 mod the 3-free part of p^2 - 1, corrected inside the 3-Sylow subgroup"""
+    q1, k = P * P - 1, 0
+    while q1 % 3 == 0:
+        q1, k = q1 // 3, k + 1
+    assert k <= 6
+    g, nr = (1, 0), (1, 1)
+    while m.f2_pow(g, 3 ** (k - 1)) == (1, 0):          # a generator of the 3-Sylow subgroup
+        nr = m.f2_add(nr, (1, 0))
+        g = m.f2_pow(nr, q1)
+    c = m.f2_pow(t, pow(3, -1, q1))
+    h = (1, 0)
+    for _ in range(3 ** k):
+        r = m.f2_mul(c, h)
+        if m.f2_mul(m.f2_sqr(r), r) == t:
+            return r
+        h = m.f2_mul(h, g)
+    return None
+
+
+def _pmul(a, b):
+    out = [(0, 0)] * (len(a) + len(b) - 1)
+    for i, x in enumerate(a):
+        for j, y in enumerate(b):
+            out[i + j] = m.f2_add(out[i + j], m.f2_mul(x, y))
+    return out
+
+
+def _padd(a, b):
+    n = max(len(a), len(b))
+    a, b = a + [(0, 0)] * (n - len(a)), b + [(0, 0)] * (n - len(b))
+    return [m.f2_add(x, y) for x, y in zip(a, b)]
+
+
+def h2c_isogeny_candidates():
+    """Velu's formulas for the kernel {O, (x0, +-y0)} of E', then the six scalings (x, y) -> (x / s^2, y / s^3) that land on
+    y^2 = x^3 + 4 (1 + i).  Each candidate is (x_num, x_den, y_num, y_den), coefficients of x'^0, x'^1, ..."""
+    x0, a, b = H2C_KERNEL_X, H2C_A, H2C_B
+    x0sq = m.f2_sqr(x0)
+    # x0 is a root of the 3-division polynomial 3 x^4 + 6 a x^2 + 12 b x - a^2
+    psi3 = m.f2_sub(m.f2_add(m.f2_add(m.f2_muls(m.f2_sqr(x0sq), 3), m.f2_muls(m.f2_mul(a, x0sq), 6)), m.f2_muls(m.f2_mul(b, x0), 12)), m.f2_sqr(a))
+    assert psi3 == (0, 0)
+    gx = m.f2_add(m.f2_muls(x0sq, 3), a)
+    v = m.f2_muls(gx, 2)
+    u = m.f2_muls(m.f2_add(m.f2_add(m.f2_mul(x0sq, x0), m.f2_mul(a, x0)), b), 4)          # (2 y0)^2
+    w = m.f2_add(u, m.f2_mul(x0, v))
+    assert m.f2_sub(a, m.f2_muls(v, 5)) == (0, 0)                                       # the image curve has a = 0
+    b_img = m.f2_sub(b, m.f2_muls(w, 7))
+    d = [m.f2_neg(x0), (1, 0)]                                                          # x - x0
+    d2, d3 = _pmul(d, d), _pmul(_pmul(d, d), d)
+    xn = _padd(_padd(_pmul([(0, 0), (1, 0)], d2), [m.f2_mul(v, c) for c in d]), [u])   # X = x + v / (x - x0) + u / (x - x0)^2
+    yn = _padd(_padd(d3, [m.f2_neg(m.f2_mul(v, c)) for c in d]), [m.f2_neg(m.f2_muls(u, 2))])   # Y = y (1 - v / (x - x0)^2 - 2 u / (x - x0)^3)
+    t = m.f2_mul(b_img, m.f2_inv((4, 4)))                                               # s^6
+    c = f2_cbrt(t)
+    s0 = f2_sqrt(c)
+    assert s0 is not None and m.f2_pow(s0, 6) == t
+    zeta = m.f2_neg(m.f2_pow((1, 1), (P * P - 1) // 3))                                 # a primitive sixth root of unity
+    assert m.f2_pow(zeta, 6) == (1, 0) and m.f2_pow(zeta, 3) != (1, 0) and m.f2_pow(zeta, 2) != (1, 0)
+    out, s = [], s0
+    for _ in range(6):
+        i2 = m.f2_inv(m.f2_sqr(s))
+        i3 = m.f2_mul(i2, m.f2_inv(s))
+        out.append(([m.f2_mul(c, i2) for c in xn], d2, [m.f2_mul(c, i3) for c in yn], d3))
+        s = m.f2_mul(s, zeta)
+    return out
+
+
+# RFC 9380 appendix E.3, coefficients of x'^0, x'^1, ...: what the derivation below must arrive at
+_K = 0x5c759507e8e333ebb5b7a9a47d7ed8532c52d39fd3a042a88b58423c50ae15d5c2638e343d9c71c6238aaaaaaaa97d6
+_L = 0x1530477c7ab4113b59a4c18b076d11930f7da5d4a07f649bf54439d87d27e500fc8c25ebf8c92f6812cfc71c71c6d706
+H2C_TABLE = (
+    [(_K, _K),
+     (0, 0x11560bf17baa99bc32126fced787c88f984f87adf7ae0c7f9a208c6b4f20a4181472aaa9cb8d555526a9ffffffffc71a),
+     (0x11560bf17baa99bc32126fced787c88f984f87adf7ae0c7f9a208c6b4f20a4181472aaa9cb8d555526a9ffffffffc71e,
+      0x8ab05f8bdd54cde190937e76bc3e447cc27c3d6fbd7063fcd104635a790520c0a395554e5c6aaaa9354ffffffffe38d),
+     (0x171d6541fa38ccfaed6dea691f5fb614cb14b4e7f4e810aa22d6108f142b85757098e38d0f671c7188e2aaaaaaaa5ed1, 0)],
+    [(0, P - 72), (12, P - 12), (1, 0)],
+    [(_L, _L),
+     (0, 0x5c759507e8e333ebb5b7a9a47d7ed8532c52d39fd3a042a88b58423c50ae15d5c2638e343d9c71c6238aaaaaaaa97be),
+     (0x11560bf17baa99bc32126fced787c88f984f87adf7ae0c7f9a208c6b4f20a4181472aaa9cb8d555526a9ffffffffc71c,
+      0x8ab05f8bdd54cde190937e76bc3e447cc27c3d6fbd7063fcd104635a790520c0a395554e5c6aaaa9354ffffffffe38f),
+     (0x124c9ad43b6cf79bfbf7043de3811ad0761b0f37a1e26286b0e977c69aa274524e79097a56dc4bd9e1b371c71c718b10, 0)],
+    [(P - 432, P - 432), (0, P - 216), (18, P - 18), (1, 0)],
+)
+
+
+def h2c_consts():
+    """(name -> Fp2 constant of the hash-to-G2 kernels, the isogeny): of the six scalings exactly one is the suite's table"""
+    cands = h2c_isogeny_candidates()
+    assert len({tuple(c[0]) for c in cands}) == 3 and len({(tuple(c[0]), tuple(c[2])) for c in cands}) == 6
+    hit = [c for c in cands if c == H2C_TABLE]
+    assert len(hit) == 1, "exactly one scaling is the suite's table"
+    iso = hit[0]
+    xn, xd, yn, yd = iso
+    assert m.f2_mul(m.f2_sqr(xn[3]), xn[3]) == m.f2_sqr(yn[3])
+    out = {}
+    for nm, coeffs in (("XNUM", xn), ("YNUM", yn)):
+        for i, cf in enumerate(coeffs):
+            out["ISO_%s%d" % (nm, i)] = cf
+    out["ISO_DEN"] = m.f2_neg(H2C_KERNEL_X)                                             # x_den = (x + DEN)^2, y_den = (x + DEN)^3
+    out["SSWU_A"], out["SSWU_B"], out["SSWU_Z"] = H2C_A, H2C_B, H2C_Z
+    out["SSWU_NBA"] = m.f2_mul(m.f2_neg(H2C_B), m.f2_inv(H2C_A))                        # -B / A
+    out["SSWU_X1E"] = m.f2_mul(H2C_B, m.f2_inv(m.f2_mul(H2C_Z, H2C_A)))                 # B / (Z A): x1 of the exceptional case
+    z3 = m.f2_mul(m.f2_sqr(H2C_Z), H2C_Z)
+    out["SSWU_Z3"] = z3
+    nz3 = (z3[0] * z3[0] + z3[1] * z3[1]) % P
+    assert pow(nz3, (P - 1) // 2, P) == P - 1                                           # Z is no square: neither is the norm of Z^3
+    out["SSWU_C"] = (pow(nz3, (P + 1) // 4, P), 0)                                      # c^2 = -norm(Z^3)
+    return out, iso
+
+
 def balanced28(v):
     """14 signed limbs in [-2^27, 2^27) with sum l_i 2^(28 i) == v (v >= 0, v < 2^391)."""
     out = []
@@ -88,6 +228,12 @@ def emit28(c):
     for i in range(1, 6):
         names.append(("GAMMA%d_0" % i, m28(c["GAMMA%d_0" % i])))
         names.append(("GAMMA%d_1" % i, m28(c["GAMMA%d_1" % i])))
+    # hash-to-G2: 1 / 2, 2^256 R (the high half of a 512-bit value), p in balanced limbs, then the Fp2 constants
+    names += [("INV2", m28((P + 1) // 2)), ("W256R", m28(m28(1 << 256)))]
+    names.append(("PBAL", P))                                  # p itself (no Montgomery form) in balanced limbs: k_h2c_clear's renormalisation
+    for k, v in h2c_consts()[0].items():
+        names.append((k + "_0", m28(v[0])))
+        names.append((k + "_1", m28(v[1])))
     pinv = (-pow(P, -1, 1 << 28)) % (1 << 28)
     lines = ["/* GENERATED by tools/gen_constants.py - do not edit.",
              " * 14 x 28-bit limbs.  ZKP28_P: unsigned limbs of p.  Everything in ZKP28_CONST_LIST is in Montgomery form",
@@ -151,6 +297,9 @@ def main():
         if k in ("P", "R", "R2"):
             continue
         names.append(("M_" + k, mont(v)))
+    for k, v in h2c_consts()[0].items():                      # hash-to-G2 (only these two headers: the oracle has no such map)
+        names.append(("M_" + k + "_0", mont(v[0])))
+        names.append(("M_" + k + "_1", mont(v[1])))
     for i, (k, v) in enumerate(names):
         lines.append("  X(%s, %s)%s" % (k, ", ".join("0x%08xu" % x for x in limbs(v, 32, 12)), " \\" if i + 1 < len(names) else ""))
     with open(os.path.join(ROOT, "zkvm_pairings_amd", "csrc", "zkp_constants.h"), "w") as f:

@@ -231,6 +231,24 @@ RECOVER_SIGNATURES = {
     "zkp_das_recover_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_u, c_u, c_int, c_vp, c_vp, c_vp]),
 }
 
+BLS_POINTS_CHECKED = 1       # ZKP_BLS_POINTS_CHECKED
+
+# name -> (restype, argtypes); MUST list every symbol include/zkp_bls.h declares (hash-to-G2 and the BLS batch verifier)
+BLS_SIGNATURES = {
+    "zkp_fp_from_wide_be_batch": (c_int, [c_vp, c_vp, c_sz, c_vp]),
+    "zkp_fp_from_wide_be_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_hash_to_field_g2_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    "zkp_hash_to_field_g2_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g2_map_from_fields_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g2_map_from_fields_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g2_clear_cofactor_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g2_clear_cofactor_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_hash_to_g2_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_hash_to_g2_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_bls_verify_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_verify_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -258,7 +276,7 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
-                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items())):
+                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -35,6 +35,9 @@ hipError_t coop_g2_mul(const uint64_t* base, size_t stride, const uint64_t* sc, 
 // out[i] = a[i] + b[i] on the 28-bit core, which = 1 (G1) or 2 (G2); ia / ib / out_inf may be null
 hipError_t coop_add(int which, const uint64_t* a, const uint8_t* ia, const uint64_t* b, const uint8_t* ib, size_t n, uint64_t* out, uint8_t* out_inf,
                     hipStream_t s);
+// hash-to-G2: out[i] = [h_eff] P_i with P_i the wire point i (pts non-null; inf may be null) or the sum of the homogeneous projective points in
+// slots 2 i and 2 i + 1 of ws (pts null; layout at k_h2c_clear, zkp_bls_clear.hip)
+hipError_t coop_h2c_clear(const uint64_t* pts, const uint8_t* inf, const int32_t* ws, size_t stride, size_t n, uint64_t* out, uint8_t* out_inf, hipStream_t s);
 // out[i] = [a] P_i + [b] (beta x_i, -y_i) with (a, b) = ab[2 (i / per)], ab[2 (i / per) + 1] (= [a + b z^2] P_i in G1); inf / out_inf may be null
 hipError_t coop_g1_mul_endo(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint32_t per, uint64_t* out, uint8_t* out_inf,
                             hipStream_t s);

@@ -13,7 +13,9 @@
 //     inputs |a|,|b| < 8p is back in (-0.04p, 1.04p): no conditional subtraction anywhere.
 // Canonical limbs are produced only at the wire (fp28_to_wire).
 #pragma once
+#ifndef ZKP_FP28_HOST   // tests/bls_kernel_host.cpp: the host build supplies its own stand-ins for the HIP keywords
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "zkp_constants28.h"

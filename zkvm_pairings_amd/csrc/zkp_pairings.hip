@@ -20,6 +20,7 @@
 #include "../../include/zkp_fk20.h"
 #include "../../include/zkp_cells.h"
 #include "../../include/zkp_recover.h"
+#include "../../include/zkp_bls.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -38,6 +39,7 @@
 #include "zkp_fk20.hpp"
 #include "zkp_cells.hpp"
 #include "zkp_recover.hpp"
+#include "zkp_bls.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -484,6 +486,8 @@ struct zkp_ctx {
     size_t fk20_cap = 0;
     uint64_t* g1ntt_split = nullptr;   // the split twiddles of kzg_dom, entry for entry (-1: none yet): rebuilt when that table grows
     int g1ntt_split_log2 = -1;
+    void* bls_ws = nullptr;     // grow-only workspace of hash-to-G2 and the BLS verifier (zkp_bls_plan.hpp layout)
+    size_t bls_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -911,6 +915,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->kzg_dom) (void)hipFree(c->kzg_dom);
     if (c->poly_coset) (void)hipFree(c->poly_coset);
     if (c->fk20_ws) (void)hipFree(c->fk20_ws);
+    if (c->bls_ws) (void)hipFree(c->bls_ws);
     if (c->g1ntt_split) (void)hipFree(c->g1ntt_split);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
@@ -1649,6 +1654,17 @@ int g1ntt_tables(zkp_ctx* c, unsigned log2_n, const uint32_t** domain, const uin
     *split = c->g1ntt_split;
     return ZKP_OK;
 }
+int grow_bls(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->bls_cap) {
+        if (c->bls_ws) { HIPCHK(c, hipFree(c->bls_ws)); c->bls_ws = nullptr; c->bls_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->bls_ws, bytes));
+        zkp_dbg_alloc("ctx.bls", c->bls_ws, bytes);
+        c->bls_cap = bytes;
+    }
+    *ws = c->bls_ws;
+    return ZKP_OK;
+}
+int* bls_bad_word(zkp_ctx* c) { return c->validate ? c->d_flag + 2 : nullptr; }
 int* validation_word(zkp_ctx* c) { return c->d_flag + 2; }
 int mul(zkp_ctx* c, int which, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, hipStream_t s) {
     return mul_dev(c, which, base, stride, sc, n, out, out_inf, s);
@@ -3026,6 +3042,166 @@ int zkp_das_recover_batch(zkp_ctx* c, const uint64_t* values, const uint8_t* pre
         if (bad) { c->err = "input limbs >= r"; return ZKP_ERR_NONCANONICAL; }
     }
     if ((rc = zkp::recover_dev(c, (const uint64_t*)dv, (const uint8_t*)dp, n, log2_n, log2_l, flags, (uint64_t*)dout, (int32_t*)(dout + off_ok), c->stream))) return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- hash-to-G2 and the BLS batch verifier (zkp_bls.hip, include/zkp_bls.h)
+namespace {
+bool h2c_msgs_bad(const zkp_ctx* c, const void* msgs, const void* offsets, size_t n, const void* dst, size_t dst_len) {
+    (void)msgs;   // may be null: every message may be empty
+    return !c || n > zkp::bls::MAX_N || zkp::bls::dst_bad(dst_len) || !dst || (n && !offsets);
+}
+// host offsets: non-decreasing, and a buffer behind them when any message has a byte
+bool offsets_malformed(const uint8_t* msgs, const uint64_t* offsets, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return true;
+    return n && offsets[n] > offsets[0] && !msgs;
+}
+// the messages of a host call in workspace slots: the bytes [offsets[0], offsets[n]) in slot `sb`, the offsets in slot `so`, the DST in `sd`;
+// *dmsgs is biased so that the caller's offsets index it
+void stage_msgs(Staging& io, int sb, int so, int sd, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len,
+                const uint8_t** dmsgs, const void** doff, const void** ddst) {
+    const uint64_t lo = n ? offsets[0] : 0, bytes = n ? offsets[n] - offsets[0] : 0;
+    const uint8_t* db = bytes ? (const uint8_t*)io.in(sb, msgs + lo, bytes) : nullptr;
+    *dmsgs = db ? db - lo : nullptr;
+    *doff = io.in(so, offsets, (n + 1) * 8);
+    *ddst = io.in(sd, dst, dst_len);
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_fp_from_wide_be_batch_dev(zkp_ctx* c, const void* bytes, size_t n, void* out, void* stream) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!bytes || !out))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return zkp::h2c_wide_dev(c, bytes, n, out, S(stream));
+}
+int zkp_fp_from_wide_be_batch(zkp_ctx* c, const uint8_t* bytes, size_t n, uint64_t* out) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!bytes || !out))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* din = io.in(0, bytes, n * 64);
+    void* dout = io.out(4, out, n * 48);
+    int rc;
+    if ((rc = io.status()) || (rc = zkp::h2c_wide_dev(c, din, n, dout, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_hash_to_field_g2_batch_dev(zkp_ctx* c, const void* msgs, const void* offsets, size_t n, const void* dst, size_t dst_len, void* out_u, void* stream) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && !out_u)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return zkp::h2c_field_dev(c, msgs, offsets, n, dst, dst_len, out_u, S(stream));
+}
+int zkp_hash_to_field_g2_batch(zkp_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, uint64_t* out_u) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && !out_u) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    void* dout = io.out(4, out_u, n * 192);
+    int rc;
+    if ((rc = io.status()) || (rc = zkp::h2c_field_dev(c, dm, dof, n, dd, dst_len, dout, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_g2_map_from_fields_batch_dev(zkp_ctx* c, const void* u, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!u || !out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, u, n * 4, S(stream))) return rc;
+    return zkp::h2c_map_dev(c, u, n, out, out_inf, S(stream));
+}
+int zkp_g2_map_from_fields_batch(zkp_ctx* c, const uint64_t* u, size_t n, uint64_t* out, uint8_t* out_inf) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!u || !out || !out_inf))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* du = io.in(0, u, n * 192);
+    void* dout = io.out(4, out, n * 192);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)du, n * 4)) || (rc = zkp::h2c_map_dev(c, du, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_g2_clear_cofactor_batch_dev(zkp_ctx* c, const void* pts, const void* inf, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!pts || !out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, pts, n * 4, S(stream))) return rc;
+    return zkp::h2c_clear_dev(c, pts, inf, n, out, out_inf, S(stream));
+}
+int zkp_g2_clear_cofactor_batch(zkp_ctx* c, const uint64_t* pts, const uint8_t* inf, size_t n, uint64_t* out, uint8_t* out_inf) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!pts || !out || !out_inf))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* dp = io.in(0, pts, n * 192);
+    const void* di = io.in(2, inf, n);
+    void* dout = io.out(4, out, n * 192);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dp, n * 4)) || (rc = zkp::h2c_clear_dev(c, dp, di, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_hash_to_g2_batch_dev(zkp_ctx* c, const void* msgs, const void* offsets, size_t n, const void* dst, size_t dst_len, void* out, void* out_inf,
+                             void* stream) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && (!out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return zkp::h2c_hash_dev(c, msgs, offsets, n, dst, dst_len, out, out_inf, S(stream));
+}
+int zkp_hash_to_g2_batch(zkp_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, uint64_t* out,
+                         uint8_t* out_inf) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && (!out || !out_inf)) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    void* dout = io.out(4, out, n * 192);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = zkp::h2c_hash_dev(c, dm, dof, n, dd, dst_len, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+static bool bls_args_bad(const zkp_ctx* c, const void* pk, const void* msgs, const void* offsets, const void* dst, size_t dst_len, const void* sig, size_t n,
+                         const void* rand, int flags, const void* all_ok) {
+    return h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || n > zkp::bls::MAX_VERIFY_N ||
+           zkp::rlc::args_bad(n, 1, 1, 0) || (n && (!pk || !sig || !rand));
+}
+int zkp_bls_verify_batch_dev(zkp_ctx* c, const void* pk, const void* inf_pk, const void* msgs, const void* offsets, const void* dst, size_t dst_len,
+                             const void* sig, const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok, void* stream) {
+    if (bls_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, pk, n * 2, S(stream))) || (rc = validate_on_stream(c, sig, n * 4, S(stream)))) return rc;
+    return zkp::bls_verify_dev(c, pk, inf_pk, msgs, offsets, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+// the seven arrays of points one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_verify_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* inf_pk, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                         size_t dst_len, const uint64_t* sig, const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags, int* all_ok) {
+    if (bls_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[5] = {pk, inf_pk, sig, inf_sig, rand};
+    const size_t bytes[5] = {n * 96, n, n * 192, n, n * 16};
+    size_t off[5], total = 0;
+    for (int i = 0; i < 5; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[5];
+    for (int i = 0; i < 5; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n * 2)) || (rc = validate_dev(c, (const uint64_t*)d[2], n * 4)) ||
+        (rc = zkp::bls_verify_dev(c, d[0], d[1], dm, dof, dd, dst_len, d[2], d[3], n, d[4], flags, c->d_flag + 1, c->stream)))
+        return rc;
     return io.finish();
 }
 

@@ -954,6 +954,148 @@ class PairingEngine:
         self._chk(self._lib.zkp_das_recover_batch(self._h, _ptr(v), _ptr(pr), n, log2_n, log2_l, flags, _ptr(coeffs), _ptr(ok)))
         return coeffs, ok
 
+    # ------------------------------------------------------------------ hash-to-G2 and BLS signatures (include/zkp_bls.h)
+    @staticmethod
+    def pack_messages(msgs):
+        """a list of bytes objects -> (buffer uint8, offsets uint64 (n + 1,)): the message layout of the hash and verify calls"""
+        offsets = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        if len(msgs):
+            offsets[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        return np.frombuffer(b"".join(bytes(x) for x in msgs), dtype=np.uint8), offsets
+
+    def _msgs_np(self, msgs, offsets, dst):
+        if offsets is None:
+            msgs, offsets = self.pack_messages(msgs)
+        buf = np.ascontiguousarray(msgs, dtype=np.uint8).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("offsets: n + 1 values, at least one")
+        if off.size > 1 and int(off.max()) > buf.size:
+            raise ValueError("offsets reach byte %d of a buffer of %d" % (int(off.max()), buf.size))
+        d = np.frombuffer(bytes(dst), dtype=np.uint8)
+        return buf, off, off.size - 1, d
+
+    def _msgs_t(self, msgs, offsets, dst):
+        import torch
+        u8 = (torch.uint8,)
+        self._t_check(offsets, None, "offsets", rows=1)
+        if msgs is not None:
+            self._t_check(msgs, None, "msgs", dtypes=u8)
+        if not _is_torch(dst):
+            dst = torch.frombuffer(bytearray(bytes(dst)), dtype=torch.uint8).to(offsets.device)
+        self._t_check(dst, None, "dst", dtypes=u8)
+        return msgs, offsets, offsets.numel() - 1, dst
+
+    def fp_from_wide_be(self, data):
+        """64 big-endian bytes per element -> canonical Fp (n, 6): OS2IP mod p (zkp_fp_from_wide_be_batch)"""
+        if _is_torch(data):
+            import torch
+            self._t_check(data, 64, "data", dtypes=(torch.uint8,))
+            n = data.numel() // 64
+            out = torch.empty((n, 6), dtype=torch.int64, device=data.device)
+            self._chk(self._lib.zkp_fp_from_wide_be_batch_dev(self._h, self._tp(data), n, self._tp(out), self._stream()))
+            return out
+        b = _np(data, 64, np.uint8)
+        out = np.empty((b.shape[0], 6), dtype=np.uint64)
+        self._chk(self._lib.zkp_fp_from_wide_be_batch(self._h, _ptr(b), b.shape[0], _ptr(out)))
+        return out
+
+    def hash_to_field_g2(self, msgs, dst, offsets=None):
+        """messages -> (u0, u1) of RFC 9380 hash_to_field for G2, (n, 24) words (zkp_hash_to_field_g2_batch).  msgs: a list of bytes, or
+        a byte buffer with offsets (n + 1,); torch tensors (buffer uint8, offsets int64, dst bytes or a uint8 tensor) stay on the GPU."""
+        if _is_torch(offsets):
+            import torch
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            out = torch.empty((n, 24), dtype=torch.int64, device=offsets.device)
+            self._chk(self._lib.zkp_hash_to_field_g2_batch_dev(self._h, self._tp(msgs), self._tp(offsets), n, self._tp(dst), dst.numel(), self._tp(out),
+                                                               self._stream()))
+            return out
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        out = np.empty((n, 24), dtype=np.uint64)
+        self._chk(self._lib.zkp_hash_to_field_g2_batch(self._h, _ptr(buf), _ptr(off), n, _ptr(d), d.size, _ptr(out)))
+        return out
+
+    def g2_map_from_fields(self, u):
+        """u (n, 24): two Fp2 elements per point -> clear_cofactor(iso(sswu(u0)) + iso(sswu(u1))): (points (n, 24), inf (n,))"""
+        if _is_torch(u):
+            import torch
+            self._t_check(u, 24, "u")
+            n = u.numel() // 24
+            out, oi = torch.empty((n, 24), dtype=u.dtype, device=u.device), torch.empty(n, dtype=torch.uint8, device=u.device)
+            self._chk(self._lib.zkp_g2_map_from_fields_batch_dev(self._h, self._tp(u), n, self._tp(out), self._tp(oi), self._stream()))
+            return out, oi
+        u = _np(u, 24)
+        out, oi = np.empty((u.shape[0], 24), dtype=np.uint64), np.empty(u.shape[0], dtype=np.uint8)
+        self._chk(self._lib.zkp_g2_map_from_fields_batch(self._h, _ptr(u), u.shape[0], _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def g2_clear_cofactor(self, pts, inf=None):
+        """[h_eff] P for any points of E2 (zkp_g2_clear_cofactor_batch): (points (n, 24), inf (n,))"""
+        if _is_torch(pts):
+            import torch
+            self._t_check(pts, 24, "pts")
+            n = pts.numel() // 24
+            self._t_bytes(inf, n, "inf")
+            out, oi = torch.empty((n, 24), dtype=pts.dtype, device=pts.device), torch.empty(n, dtype=torch.uint8, device=pts.device)
+            self._chk(self._lib.zkp_g2_clear_cofactor_batch_dev(self._h, self._tp(pts), self._tp(inf), n, self._tp(out), self._tp(oi), self._stream()))
+            return out, oi
+        pts = _np(pts, 24)
+        n = pts.shape[0]
+        i = _flags(inf, n, "inf")
+        out, oi = np.empty((n, 24), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_g2_clear_cofactor_batch(self._h, _ptr(pts), _ptr(i), n, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def hash_to_g2(self, msgs, dst, offsets=None):
+        """messages -> points of G2 (RFC 9380 BLS12381G2_XMD:SHA-256_SSWU_RO_; zkp_hash_to_g2_batch): (points (n, 24), inf (n,));
+        the arguments of hash_to_field_g2"""
+        if _is_torch(offsets):
+            import torch
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            out, oi = torch.empty((n, 24), dtype=torch.int64, device=offsets.device), torch.empty(n, dtype=torch.uint8, device=offsets.device)
+            self._chk(self._lib.zkp_hash_to_g2_batch_dev(self._h, self._tp(msgs), self._tp(offsets), n, self._tp(dst), dst.numel(), self._tp(out), self._tp(oi),
+                                                         self._stream()))
+            return out, oi
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        out, oi = np.empty((n, 24), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_hash_to_g2_batch(self._h, _ptr(buf), _ptr(off), n, _ptr(d), d.size, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def bls_verify(self, pk, msgs, sig, dst, offsets=None, inf_pk=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """n BLS signatures (public keys in G1, signatures in G2) verified as ONE pairing product (zkp_bls_verify_batch): True iff
+        prod_i e([r_i] pk_i, H(m_i)) e(-g1, sum_i [r_i] sig_i) == 1, every pk and sig is valid (unless points_checked), no pk is the
+        identity and no (a_i, b_i) of rand is zero.  rand (n, 2) uint64, by default fresh from os.urandom (rlc_random).  Host arrays
+        return a bool; resident torch tensors fill and return all_ok (int32 (1,)) without synchronising."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(pk):
+            import torch
+            self._t_check(pk, 12, "pk"), self._t_check(sig, 24, "sig")
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            if pk.numel() // 12 != n or sig.numel() // 24 != n:
+                raise ValueError("%d messages, %d public keys, %d signatures" % (n, pk.numel() // 12, sig.numel() // 24))
+            self._t_bytes(inf_pk, n, "inf_pk"), self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(pk.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=pk.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_verify_batch_dev(self._h, self._tp(pk), self._tp(inf_pk), self._tp(msgs), self._tp(offsets), self._tp(dst), dst.numel(),
+                                                         self._tp(sig), self._tp(inf_sig), n, self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            return all_ok
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        pk, sig = _np(pk, 12), _np(sig, 24)
+        if pk.shape[0] != n or sig.shape[0] != n:
+            raise ValueError("%d messages, %d public keys, %d signatures" % (n, pk.shape[0], sig.shape[0]))
+        ip, isg = _flags(inf_pk, n, "inf_pk"), _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_verify_batch(self._h, _ptr(pk), _ptr(ip), _ptr(buf), _ptr(off), _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags,
+                                                 ctypes.byref(ok)))
+        return bool(ok.value)
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

@@ -376,3 +376,20 @@ def das_recover_instance(seed, n, log2_n, log2_l, bitrev=True, keep=None, engine
         present[j, rng.permutation(big_m)[:keep]] = 1
     values[present == 0] = np.uint64(0xFFFFFFFFFFFFFFFF)
     return values, present, cw
+
+
+def bls_instance(n, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
+    """n valid BLS signatures from the seed: secret keys, messages of 0 .. 63 bytes, public keys [sk] g1 and signatures [sk] H(m), the
+    hash and both multiplications on the engine.  -> (sks (n, 4), pks (n, 12), msgs (list of bytes), sigs (n, 24))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    sks = scalars(seed ^ 0xB15, n)
+    raw = splitmix64(seed ^ 0x5E5, 9 * n).reshape(n, 9) if n else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [raw[i, 1:].tobytes()[:int(raw[i, 0]) % 64] for i in range(n)]
+    if n == 0:
+        return sks, np.zeros((0, 12), dtype=np.uint64), msgs, np.zeros((0, 24), dtype=np.uint64)
+    pks, _ = engine.g1_mul(G1_GENERATOR, sks)
+    h, _ = engine.hash_to_g2(msgs, dst)
+    sigs, _ = engine.g2_mul(h, sks)
+    return sks, pks, msgs, sigs
