@@ -187,6 +187,52 @@ def clear_cofactor_psi(pt):
     return m.g2_add(out, psi2)
 
 
+LADDER_ADDS = (2, 12, 104, 53760, 53761 << 32)         # the multiple of the base the MSB-first ladder on X_ABS holds at its additions after the first
+
+
+def _traced_add(p1, p2, site, seen):
+    """p1 + p2 with the case csrc/zkp_bls_clear.hip's jac_add takes, tested in its order: the accumulator p1 at infinity, the operand p2 at
+    infinity, equal points (doubled), opposite points, the generic formula"""
+    if p1 is None:
+        branch = "p_inf"
+    elif p2 is None:
+        branch = "q_inf"
+    elif p1 == p2:
+        branch = "dbl"
+    elif p1 == m.g2_neg(p2):
+        branch = "cancel"
+    else:
+        branch = "generic"
+    seen.add((site, branch))
+    return m.g2_add(p1, p2)
+
+
+def _traced_ladder(base, site, seen):
+    """[X_ABS] base as k_h2c_clear walks it: from the identity, MSB first, a doubling per bit and an addition per set bit"""
+    r = None
+    for b in range(63, -1, -1):
+        r = m.g2_add(r, r)
+        if (X_ABS >> b) & 1:
+            r = _traced_add(r, base, site, seen)
+    return r
+
+
+def clear_cofactor_trace(pt):
+    """clear_cofactor_psi in k_h2c_clear's order of operations: A = [|x|] P (site "A"), B = psi(P) + (-A) ("B"), C = [|x|] B ("C"),
+    -C + A - P - psi(P) + psi^2(2 P) ("F0" .. "F3").  Returns (result, the set of (site, branch) its additions took)"""
+    seen = set()
+    a = _traced_ladder(pt, "A", seen)
+    psi_p = m.g2_psi(pt) if pt is not None else None
+    b = _traced_add(psi_p, m.g2_neg(a), "B", seen)
+    c = _traced_ladder(b, "C", seen)
+    dbl = m.g2_add(pt, pt)
+    psi2 = m.g2_psi(m.g2_psi(dbl)) if dbl is not None else None
+    r = m.g2_neg(c)
+    for step, q in enumerate((a, m.g2_neg(pt), m.g2_neg(psi_p), psi2)):
+        r = _traced_add(r, q, "F%d" % step, seen)
+    return r, seen
+
+
 def map_from_fields(u0, u1):
     q0, q1 = iso3(sswu(u0)[0]), iso3(sswu(u1)[0])
     return clear_cofactor_psi(m.g2_add(q0, q1))

@@ -20,7 +20,13 @@ without a GPU for every Call made here; the next sliced entry point gets a pool 
 Condition 3 on the opening's flags needs identity proofs, which dense random polynomials never give: its pool holds two constant
 polynomials and the zero polynomial next to the dense ones, one of the constants in the tail.  The seeds below are ones for which the
 conditions hold (three flag bytes of a tail can equal the first three of a call by chance): they are properties of the inputs alone, and
-test_slices_cpu.py is their judge - change a seed or a shape, run it."""
+test_slices_cpu.py is their judge - change a seed or a shape, run it.
+
+Hash-to-G2 and the BLS verifier (csrc/zkp_bls.hip; the last section) follow the same pattern on messages, pairs of field elements and
+signatures, with the model of tests/h2c_model.py behind the expected bytes.  Two departures, both stated where they occur: the flags of
+hash_to_g2 are zero everywhere (no message hashes to the identity), so condition 3 holds for its points only; and the verifier returns
+one verdict, so conditions 2 and 3 are checked on the array its slices write, the hashed points, and the GPU test moves a forgery across
+the boundary instead."""
 import random
 
 import numpy as np
@@ -241,3 +247,142 @@ def open_call(bitrev):
     call = Call(OPEN_N, OPEN_SLICE, idx, inputs, outputs, p)
     call.iz = iz
     return call
+
+
+# ------------------------------------------------------------------------------------------------------------------- hash-to-G2 and the BLS verifier
+# csrc/zkp_bls.hip walks the messages (or the pairs of field elements) in slices of bls::SLICE; the u values and the projective points of a
+# slice overwrite those of the slice before it, and the stride of the point workspace is twice the slice length of the CALL.  The last slice
+# of a hash call is longer than any pool (61 items, a partial wavefront of k_h2c_clear), so it is drawn from four pool items that occur
+# nowhere before it; the tails of the map and of the verifier are distinct items like the ones above.
+BLS_SLICE = 1 << 17
+BLS_B = 13
+HASH_N = BLS_SLICE + 61
+HASH_LENGTHS = (0, 1, 55, 56, 64, 119, 120, 8, 9, 72, 73, 17, 37)   # the empty message; 8 | 9 and 72 | 73 are where b_0 (43-byte tag) gains a block
+HASH_TAIL = (3, 8, 10, 12)                                           # 56, 9, 73 and 37 bytes
+HASH_BASE = 5                                                        # offsets[0]: the messages do not start at the buffer's first byte
+MAP_N = 2 * BLS_SLICE + 5
+MAP_TAIL = (8, 9, 10, 11, 12)
+MAP_INF = 10                                                         # the pair (a, -a): the identity, in the tail
+MAP_INF_BODY = 3                                                     # another such pair, so that the flags of the full slices differ as well
+VERIFY_N = BLS_SLICE + 6
+VERIFY_TAIL = (7, 8, 9, 10, 11, 12)
+VERIFY_BASE = 3
+
+
+def draw_spread(seed, n, tail, tail_ids, n_pool):
+    """idx: the last `tail` items drawn from tail_ids (each at least once), everything before them from the other pool items"""
+    body = np.array([j for j in range(n_pool) if j not in tail_ids], dtype=np.int64)
+    idx = body[np.random.RandomState(seed).randint(0, len(body), size=n)]
+    ids = np.array(tail_ids, dtype=np.int64)
+    last = ids[np.random.RandomState(seed + 1).randint(0, len(ids), size=tail)]
+    last[:len(ids)] = ids
+    idx[n - tail:] = last
+    return idx
+
+
+def pack_from_pool(msgs, idx, base):
+    """the messages idx of the pool as one buffer behind `base` filler bytes -> (buffer, offsets (n + 1,), rows): rows (n, width + 1) are
+    the messages zero-padded to one width with the length in the last column, the fixed-width form the slice conditions are checked on"""
+    width = max(len(x) for x in msgs)
+    assert width < 256
+    mat = np.zeros((len(msgs), width + 1), dtype=np.uint8)
+    for j, x in enumerate(msgs):
+        mat[j, :len(x)] = np.frombuffer(x, dtype=np.uint8)
+        mat[j, width] = len(x)
+    rows = mat[idx]
+    lens = rows[:, width].astype(np.uint64)
+    off = np.full(len(idx) + 1, base, dtype=np.uint64)
+    off[1:] += np.cumsum(lens, dtype=np.uint64)
+    keep = np.arange(width, dtype=np.uint64)[None, :] < lens[:, None]
+    buf = np.concatenate([np.full(base, 0xA5, dtype=np.uint8), rows[:, :width][keep]])
+    return buf, off, rows
+
+
+def hash_pool():
+    def build():
+        import bls_replay_cases as brc
+        rng = random.Random(SEED * 11)
+        msgs = [bytes(rng.randrange(256) for _ in range(k)) for k in HASH_LENGTHS]
+        _distinct(msgs)
+        pts = [brc.hashed(x, brc.DST) for x in msgs]
+        points, inf = brc.point_rows(pts)
+        return dict(msgs=msgs, pts=pts, u=brc.field_rows(msgs, brc.DST), points=points, inf=inf)
+    return rc._cached(("slice-hash-pool",), build)
+
+
+def hash_call(points):
+    """hash_to_g2 (points and flags) or hash_to_field_g2 (u) on SLICE + 61 messages; Call.msgs / Call.offsets are the arguments"""
+    p = hash_pool()
+    idx = draw_spread(SEED + 401 + points, HASH_N, HASH_N - BLS_SLICE, HASH_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, HASH_BASE)
+    outputs = dict(points=(p["points"][idx], 1), inf=(p["inf"][idx], 1)) if points else dict(u=(p["u"][idx], 1))
+    call = Call(HASH_N, BLS_SLICE, idx, dict(msg=(rows, 1)), outputs, p)
+    call.msgs, call.offsets = buf, off
+    call.constant = {"inf"} if points else set()     # no message hashes to the identity: the flags are zero in every slice
+    return call
+
+
+def map_pool():
+    def build():
+        import bls12_381_model as m
+        import bls_replay_cases as brc
+        import h2c_model as h
+        g = m.SplitMix64(SEED * 13)
+        us = [((g.below(h.P), g.below(h.P)), (g.below(h.P), g.below(h.P))) for _ in range(BLS_B)]
+        for j in (MAP_INF, MAP_INF_BODY):
+            us[j] = (us[j][0], m.f2_neg(us[j][0]))
+        _distinct(us)
+        pts = [h.map_from_fields(a, b) for a, b in us]
+        points, inf = brc.point_rows(pts)
+        return dict(us=us, pts=pts, u=brc.u64([h.f2_words(a) + h.f2_words(b) for a, b in us]).reshape(-1, 24), points=points, inf=inf)
+    return rc._cached(("slice-map-pool",), build)
+
+
+def map_call():
+    p = map_pool()
+    idx = draw(SEED + 501, MAP_N, MAP_TAIL, BLS_B)
+    call = Call(MAP_N, BLS_SLICE, idx, dict(u=(p["u"][idx], 1)), dict(points=(p["points"][idx], 1), inf=(p["inf"][idx], 1)), p)
+    call.constant = set()
+    return call
+
+
+def verify_pool():
+    def build():
+        import bls_replay_cases as brc
+        import h2c_model as h
+        pool = brc.signed_pool()[:BLS_B]         # all 16 would make the slice a multiple of the pool size
+        msgs = [x[2] for x in pool]
+        _distinct(msgs)
+        hq, hinf = brc.point_rows([brc.hashed(x, brc.DST) for x in msgs])
+        assert not hinf.any()
+        return dict(pool=pool, msgs=msgs, pk=brc.u64([h.g1_words(x[1])[0] for x in pool]).reshape(-1, 12),
+                    sig=brc.u64([h.g2_words(x[3])[0] for x in pool]).reshape(-1, 24), hq=hq)
+    return rc._cached(("slice-verify-pool",), build)
+
+
+def verify_call():
+    """bls_verify on SLICE + 6 valid signatures.  The call's one output is a verdict; what the slices write is the workspace array of hashed
+    points, so that is the array the conditions are checked on.  Call.forged: the items whose message a test changes, one at a time"""
+    p = verify_pool()
+    idx = draw(SEED + 601, VERIFY_N, VERIFY_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, VERIFY_BASE)
+    rand = np.random.RandomState(SEED + 602).randint(1, 1 << 62, size=(VERIFY_N, 2)).astype(np.uint64)
+    inputs = dict(pk=(p["pk"][idx], 1), sig=(p["sig"][idx], 1), msg=(rows, 1), rand=(rand, 1))
+    call = Call(VERIFY_N, BLS_SLICE, idx, inputs, dict(hq=(p["hq"][idx], 1)), p)
+    call.msgs, call.offsets, call.constant = buf, off, set()
+    call.forged = (BLS_SLICE - 1, BLS_SLICE, VERIFY_N - 1)
+    return call
+
+
+def forged_messages(call, j):
+    """the message buffer with the first byte of message j changed (message j is not empty: test_slices_cpu.py)"""
+    buf = call.msgs.copy()
+    buf[int(call.offsets[j])] ^= 1
+    return buf
+
+
+def message_list(call, msgs=None):
+    """the call's messages as a list of bytes, for the entry points that take one"""
+    buf = (call.msgs if msgs is None else msgs).tobytes()
+    off = call.offsets.tolist()
+    return [buf[a:b] for a, b in zip(off[:-1], off[1:])]

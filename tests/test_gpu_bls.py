@@ -22,12 +22,12 @@ def eng():
     e.close()
 
 
-def verify_both(eng, b, want_all, want_each=None, msgs=None, **kw):
+def verify_both(eng, b, want_all, want_each=None, msgs=None, rand=None, **kw):
     import torch
     import zkvm_pairings_amd as z
     msgs = b["msgs"] if msgs is None else msgs
     n = len(msgs)
-    rand = brc.rand_rows(n, 77)
+    rand = brc.rand_rows(n, 77) if rand is None else rand
     got = z.bls_verify_batch(b["pk"], msgs, b["sig"], DST, rand=rand, engine=eng, **kw)
     assert got is want_all
     # the _dev flavour gives the same answer
@@ -76,6 +76,104 @@ def test_swapped_neighbours_and_a_signature_outside_g2(eng, n):
     each = np.ones(n, dtype=bool)
     each[2] = False
     verify_both(eng, bad, False, each)
+
+
+def _down(n, *where):
+    each = np.ones(n, dtype=bool)
+    each[list(where)] = False
+    return each
+
+
+def _flags(n, *where):
+    f = np.zeros(n, dtype=np.uint8)
+    f[list(where)] = 1
+    return f
+
+
+@pytest.mark.parametrize("n", [5, 61])
+def test_points_checked_skips_the_points_check_and_nothing_else(eng, n):
+    b = brc.batch(n)
+    verify_both(eng, b, True, points_checked=True)
+    msgs = list(b["msgs"])
+    msgs[1] = msgs[1] + b"!"
+    verify_both(eng, b, False, _down(n, 1), msgs=msgs, points_checked=True)
+    # KeyValidate is no part of the skipped check: an identity public key still refuses the batch
+    for j in (0, n - 1):
+        verify_both(eng, b, False, _down(n, j), inf_pk=_flags(n, j), points_checked=True)
+
+
+@pytest.mark.parametrize("n", [5, 61])
+def test_an_identity_signature_fails_alone_and_next_to_an_identity_key(eng, n):
+    """inf_sig on a position whose stored signature is the valid one: dropping the flag would accept it.  With inf_pk on the same position
+    the pairing product of that check is one, and the identity key alone refuses it"""
+    b = brc.batch(n)
+    for j in (0, n // 2, n - 1):
+        verify_both(eng, b, False, _down(n, j), inf_sig=_flags(n, j))
+    j = n // 2
+    verify_both(eng, b, False, _down(n, j), inf_pk=_flags(n, j), inf_sig=_flags(n, j))
+
+
+@pytest.mark.parametrize("n", [5, 61])
+def test_bad_points_at_the_first_middle_and_last_position(eng, n):
+    """a public key on the curve outside G1, a valid key shifted by a point of small order (the one case the pairing product cannot see: a
+    verifier that skipped the points check would accept it), a public key off the curve, a signature off the curve (one outside G2: above)"""
+    b = brc.batch(n)
+    outside = [q for q in og.g1_points().values() if m.g1_on_curve(q) and not m.g1_torsion_free(q)]
+    assert outside
+    for k, j in enumerate((0, n // 2, n - 1)):
+        bad = dict(b, pk=b["pk"].copy())
+        bad["pk"][j] = brc.u64(h.g1_words(outside[k % len(outside)])[0])
+        verify_both(eng, bad, False, _down(n, j))
+        # pk + T, T of order 3 or 11: T is r times a point, so the pairing equation holds as it does for pk (the model's verify says so)
+        # and only the subgroup check refuses the key
+        _, pk, msg, sig = brc.signed_pool()[b["idx"][j]]
+        shifted = m.g1_add(pk, og.g1_points()[("order3", "order11", "order3_neg")[k]])
+        assert m.g1_on_curve(shifted) and not m.g1_torsion_free(shifted) and (n > 5 or h.verify(shifted, msg, sig, DST))
+        bad["pk"][j] = brc.u64(h.g1_words(shifted)[0])
+        verify_both(eng, bad, False, _down(n, j))
+        off = (pk[0], (pk[1] + 1) % h.P)
+        assert not m.g1_on_curve(off)
+        bad["pk"][j] = brc.u64(h.g1_words(off)[0])
+        verify_both(eng, bad, False, _down(n, j))
+        sig = brc.signed_pool()[b["idx"][j]][3]
+        off = (sig[0], (sig[1][0], (sig[1][1] + 1) % h.P))
+        assert not m.g2_on_curve(off)
+        bad = dict(b, sig=b["sig"].copy())
+        bad["sig"][j] = brc.u64(h.g2_words(off)[0])
+        verify_both(eng, bad, False, _down(n, j))
+
+
+@pytest.mark.parametrize("n", [5, 61])
+def test_a_zero_row_of_rand_fails_the_batch_and_half_zero_rows_do_not(eng, n):
+    """(a, b) = (0, 0) would drop a check from the product: the batch is refused although every signature holds (the per-signature path
+    takes no scalars: all flags up).  (a, 0) and (0, b) are non-zero exponents"""
+    b = brc.batch(n)
+    for j in (0, n // 2, n - 1):
+        rand = brc.rand_rows(n, 31 + j)
+        rand[j] = 0
+        verify_both(eng, b, False, np.ones(n, dtype=bool), rand=rand)
+    rand = brc.rand_rows(n, 35)
+    rand[0, 1] = 0
+    rand[n // 2, 0] = 0
+    rand[n - 1, 1] = 0
+    verify_both(eng, b, True, rand=rand)
+
+
+@pytest.mark.parametrize("n", [5, 61])
+def test_negated_pairs_and_duplicates(eng, n):
+    b = brc.batch(n)
+    pool = brc.signed_pool()
+    j = n // 2
+    _, pk, _, sig = pool[b["idx"][j]]
+    neg = dict(b, pk=b["pk"].copy(), sig=b["sig"].copy())
+    neg["pk"][j] = brc.u64(h.g1_words(m.g1_neg(pk))[0])
+    neg["sig"][j] = brc.u64(h.g2_words(m.g2_neg(sig))[0])
+    verify_both(eng, neg, True)                                   # e(-pk, H) e(-g1, -sig) = 1
+    neg["pk"][j] = b["pk"][j]
+    verify_both(eng, neg, False, _down(n, j))                     # (pk, m, -sig)
+    k = b["idx"][0]
+    dup = dict(pk=np.tile(b["pk"][0], (n, 1)), msgs=[pool[k][2]] * n, sig=np.tile(b["sig"][0], (n, 1)))
+    verify_both(eng, dup, True)
 
 
 def test_cancelling_forgeries_need_the_random_scalars(eng):

@@ -128,6 +128,36 @@ def test_clear_cofactor(eng):
     assert not eng.g2_is_valid(got, ginf).any()
 
 
+def test_map_from_fields_on_colliding_and_real_g_elements(eng):
+    """tests/h2c_adversarial.py in one call: pairs of different u with one image or opposite images (k_h2c_clear's first addition meets
+    H = 0, and r = 0 or not, on operands computed from different u, for the cross pairs along different branches of the map)
+    and u whose g(x1) lies in Fp (a residue: the root is real; a non-residue: the fallback of f2_sqrt_with_norm, a purely imaginary root).
+    tests/test_h2c_cpu.py has shown that the inputs are what they are called"""
+    import h2c_adversarial as ha
+    rows = ha.inputs()
+    pts, inf = both(eng, "g2_map_from_fields", (_u_rows([(a, b) for _, a, b in rows]),))
+    want, winf = brc.point_rows(ha.expected())
+    assert winf.sum() == 8
+    for j, (label, _, _) in enumerate(rows):
+        assert inf[j] == winf[j] and pts[j].tobytes() == want[j].tobytes(), (j, label)
+    assert not eng.g2_is_valid(pts, inf).any()
+
+
+def test_clear_cofactor_through_every_reachable_addition_branch(eng):
+    """the inputs whose additions tests/test_h2c_cpu.py has traced branch by branch (COFACTOR_BRANCHES there): the identity, points of G2,
+    every multiple of a point of order 13, the other small orders, and their sums with a point of G2; and four multiples of the generator
+    whose doubling at B = psi(P) - A meets an H that is zero mod p with non-zero limbs (NEAR_ZERO_MULTIPLES of tests/h2c_adversarial.py)"""
+    import h2c_adversarial as ha
+    cases = ha.cofactor_points()
+    rows, inf = brc.point_rows([q for _, q in cases])
+    got, ginf = both(eng, "g2_clear_cofactor", (rows,), inf=inf)
+    want, winf = brc.point_rows([r for r, _ in ha.cofactor_traces()])
+    assert 0 < winf.sum() < len(cases)
+    for j, (label, _) in enumerate(cases):
+        assert ginf[j] == winf[j] and got[j].tobytes() == want[j].tobytes(), (j, label)
+    assert not eng.g2_is_valid(got, ginf).any()
+
+
 def test_hash_to_g2_rfc_vectors_and_seeded_messages(eng):
     with open(os.path.join(ROOT, "tests", "golden", "h2c_vectors.json")) as f:
         v = json.load(f)

@@ -1,4 +1,5 @@
-"""The slice loops of the G1 NTT, FK20 (csrc/zkp_fk20.hip) and the KZG opening (csrc/zkp_poly.hip) on one MI355X (run with -m gpu): every
+"""The slice loops of the G1 NTT, FK20 (csrc/zkp_fk20.hip), the KZG opening (csrc/zkp_poly.hip) and of hash-to-G2 and the BLS verifier
+(csrc/zkp_bls.hip) on one MI355X (run with -m gpu): every
 call here is the smallest that crosses a slice boundary of its entry point and ends in a short last slice, its inputs and expected bytes
 are assembled from a small pool by a pseudo-random index sequence (tests/slice_pools.py), and tests/test_slices_cpu.py has shown without
 a GPU that a slice which took offset 0, the previous slice's offset, or another slice's rows in ANY operand cannot give these bytes.
@@ -119,3 +120,58 @@ def test_kzg_open_two_slices_with_a_short_last_one(eng, helper, bitrev):
     assert z.kzg_verify_batch(vs, c, zs[t], y_t, np.ascontiguousarray(proof.reshape(-1, 12)[t]), **args) is True
     y_bad = fr_rows([(int.from_bytes(y_t[k].tobytes(), "little") + (k == 2)) % R for k in range(3)])
     assert z.kzg_verify_batch(vs, c, zs[t], y_bad, np.ascontiguousarray(proof.reshape(-1, 12)[t]), **args) is False
+
+
+# ------------------------------------------------------------------------------------------------------------------- hash-to-G2 and the BLS verifier
+@pytest.mark.parametrize("points", [False, True])
+def test_hash_two_slices_of_mixed_length_messages(eng, points):
+    """2^17 + 61 messages of 0 .. 120 bytes behind a non-zero offsets[0]: k_h2f's message index and output pointer in the second slice, whose
+    four messages occur nowhere in the first; for hash_to_g2 also the u values and projective points of a slice written over the previous
+    slice's, and a last launch of k_h2c_clear with one full and one partial wavefront"""
+    import h2c_model as h
+    call = sp.hash_call(points)
+    name = "hash_to_g2" if points else "hash_to_field_g2"
+    keys = ("points", "inf") if points else ("u",)
+    got = getattr(eng, name)(call.msgs, h.ETH_DST, offsets=call.offsets)
+    same(call, dict(zip(keys, got if points else (got,))), name + " (host)")
+    got = getattr(eng, name)(to_dev(call.msgs), h.ETH_DST, offsets=to_dev(call.offsets))
+    same(call, dict(zip(keys, got if points else (got,))), name + " (dev)")
+
+
+def test_map_three_slices_with_an_identity_in_the_tail(eng):
+    """2 * 2^17 + 5 pairs of field elements: the input and output pointers of the second and third slice; (a, -a) among the five of the tail"""
+    call = sp.map_call()
+    assert call.want("inf")[call.n - call.tail:].any()
+    pts, inf = eng.g2_map_from_fields(call.arg("u"))
+    same(call, dict(points=pts, inf=inf), "g2_map_from_fields (host)")
+    pts, inf = eng.g2_map_from_fields(to_dev(call.arg("u")))
+    same(call, dict(points=pts, inf=inf), "g2_map_from_fields (dev)")
+
+
+def _verify(eng, call, msgs, dev):
+    import h2c_model as h
+    t = to_dev if dev else (lambda a: a)
+    got = eng.bls_verify(t(call.arg("pk")), t(msgs), t(call.arg("sig")), h.ETH_DST, offsets=t(call.offsets), rand=t(call.arg("rand")))
+    return bool(to_host(got)[0]) if dev else got
+
+
+def test_bls_verify_two_slices_holds(eng):
+    """2^17 + 6 model-signed messages: the hashed point of every check of the second slice must be its own for the product to be one"""
+    call = sp.verify_call()
+    assert _verify(eng, call, call.msgs, False) is True
+    assert _verify(eng, call, call.msgs, True) is True
+
+
+@pytest.mark.parametrize("where", [0, 1, 2])
+def test_bls_verify_one_forgery_on_either_side_of_the_boundary(eng, where):
+    """one message byte changed in the last item of the first slice, the first of the second, or the last of the call: the batch fails and
+    bls_verify_each names exactly that signature"""
+    import h2c_model as h
+    import zkvm_pairings_amd as z
+    call = sp.verify_call()
+    j = call.forged[where]
+    bad = sp.forged_messages(call, j)
+    assert _verify(eng, call, bad, False) is False
+    assert _verify(eng, call, bad, True) is False
+    each = z.bls_verify_each(call.arg("pk"), sp.message_list(call, bad), call.arg("sig"), h.ETH_DST, engine=eng)
+    assert np.nonzero(~each)[0].tolist() == [j]

@@ -87,6 +87,89 @@ def test_sswu_signs_the_exceptional_case_and_both_branches():
     assert h.map_from_fields(us[0], us[0]) == h.clear_cofactor_psi(m.g2_add(q, q))
 
 
+def test_adversarial_field_elements_have_their_stated_properties():
+    """tests/h2c_adversarial.py: what test_gpu_h2c.py feeds the map is what its docstring says, in the model"""
+    import h2c_adversarial as ha
+    # two facts k_h2c_map leans on: u^2 = -1 / Z has no solution, so Z^2 u^4 + Z u^2 vanishes at u = 0 only; and E' has no point at the
+    # isogeny's pole, so no u maps to the identity (which is why there is no such input)
+    assert not h.f2_is_square(m.f2_neg(m.f2_inv(h.Z_SSWU)))
+    assert not h.f2_is_square(ha.g_iso(h.KERNEL_X))
+    pairs = ha.colliding_pairs()
+    assert set(pairs) == {"same", "opposite", "cross_same", "cross_opposite"}
+    for kind, ps in pairs.items():
+        assert len(ps) >= 2, kind
+        cross, same = kind.startswith("cross"), kind.endswith("same")
+        for u0, u1 in ps:
+            assert u1 not in (u0, m.f2_neg(u0))
+            (p0, sq0), (p1, sq1) = h.sswu(u0), h.sswu(u1)
+            assert sq1 and sq0 == (not cross), kind                       # u1 on the x1 branch; u0 on it unless the pair is a cross pair
+            assert ha.x1_of(u1) == p0[0] == p1[0] and (ha.x1_of(u0) == p0[0]) == (not cross)
+            q0, q1 = h.iso3(p0), h.iso3(p1)
+            assert q0 is not None and q0 == (q1 if same else m.g2_neg(q1)), kind
+            for a, b in ((u0, u1), (u1, u0)):
+                assert h.map_from_fields(a, b) == (h.clear_cofactor_psi(m.g2_add(q0, q0)) if same else None)
+    real = ha.real_g_elements()
+    assert set(real) == {"residue", "nonresidue"}
+    for kind, us in real.items():
+        assert len(us) >= 4 and len(set(us)) == len(us), kind
+        for u in us:
+            gx = ha.g_iso(ha.x1_of(u))
+            (x, y), square = h.sswu(u)
+            assert gx[1] == 0 and square and x == ha.x1_of(u)
+            assert pow(gx[0], (h.P - 1) // 2, h.P) == (1 if kind == "residue" else h.P - 1)
+            assert (y[1] == 0 and y[0]) if kind == "residue" else (y[0] == 0 and y[1])          # a real root / a purely imaginary one
+    rows = ha.inputs()
+    assert len(rows) == 2 * sum(len(v) for v in pairs.values()) + sum(len(v) for v in real.values()) == len(set(rows)) == 24
+    assert {k for k, _, _ in rows} == {a + b for a in pairs for b in ("", "-swapped")} | {a + b for a in real for b in ("", "-second")}
+    assert [q is None for q in ha.expected()] == [k.split("-")[0].endswith("opposite") for k, _, _ in rows]
+    assert all(q is None or m.g2_torsion_free(q) for q in ha.expected())
+
+
+# what the inputs of tests/h2c_adversarial.py's cofactor_points reach in k_h2c_clear's additions (sites of h.clear_cofactor_trace)
+COFACTOR_BRANCHES = {("A", "p_inf"), ("A", "generic"), ("A", "cancel"), ("C", "p_inf"), ("C", "generic"), ("C", "cancel"),
+                     ("B", "p_inf"), ("B", "generic"), ("B", "dbl"),
+                     ("F0", "p_inf"), ("F0", "generic"), ("F1", "p_inf"), ("F1", "generic"), ("F2", "p_inf"), ("F2", "generic"),
+                     ("F3", "p_inf"), ("F3", "generic"), ("F3", "cancel")}
+
+
+def test_cofactor_trace_equals_both_formulas_and_reaches_the_stated_branches():
+    import h2c_adversarial as ha
+    pts, traces = ha.cofactor_points(), ha.cofactor_traces()
+    labels = [k for k, _ in pts]
+    assert len(set(labels)) == len(pts) == len(traces) and sum(k.startswith("order13*") for k in labels) == 12
+    assert {"identity", "generator", "e2-0", "fixture-order13", "fixture-cofactor", "order23", "order262069", "order13+g2", "order262069+g2"} <= set(labels)
+    hit = set()
+    for (label, q), (got, seen) in zip(pts, traces):
+        assert q is None or m.g2_on_curve(q), label
+        assert got == h.clear_cofactor_psi(q) == h.clear_cofactor_h_eff(q), label
+        hit |= seen
+    assert COFACTOR_BRANCHES <= hit, sorted(COFACTOR_BRANCHES - hit)
+    # which input takes which: the identity every p_inf of the tail; a point of G2 doubles at B (psi(P) = [x] P = -A); order 13 cancels
+    # in both ladders at the prefix 13 = 12 + 1; a point the cofactor kills ends in (-psi^2(2 P)) + psi^2(2 P)
+    by = dict(zip(labels, (s for _, s in traces)))
+    assert {("B", "p_inf"), ("F0", "p_inf"), ("F3", "p_inf")} <= by["identity"] and ("B", "dbl") in by["generator"]
+    assert len(ha.NEAR_ZERO_MULTIPLES) >= 4 and all(("B", "dbl") in by["generator*%d" % k] for k in ha.NEAR_ZERO_MULTIPLES)
+    assert all({("A", "cancel"), ("C", "cancel")} <= by["order13*%d" % k] for k in range(1, 13))
+    assert all(("F3", "cancel") in by["order%d" % ell] for ell in ha.SMALL_ORDERS[1:])
+    # the ladders' other exceptional branches.  #E2 and its prime factors:
+    order = 1
+    for q, e in ha.E2_FACTORS.items():
+        assert all(q % d for d in range(2, 513) if d * d <= q) if q < 1 << 18 else pow(2, q - 1, q) == 1, q      # trial division; Fermat for the two large ones
+        order *= q ** e
+    assert order == ha.E2_ORDER and m.g2_mul(pts[labels.index("e2-0")][1], order) is None
+    # At its additions after the first a ladder holds [v] Q, v in LADDER_ADDS, and adds Q: it doubles iff ord(Q) > 1 divides v - 1, and
+    # the operand is at infinity only when the accumulator is as well, which jac_add asks first.  So q_inf is unreachable, and dbl needs a
+    # prime factor of #E2 that divides some v - 1: a point of that order is then required to double, and where there is none the branch is
+    # absent because no point of E2 reaches it.
+    assert h.LADDER_ADDS == tuple(2 * (h.X_ABS >> b) for b in range(63, 0, -1) if (h.X_ABS >> (b - 1)) & 1) and h.X_ABS >> 63 == 1
+    doubling = sorted({q for v in h.LADDER_ADDS for q in ha.E2_FACTORS if (v - 1) % q == 0})
+    for q in doubling:
+        assert ("A", "dbl") in h.clear_cofactor_trace(ha.point_of_order(q))[1], q
+    if not doubling:
+        assert not {("A", "dbl"), ("C", "dbl"), ("A", "q_inf"), ("C", "q_inf")} & hit
+    assert sorted({q for v in h.LADDER_ADDS for q in ha.E2_FACTORS if (v + 1) % q == 0}) == [13]   # the one cancellation: 12 + 1
+
+
 def test_generator_constants_equal_the_suite():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))

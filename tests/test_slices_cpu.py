@@ -2,7 +2,8 @@
 own offsets (the docstring of tests/slice_pools.py states them).  The slice lengths the GPU tests assume are what the planning headers
 compute for the exact shapes; every shape crosses its boundaries and ends in a short slice; no slice of any input or expected output
 equals another slice's rows; the expected arrays read with a wrong offset differ from the true ones in every output array; the pools
-are consistent on integers by a second route.  No GPU and no library call."""
+are consistent on integers by a second route.  The same for the sliced calls of csrc/zkp_bls.hip: hash_to_field_g2, hash_to_g2, the map
+and the verifier (BLS_NAMES).  No GPU and no library call."""
 import os
 import subprocess
 
@@ -23,6 +24,7 @@ PROGRAM = """
 #include <cstdio>
 #include "zkp_fk20_plan.hpp"
 #include "zkp_poly_plan.hpp"
+#include "zkp_bls_plan.hpp"
 int main() {
     using namespace zkp;
     std::printf("g1ntt %%zu\\n", fk20::slice_vectors((size_t)%d, %du));
@@ -31,6 +33,12 @@ int main() {
     std::printf("g1ntt_max %%zu\\n", fk20::slice_vectors((size_t)4, fk20::G1NTT_MAX_LOG2));
     std::printf("fk20_max %%zu\\n", fk20::fk20_layout((size_t)4, fk20::FK20_MAX_LOG2).slice);
     std::printf("open_max %%zu\\n", poly::open_slice((size_t)16, poly::NTT_MAX_LOG2));
+    std::printf("bls_const %%zu\\n", bls::SLICE);
+    std::printf("bls_hash %%zu\\n", bls::layout((size_t)%d, false).slice);
+    std::printf("bls_map %%zu\\n", bls::layout((size_t)%d, false).slice);
+    std::printf("bls_verify %%zu\\n", bls::layout((size_t)%d, true).slice);
+    std::printf("bls_small %%zu\\n", bls::layout((size_t)5, true).slice);
+    std::printf("bls_stride %%zu\\n", (bls::layout((size_t)%d, false).hq - bls::layout((size_t)%d, false).pts) / (bls::POINT_I32 * 4));
     return 0;
 }
 """
@@ -41,7 +49,7 @@ def header_slices(tmp_path_factory):
     d = tmp_path_factory.mktemp("slices")
     src, exe = str(d / "slices.cpp"), str(d / "slices")
     with open(src, "w") as f:
-        f.write(PROGRAM % (sp.NTT_N_VEC, sp.NTT_LOG2, sp.FK20_N, sp.FK20_LOG2, sp.OPEN_N, sp.OPEN_LOG2))
+        f.write(PROGRAM % (sp.NTT_N_VEC, sp.NTT_LOG2, sp.FK20_N, sp.FK20_LOG2, sp.OPEN_N, sp.OPEN_LOG2, sp.HASH_N, sp.MAP_N, sp.VERIFY_N, sp.HASH_N, sp.HASH_N))
     cc = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", exe, src], capture_output=True, text=True, timeout=300)
     assert cc.returncode == 0, cc.stdout[-3000:] + cc.stderr[-3000:]
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
@@ -58,10 +66,12 @@ def calls():
     for bitrev in (False, True):
         out["fk20-bitrev%d" % bitrev] = sp.fk20_call(bitrev)
         out["open-bitrev%d" % bitrev] = sp.open_call(bitrev)
+    out["bls_field"], out["bls_hash"], out["bls_map"], out["bls_verify"] = sp.hash_call(False), sp.hash_call(True), sp.map_call(), sp.verify_call()
     return out
 
 
 NAMES = ["g1_ntt-flags0", "g1_ntt-flags3", "g1_ntt-finite", "fk20-bitrev0", "fk20-bitrev1", "open-bitrev0", "open-bitrev1"]
+BLS_NAMES = ["bls_field", "bls_hash", "bls_map", "bls_verify"]
 
 
 # ------------------------------------------------------------------------------------------------------------------- slice sizes and shapes
@@ -142,7 +152,7 @@ def test_in_domain_points_fall_in_both_slices_and_in_the_tail(calls):
 
 
 # ------------------------------------------------------------------------------------------------------------------- no shift invariance
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + BLS_NAMES)
 def test_no_slice_repeats_the_rows_of_another(calls, name):
     c = calls[name]
     arrays = list(c.inputs.items()) + list(c.outputs.items())
@@ -155,16 +165,23 @@ def test_no_slice_repeats_the_rows_of_another(calls, name):
             for what, (arr, per) in arrays:
                 if name == "g1_ntt-finite" and what == "inf":
                     continue                                                                     # all zero: the call passes inf = NULL
+                if what in getattr(c, "constant", ()):
+                    continue                                                                     # hash_to_g2's flags: no message gives the identity
                 assert sp.rows(arr, per, at, w).tobytes() != sp.rows(arr, per, other, w).tobytes(), (name, what, at, other)
 
 
 # ------------------------------------------------------------------------------------------------------------------- mutations
 @pytest.mark.parametrize("how", ["zero", "previous"])
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + BLS_NAMES)
 def test_a_wrong_offset_in_any_slice_changes_every_output_array(calls, name, how):
     c = calls[name]
-    assert set(c.outputs) == {"g1_ntt": {"out", "out_inf"}, "fk20": {"proof", "inf"}, "open": {"y", "proof", "inf"}}[name.split("-")[0]]
+    assert set(c.outputs) == {"g1_ntt": {"out", "out_inf"}, "fk20": {"proof", "inf"}, "open": {"y", "proof", "inf"}, "bls_field": {"u"},
+                              "bls_hash": {"points", "inf"}, "bls_map": {"points", "inf"}, "bls_verify": {"hq"}}[name.split("-")[0]]
+    assert getattr(c, "constant", set()) == ({"inf"} if name == "bls_hash" else set())
     for what, (arr, per) in c.outputs.items():
+        if what in getattr(c, "constant", ()):
+            assert not arr.any()                 # zero in every slice under any reading: compared on the GPU, but it cannot tell offsets apart
+            continue
         wrong = sp.reading(c, what, how)
         assert wrong.shape == arr.shape and wrong.tobytes() != arr.tobytes(), (name, what, how)
         # slice by slice: every slice after the first is wrong on its own, and the first is untouched
@@ -176,6 +193,90 @@ def test_a_wrong_offset_in_any_slice_changes_every_output_array(calls, name, how
     if len(c.starts) > 2:                        # three slices: the two readings are different mistakes
         for what in c.outputs:
             assert sp.reading(c, what, "zero").tobytes() != sp.reading(c, what, "previous").tobytes(), (name, what)
+
+
+# ------------------------------------------------------------------------------------------------------------------- hash-to-G2 and the BLS verifier
+def test_bls_slice_lengths_shapes_and_tails(header_slices, calls):
+    h = header_slices
+    assert h["bls_const"] == h["bls_hash"] == h["bls_map"] == h["bls_verify"] == sp.BLS_SLICE == 1 << 17
+    # a small call has the slice, and with it the stride of the point workspace, of its own size: 2 * 5 against 2 * 2^17 slots
+    assert h["bls_small"] == 5 and h["bls_stride"] == 2 * sp.BLS_SLICE
+    want = {"bls_field": (2, 61), "bls_hash": (2, 61), "bls_map": (3, 5), "bls_verify": (2, 6)}
+    tails = {"bls_field": sp.HASH_TAIL, "bls_hash": sp.HASH_TAIL, "bls_map": sp.MAP_TAIL, "bls_verify": sp.VERIFY_TAIL}
+    for name in BLS_NAMES:
+        c = calls[name]
+        n_slices, tail = want[name]
+        assert c.slice == sp.BLS_SLICE and c.starts == [s * c.slice for s in range(n_slices)] and c.tail == tail == c.n - c.starts[-1], name
+        for arr, per in list(c.inputs.values()) + list(c.outputs.values()):
+            assert per == 1 and arr.shape[0] == c.n and arr.flags.c_contiguous, name
+        # the last slice is made of pool items that occur nowhere before it, every one of them; the body uses all the others
+        last, body = c.idx[c.n - c.tail:], c.idx[:c.n - c.tail]
+        assert set(last.tolist()) == set(tails[name]) and set(body.tolist()) == set(range(sp.BLS_B)) - set(tails[name]), name
+        assert sp.BLS_B == 13 and c.slice % sp.BLS_B
+        for shift in list(range(1, 64)) + [c.slice]:
+            if shift < len(body):
+                assert (body[shift:] != body[:-shift]).mean() > 0.5, (name, shift)
+    assert calls["bls_map"].tail == len(sp.MAP_TAIL) and calls["bls_verify"].tail == len(sp.VERIFY_TAIL)          # distinct items
+    # 61 messages: 122 lanes of k_h2c_clear, one full wavefront and a partial one
+    assert 2 * calls["bls_hash"].tail == 64 + 58
+
+
+def test_bls_messages_are_packed_as_the_pool_has_them(calls):
+    for name in ("bls_field", "bls_hash", "bls_verify"):
+        c = calls[name]
+        off, msgs = c.offsets, c.pool["msgs"]
+        base = sp.VERIFY_BASE if name == "bls_verify" else sp.HASH_BASE
+        assert off.dtype == np.uint64 and off.shape == (c.n + 1,) and int(off[0]) == base > 0 and int(off[-1]) == c.msgs.size
+        assert (c.msgs[:base] == 0xA5).all() and (np.diff(off.astype(np.int64)) == np.array([len(x) for x in msgs])[c.idx]).all()
+        for j in (0, 1, 2, c.slice - 1, c.slice, c.slice + 1, c.n - 2, c.n - 1):
+            assert c.msgs[int(off[j]):int(off[j + 1])].tobytes() == msgs[c.idx[j]], (name, j)
+        lens = np.diff(off.astype(np.int64))
+        for at in c.starts:                                                                      # mixed lengths inside every wavefront's reach
+            assert len(set(lens[at:at + sp.window(c, at)].tolist())) >= 4, (name, at)
+    c = calls["bls_hash"]
+    assert tuple(len(x) for x in c.pool["msgs"]) == sp.HASH_LENGTHS and {0, 1, 55, 56, 64, 119, 120} <= set(sp.HASH_LENGTHS)
+    assert (np.diff(c.offsets.astype(np.int64))[:c.slice] == 0).any()                            # the empty message
+
+
+def test_bls_identity_outputs_on_both_sides_of_every_boundary(calls):
+    c = calls["bls_map"]
+    inf = c.want("inf")
+    assert inf[c.n - c.tail:].tolist() == [int(j == sp.MAP_INF) for j in sp.MAP_TAIL] and inf[c.n - c.tail:].sum() == 1
+    for at in c.starts[:-1]:
+        assert inf[at:at + 64].any() and not inf[at:at + 64].all() and inf[at + c.slice - 64:at + c.slice].any()
+    assert (c.want("points")[inf == 1] == np.eye(1, 24, 12, dtype=np.uint64)[0]).all()
+
+
+def test_bls_pools_are_consistent_by_a_second_route(calls):
+    import bls12_381_model as m
+    import bls_replay_cases as brc
+    import h2c_model as h
+    p = sp.hash_pool()
+    for j, msg in enumerate(p["msgs"]):
+        u0, u1 = h.hash_to_field_g2(msg, brc.DST)
+        assert _ints(p["u"][j].reshape(4, 6)) == [u0[0], u0[1], u1[0], u1[1]]
+        q = m.g2_add(h.iso3(h.sswu(u0)[0]), h.iso3(h.sswu(u1)[0]))
+        assert p["pts"][j] == h.clear_cofactor_h_eff(q) and p["pts"][j] is not None           # the psi formula made it; [h_eff] is the other route
+        assert h.words_g2(p["points"][j], p["inf"][j]) == p["pts"][j]
+    p = sp.map_pool()
+    assert [q is None for q in p["pts"]] == [j in (sp.MAP_INF, sp.MAP_INF_BODY) for j in range(sp.BLS_B)]
+    for (u0, u1), q, row, flag in zip(p["us"], p["pts"], p["points"], p["inf"]):
+        assert q == h.clear_cofactor_h_eff(m.g2_add(h.iso3(h.sswu(u0)[0]), h.iso3(h.sswu(u1)[0]))) and h.words_g2(row, flag) == q
+    p = sp.verify_pool()
+    assert len(p["pool"]) == sp.BLS_B
+    for j, (sk, pk, msg, sig) in enumerate(p["pool"]):
+        assert h.verify(pk, msg, sig, brc.DST) and pk == h.sk_to_pk(sk)
+        assert h.words_g2(p["hq"][j], 0) == brc.hashed(msg, brc.DST) and h.words_g2(p["sig"][j], 0) == sig
+    c = calls["bls_verify"]
+    assert c.forged == (c.slice - 1, c.slice, c.n - 1)
+    for j in c.forged:                                                                           # the forgeries of test_gpu_slices.py are forgeries
+        sk, pk, msg, sig = p["pool"][c.idx[j]]
+        bad = sp.forged_messages(c, j)
+        assert len(msg) > 0 and (bad != c.msgs).sum() == 1
+        lst = sp.message_list(c, bad)
+        assert lst[j] != msg and len(lst[j]) == len(msg) and lst[j - 1] == p["msgs"][c.idx[j - 1]]
+        assert not h.verify(pk, lst[j], sig, brc.DST)
+    assert sp.message_list(c)[c.slice] == p["msgs"][c.idx[c.slice]] and (c.arg("rand") != 0).all()
 
 
 # ------------------------------------------------------------------------------------------------------------------- the pools on integers
