@@ -14,6 +14,7 @@ pub mod fk20;
 pub mod cells;
 pub mod recover;
 pub mod bls;
+pub mod bls_agg;
 
 #[repr(C)]
 pub struct ZkpCtx {

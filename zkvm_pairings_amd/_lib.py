@@ -249,6 +249,15 @@ BLS_SIGNATURES = {
     "zkp_bls_verify_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
 }
 
+# name -> (restype, argtypes); MUST list every symbol include/zkp_bls_agg.h declares (G1 segment sums and FastAggregateVerify)
+AGG_SIGNATURES = {
+    "zkp_g1_segment_sum_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g1_segment_sum_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_bls_fast_aggregate_verify_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_fast_aggregate_verify_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp,
+                                                        c_vp]),
+}
+
 _lib = None
 
 
@@ -276,7 +285,7 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
-                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items())):
+                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items()) + list(AGG_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

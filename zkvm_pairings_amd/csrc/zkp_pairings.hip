@@ -21,6 +21,7 @@
 #include "../../include/zkp_cells.h"
 #include "../../include/zkp_recover.h"
 #include "../../include/zkp_bls.h"
+#include "../../include/zkp_bls_agg.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -40,6 +41,7 @@
 #include "zkp_cells.hpp"
 #include "zkp_recover.hpp"
 #include "zkp_bls.hpp"
+#include "zkp_bls_agg.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -488,6 +490,8 @@ struct zkp_ctx {
     int g1ntt_split_log2 = -1;
     void* bls_ws = nullptr;     // grow-only workspace of hash-to-G2 and the BLS verifier (zkp_bls_plan.hpp layout)
     size_t bls_cap = 0;
+    void* agg_ws = nullptr;     // grow-only workspace of the G1 segment sums and FastAggregateVerify (zkp_bls_agg_plan.hpp layout)
+    size_t agg_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -916,6 +920,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->poly_coset) (void)hipFree(c->poly_coset);
     if (c->fk20_ws) (void)hipFree(c->fk20_ws);
     if (c->bls_ws) (void)hipFree(c->bls_ws);
+    if (c->agg_ws) (void)hipFree(c->agg_ws);
     if (c->g1ntt_split) (void)hipFree(c->g1ntt_split);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
@@ -1662,6 +1667,16 @@ int grow_bls(zkp_ctx* c, size_t bytes, void** ws) {
         c->bls_cap = bytes;
     }
     *ws = c->bls_ws;
+    return ZKP_OK;
+}
+int grow_agg(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->agg_cap) {
+        if (c->agg_ws) { HIPCHK(c, hipFree(c->agg_ws)); c->agg_ws = nullptr; c->agg_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->agg_ws, bytes));
+        zkp_dbg_alloc("ctx.agg", c->agg_ws, bytes);
+        c->agg_cap = bytes;
+    }
+    *ws = c->agg_ws;
     return ZKP_OK;
 }
 int* bls_bad_word(zkp_ctx* c) { return c->validate ? c->d_flag + 2 : nullptr; }
@@ -3201,6 +3216,91 @@ int zkp_bls_verify_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* inf_pk, 
     int rc;
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n * 2)) || (rc = validate_dev(c, (const uint64_t*)d[2], n * 4)) ||
         (rc = zkp::bls_verify_dev(c, d[0], d[1], dm, dof, dd, dst_len, d[2], d[3], n, d[4], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- G1 segment sums and FastAggregateVerify (zkp_bls_agg.hip, include/zkp_bls_agg.h)
+namespace {
+bool agg_sum_args_bad(const zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, const void* out,
+                      const void* out_inf, const void* status) {
+    return !c || zkp::agg::args_bad(n_table, n_idx, n_seg) || (n_table && !table) || (n_idx && !idx) || ((n_seg || n_idx) && !seg_off) ||
+           (n_seg && (!out || !out_inf || !status));
+}
+bool agg_verify_args_bad(const zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, const void* msgs,
+                         const void* offsets, const void* dst, size_t dst_len, const void* sig, size_t n, const void* rand, int flags, const void* all_ok) {
+    return h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || n > zkp::bls::MAX_VERIFY_N ||
+           zkp::rlc::args_bad(n, 1, 1, 0) || (n && (!sig || !rand)) || zkp::agg::args_bad(n_table, n_idx, n) || (n_table && !table) || (n_idx && !idx) ||
+           ((n || n_idx) && !seg_off);
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_g1_segment_sum_batch_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, void* out,
+                                 void* out_inf, void* status, void* stream) {
+    if (agg_sum_args_bad(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, table, n_table * 2, S(stream))) return rc;
+    return zkp::agg_segment_sum_dev(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status, S(stream));
+}
+int zkp_g1_segment_sum_batch(zkp_ctx* c, const uint64_t* table, size_t n_table, const uint32_t* idx, size_t n_idx, const uint64_t* seg_off, size_t n_seg,
+                             uint64_t* out, uint8_t* out_inf, uint8_t* status) {
+    if (agg_sum_args_bad(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    if (!n_seg && !n_idx) return ZKP_OK;
+    if (zkp::agg::offsets_malformed(seg_off, n_seg, n_idx) || zkp::agg::rows_out_of_range(idx, n_idx, n_table)) return ZKP_ERR_ARG;
+    HostIO io(c);
+    const void* dt = io.in(0, table, n_table * 96);
+    const void* di = io.in(1, idx, n_idx * 4);
+    const void* ds = io.in(2, seg_off, (n_seg + 1) * 8);
+    void* dout = io.out(4, out, n_seg * 96);
+    void* dinf = io.out(5, out_inf, n_seg);
+    void* dst = io.out(6, status, n_seg);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dt, n_table * 2)) ||
+        (rc = zkp::agg_segment_sum_dev(c, dt, n_table, di, n_idx, ds, n_seg, dout, dinf, dst, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_fast_aggregate_verify_batch_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, const void* msgs,
+                                            const void* offsets, const void* dst, size_t dst_len, const void* sig, const void* inf_sig, size_t n,
+                                            const void* rand, int flags, void* all_ok, void* stream) {
+    if (agg_verify_args_bad(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, table, n_table * 2, S(stream))) || (rc = validate_on_stream(c, sig, n * 4, S(stream)))) return rc;
+    return zkp::agg_verify_dev(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+// the six arrays one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_fast_aggregate_verify_batch(zkp_ctx* c, const uint64_t* table, size_t n_table, const uint32_t* idx, size_t n_idx, const uint64_t* seg_off,
+                                        const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len, const uint64_t* sig,
+                                        const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags, int* all_ok) {
+    if (agg_verify_args_bad(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok) ||
+        offsets_malformed(msgs, offsets, n))
+        return ZKP_ERR_ARG;
+    if ((n || n_idx) && (zkp::agg::offsets_malformed(seg_off, n, n_idx) || zkp::agg::rows_out_of_range(idx, n_idx, n_table))) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[6] = {table, idx, seg_off, sig, inf_sig, rand};
+    const size_t bytes[6] = {n_table * 96, n_idx * 4, (n + 1) * 8, n * 192, n, n * 16};
+    size_t off[6], total = 0;
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[6];
+    for (int i = 0; i < 6; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_table * 2)) || (rc = validate_dev(c, (const uint64_t*)d[3], n * 4)) ||
+        (rc = zkp::agg_verify_dev(c, d[0], n_table, d[1], n_idx, d[2], dm, dof, dd, dst_len, d[3], d[4], n, d[5], flags, c->d_flag + 1, c->stream)))
         return rc;
     return io.finish();
 }

@@ -1096,6 +1096,81 @@ class PairingEngine:
                                                  ctypes.byref(ok)))
         return bool(ok.value)
 
+    # ------------------------------------------------------------------ committee aggregation (include/zkp_bls_agg.h)
+    @staticmethod
+    def _entries_np(idx, seg_off):
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+        if seg_off.size < 1:
+            raise ValueError("seg_off: n_seg + 1 values, at least one")
+        return idx, seg_off
+
+    def _entries_t(self, table, idx, seg_off):
+        import torch
+        self._t_check(table, 12, "table")
+        self._t_check(idx, None, "idx", dtypes=(torch.int32, torch.uint32))
+        self._t_check(seg_off, None, "seg_off", rows=1)
+        return table.numel() // 12, idx.numel(), seg_off.numel() - 1
+
+    def g1_segment_sum(self, table, idx, seg_off):
+        """out[j] = sum of (+/-) table[idx[e] & 0x7fffffff] over e in [seg_off[j], seg_off[j + 1]) (bit 31 of idx[e]: subtract;
+        zkp_g1_segment_sum_batch): (points (n_seg, 12), inf (n_seg,), status (n_seg,)).  table (n_table, 12) finite G1 points, idx uint32,
+        seg_off (n_seg + 1,) uint64.  Host arrays with malformed offsets or a row beyond the table raise; resident torch tensors (idx int32,
+        seg_off int64) stay on the GPU, where such a segment is the identity with status 1."""
+        if _is_torch(table):
+            import torch
+            n_table, n_idx, n_seg = self._entries_t(table, idx, seg_off)
+            out = torch.empty((n_seg, 12), dtype=table.dtype, device=table.device)
+            oi, st = torch.empty(n_seg, dtype=torch.uint8, device=table.device), torch.empty(n_seg, dtype=torch.uint8, device=table.device)
+            self._chk(self._lib.zkp_g1_segment_sum_batch_dev(self._h, self._tp(table), n_table, self._tp(idx), n_idx, self._tp(seg_off), n_seg, self._tp(out),
+                                                             self._tp(oi), self._tp(st), self._stream()))
+            return out, oi, st
+        table = _np(table, 12)
+        idx, seg_off = self._entries_np(idx, seg_off)
+        n_seg = seg_off.size - 1
+        out, oi, st = np.empty((n_seg, 12), dtype=np.uint64), np.empty(n_seg, dtype=np.uint8), np.empty(n_seg, dtype=np.uint8)
+        self._chk(self._lib.zkp_g1_segment_sum_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), n_seg, _ptr(out), _ptr(oi),
+                                                     _ptr(st)))
+        return out, oi, st
+
+    def bls_fast_aggregate_verify(self, table, idx, seg_off, msgs, sig, dst, offsets=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """n aggregate signatures, each by the committee idx[seg_off[i] .. seg_off[i + 1]) of the key table on message i
+        (zkp_bls_fast_aggregate_verify_batch): True iff bls_verify holds on the committees' key sums, no committee is empty and no row
+        lies beyond the table.  The arguments of g1_segment_sum and bls_verify; host arrays return a bool, resident torch tensors fill and
+        return all_ok (int32 (1,)) without synchronising."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(table):
+            import torch
+            n_table, n_idx, n = self._entries_t(table, idx, seg_off)
+            self._t_check(sig, 24, "sig")
+            msgs, offsets, n_msg, dst = self._msgs_t(msgs, offsets, dst)
+            if n_msg != n or sig.numel() // 24 != n:
+                raise ValueError("%d committees, %d messages, %d signatures" % (n, n_msg, sig.numel() // 24))
+            self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(table.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=table.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_fast_aggregate_verify_batch_dev(self._h, self._tp(table), n_table, self._tp(idx), n_idx, self._tp(seg_off), self._tp(msgs),
+                                                                        self._tp(offsets), self._tp(dst), dst.numel(), self._tp(sig), self._tp(inf_sig), n,
+                                                                        self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            return all_ok
+        table, sig = _np(table, 12), _np(sig, 24)
+        idx, seg_off = self._entries_np(idx, seg_off)
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        if seg_off.size - 1 != n or sig.shape[0] != n:
+            raise ValueError("%d committees, %d messages, %d signatures" % (seg_off.size - 1, n, sig.shape[0]))
+        isg = _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_fast_aggregate_verify_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), _ptr(buf), _ptr(off),
+                                                                _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

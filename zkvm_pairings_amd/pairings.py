@@ -949,3 +949,71 @@ def bls_verify_each_compressed(pk_bytes, msgs, sig_bytes, dst, engine=None):
     e = engine or default_engine()
     pk, ipk, sg, isg, dec = _bls_decompress(pk_bytes, sig_bytes, e)
     return dec & bls_verify_each(pk, msgs, sg, dst, inf_pk=ipk, inf_sig=isg, engine=e)
+
+
+# ------------------------------------------------------------------------------------------------ committee aggregation (include/zkp_bls_agg.h)
+SUBTRACT = 0x80000000   # bit 31 of an entry: subtract the table row
+
+
+def committee_entries(committees, bits=None, absent_from=None):
+    """Lists of table rows, one list per committee -> (idx uint32, seg_off uint64 (n + 1,)): the entries of g1_segment_sum and
+    bls_fast_aggregate_verify.  bits: one aggregation bitfield per committee (a sequence of 0 / 1, one per member): only the members whose
+    bit is set enter.  absent_from: the table row that holds the total of a committee (one row, or one per committee): the lists then name
+    the ABSENT members, and committee i becomes (+total_i, -a, -b, ...), "the aggregate of all minus the absent"."""
+    if bits is not None and absent_from is not None:
+        raise ValueError("bits selects the members that signed, absent_from takes the lists as the members that did not: give one")
+    committees = [list(c) for c in committees]
+    if bits is not None:
+        if len(bits) != len(committees) or any(len(b) != len(c) for b, c in zip(bits, committees)):
+            raise ValueError("one bit per member of every committee")
+        committees = [[r for r, b in zip(c, bs) if b] for c, bs in zip(committees, bits)]
+    for c in committees:
+        if any(not 0 <= int(r) < SUBTRACT for r in c):
+            raise ValueError("table rows lie in [0, 2^31)")
+    if absent_from is not None:
+        totals = [absent_from] * len(committees) if np.isscalar(absent_from) else list(absent_from)
+        if len(totals) != len(committees) or any(not 0 <= int(t) < SUBTRACT for t in totals):
+            raise ValueError("one total row in [0, 2^31) per committee")
+        committees = [[int(t)] + [int(r) | SUBTRACT for r in c] for t, c in zip(totals, committees)]
+    seg_off = np.zeros(len(committees) + 1, dtype=np.uint64)
+    if committees:
+        seg_off[1:] = np.cumsum([len(c) for c in committees], dtype=np.uint64)
+    idx = np.array([int(r) for c in committees for r in c], dtype=np.uint32)
+    return idx, seg_off
+
+
+def _entries(committees, bits, absent_from):
+    """committees as lists of rows (through committee_entries), or the ready pair (idx, seg_off) of arrays"""
+    if isinstance(committees, tuple) and len(committees) == 2 and isinstance(committees[0], np.ndarray):
+        if bits is not None or absent_from is not None:
+            raise ValueError("bits and absent_from shape lists of rows, not ready entries")
+        return (np.ascontiguousarray(committees[0], dtype=np.uint32).reshape(-1), np.ascontiguousarray(committees[1], dtype=np.uint64).reshape(-1))
+    return committee_entries(committees, bits, absent_from)
+
+
+def bls_aggregate_keys(table, committees, bits=None, absent_from=None, engine=None):
+    """the committees' aggregate public keys: (points (n, 12), inf (n,)) (PairingEngine.g1_segment_sum on committee_entries; committees
+    may also be a ready (idx, seg_off) pair)"""
+    idx, seg_off = _entries(committees, bits, absent_from)
+    out, inf, _ = (engine or default_engine()).g1_segment_sum(table, idx, seg_off)
+    return out, inf
+
+
+def bls_fast_aggregate_verify_batch(table, committees, msgs, sigs, dst, bits=None, absent_from=None, rand=None, points_checked=False, inf_sig=None,
+                                    engine=None):
+    """True iff every aggregate signature verifies under the sum of its committee's keys (PairingEngine.bls_fast_aggregate_verify): table
+    (n_table, 12) validated public keys, committees lists of rows (committee_entries) or a ready (idx, seg_off) pair, messages a list of
+    bytes, signatures (n, 24)"""
+    idx, seg_off = _entries(committees, bits, absent_from)
+    return (engine or default_engine()).bls_fast_aggregate_verify(table, idx, seg_off, msgs, sigs, dst, inf_sig=inf_sig, rand=rand,
+                                                                  points_checked=points_checked)
+
+
+def bls_fast_aggregate_verify_each(table, committees, msgs, sigs, dst, bits=None, absent_from=None, points_checked=False, inf_sig=None, engine=None):
+    """bool array (n,): aggregate i verifies - the segment sums, then bls_verify_each on them, ANDed with the statuses and with the
+    committee not being empty"""
+    e = engine or default_engine()
+    idx, seg_off = _entries(committees, bits, absent_from)
+    apk, inf, st = e.g1_segment_sum(table, idx, seg_off)
+    ok = bls_verify_each(apk, msgs, sigs, dst, points_checked=points_checked, inf_pk=inf, inf_sig=inf_sig, engine=e)
+    return ok & (np.asarray(st) == 0) & (np.diff(seg_off.astype(np.int64)) > 0)

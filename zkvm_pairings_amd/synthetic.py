@@ -393,3 +393,30 @@ def bls_instance(n, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256
     h, _ = engine.hash_to_g2(msgs, dst)
     sigs, _ = engine.g2_mul(h, sks)
     return sks, pks, msgs, sigs
+
+
+def bls_aggregate_instance(n_table, sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
+    """A table of n_table key pairs and one valid aggregate signature per committee size in `sizes`, from the seed: committee i draws
+    sizes[i] rows (with repetition) and signs message i with the SUM of their secret keys, sig_i = [sum sk] H(m_i) - which is what the
+    sum of the members' signatures is.  -> (sks (n_table, 4), table (n_table, 12), committees (list of lists), msgs, sigs (n, 24))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    n = len(sizes)
+    sks = scalars(seed ^ 0xA66, n_table)
+    table, _ = engine.g1_mul(G1_GENERATOR, sks) if n_table else (np.zeros((0, 12), dtype=np.uint64), None)
+    draw = splitmix64(seed ^ 0xC0117, int(sum(sizes)))
+    committees, at = [], 0
+    for k in sizes:
+        committees.append([int(v % np.uint64(n_table)) for v in draw[at:at + k]])
+        at += k
+    raw = splitmix64(seed ^ 0x5E5A, 9 * n).reshape(n, 9) if n else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [raw[i, 1:].tobytes()[:int(raw[i, 0]) % 64] for i in range(n)]
+    if n == 0:
+        return sks, table, committees, msgs, np.zeros((0, 24), dtype=np.uint64)
+    sums = np.stack([int_to_scalar(sum(scalar_to_int(sks[r]) for r in c) % R_ORDER) for c in committees])
+    h, _ = engine.hash_to_g2(msgs, dst)
+    sigs, inf = engine.g2_mul(h, sums)
+    sigs[inf != 0] = 0
+    sigs[inf != 0, 12] = 1
+    return sks, table, committees, msgs, sigs
