@@ -15,6 +15,7 @@ pub mod cells;
 pub mod recover;
 pub mod bls;
 pub mod bls_agg;
+pub mod bls_grouped;
 
 #[repr(C)]
 pub struct ZkpCtx {

@@ -1,6 +1,6 @@
 """MI355X-native batched BLS12-381 pairing engine behind the zkvm-pairings API shape.
 
-Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h and include/zkp_bls_agg.h); it raises if
+Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h, include/zkp_bls_agg.h and include/zkp_bls_grouped.h); it raises if
 the library has not been built.  There is no CPU fallback."""
 from . import _lib
 from ._lib import ZkpError
@@ -14,6 +14,7 @@ from .pairings import (R1CS, CellSetup, Fk20Setup, Fr, G1Affine, G2Affine, Groth
                        recover_polynomials_batch, recover_cells_and_kzg_proofs_batch,
                        hash_to_g2, bls_sign_batch, bls_verify_batch, bls_verify_each, bls_verify_batch_compressed, bls_verify_each_compressed,
                        committee_entries, bls_aggregate_keys, bls_fast_aggregate_verify_batch, bls_fast_aggregate_verify_each,
+                       group_by_message, bls_verify_grouped_batch, bls_fast_aggregate_verify_grouped_batch,
                        multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
@@ -23,4 +24,5 @@ __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "p
            "kzg_cell_verify_batch", "kzg_cell_verify_each", "recover_polynomials_batch", "recover_cells_and_kzg_proofs_batch",
            "hash_to_g2", "bls_sign_batch", "bls_verify_batch", "bls_verify_each", "bls_verify_batch_compressed", "bls_verify_each_compressed",
            "committee_entries", "bls_aggregate_keys", "bls_fast_aggregate_verify_batch", "bls_fast_aggregate_verify_each",
+           "group_by_message", "bls_verify_grouped_batch", "bls_fast_aggregate_verify_grouped_batch",
            "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

@@ -258,6 +258,18 @@ AGG_SIGNATURES = {
                                                         c_vp]),
 }
 
+# name -> (restype, argtypes); MUST list every symbol include/zkp_bls_grouped.h declares (scaled G1 segment sums and the verifiers grouped by message)
+GRP_SIGNATURES = {
+    "zkp_g1_scaled_segment_sum_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g1_scaled_segment_sum_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_bls_verify_grouped_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_verify_grouped_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
+    "zkp_bls_fast_aggregate_verify_grouped_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int,
+                                                            c_vp]),
+    "zkp_bls_fast_aggregate_verify_grouped_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp,
+                                                                c_int, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -285,7 +297,8 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
-                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items()) + list(AGG_SIGNATURES.items())):
+                                  list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items()) + list(AGG_SIGNATURES.items()) +
+                                  list(GRP_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

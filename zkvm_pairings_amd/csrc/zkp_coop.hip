@@ -1902,6 +1902,44 @@ __global__ void __launch_bounds__(64, 2) k_g1_mul_endo28(const uint64_t* base, c
     if (out_inf) out_inf[i] = pinf ? 1 : 0;
 }
 
+// rec[i] = [a_i + b_i z^2] P_i as a JACOBIAN record (zkp_bls_grouped.hip: the scaled keys go straight into the accumulation levels of
+// the bucket MSM, msm_accum(1, false, ...), so they never need to be affine).  k_g1_mul_endo28's joint double-and-add with its table in
+// LDS and the full jac_add, one (a, b) per point; no jac_affine and no wire conversion at the end: about 461 of the 1,500 products of
+// that kernel go.  A point at infinity and a zero (a, b) store the identity (1, 1, 0).
+__global__ void __launch_bounds__(64, 2) k_grp_scale(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, uint32_t n, int4* rec) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    F1 f{0};
+    const int lane = threadIdx.x;
+    __shared__ int4 park[5 * 4 * 64];   // 0 x, 1 y of P; 2..4 T (Jacobian)
+    const uint64_t a = ab[2 * (size_t)i], b = ab[2 * (size_t)i + 1];
+    JacP p;
+    fp28_from_wire(p.x, base + 12 * (size_t)i);
+    fp28_from_wire(p.y, base + 12 * (size_t)i + 6);
+    valid_park(park, lane, 0, p.x);
+    valid_park(park, lane, 1, p.y);
+    p.z = f.one();
+    jac_madd(f, p, [&](int v) -> Fp28 { return v == 0 ? f.mul(valid_unpark(park, lane, 0), f_const(K28_BETA)) : c_neg(valid_unpark(park, lane, 1)); });
+    jac_park(park, lane, 2, p);
+    jac_set_inf(f, p);
+    if (!(inf && inf[i])) {
+#pragma unroll 1
+        for (int bit = 63; bit >= 0; bit--) {
+            jac_dbl(f, p);
+            const int sel = (int)((a >> bit) & 1) | (int)((b >> bit) & 1) << 1;   // 1: P, 2: phi'(P), 3: T
+            if (sel)
+                jac_add(f, p, [&](int v) -> Fp28 {
+                    if (sel == 3) return valid_unpark(park, lane, 2 + v);
+                    if (v == 2) return f.one();
+                    const Fp28 q = valid_unpark(park, lane, v);
+                    if (sel == 1) return q;
+                    return v == 0 ? f.mul(q, f_const(K28_BETA)) : c_neg(q);
+                });
+        }
+    }
+    jrec_st<1>(rec, i, 0, p);
+}
+
 // =============================================================================== the G1 NTT and the FK20 scalar products (zkp_fk20.hip drives
 // them; zkp_fk20_plan.hpp holds every index).  One lane per butterfly, Jacobian records (jrec_*) in a workspace between the stages, every
 // stage in place: a lane reads and writes the same two records.
@@ -3094,6 +3132,11 @@ hipError_t coop_g1_mul_endo(const uint64_t* base, const uint8_t* inf, const uint
     if (!n) return hipSuccess;
     if (!per) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_g1_mul_endo28, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, base, inf, ab, (uint32_t)n, per, out, out_inf);
+    return hipGetLastError();
+}
+hipError_t grp_scale(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, uint32_t n, void* rec, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_grp_scale, dim3((n + 63) / 64), dim3(64), 0, s, base, inf, ab, n, (int4*)rec);
     return hipGetLastError();
 }
 hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s) {

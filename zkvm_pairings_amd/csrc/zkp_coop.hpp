@@ -41,6 +41,9 @@ hipError_t coop_h2c_clear(const uint64_t* pts, const uint8_t* inf, const int32_t
 // out[i] = [a] P_i + [b] (beta x_i, -y_i) with (a, b) = ab[2 (i / per)], ab[2 (i / per) + 1] (= [a + b z^2] P_i in G1); inf / out_inf may be null
 hipError_t coop_g1_mul_endo(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, size_t n, uint32_t per, uint64_t* out, uint8_t* out_inf,
                             hipStream_t s);
+// rec[i] = [a_i + b_i z^2] P_i as Jacobian records (192 B each) with (a_i, b_i) = ab[2 i], ab[2 i + 1]: the input of msm_accum(1, false, ...);
+// inf may be null (zkp_bls_grouped.hip)
+hipError_t grp_scale(const uint64_t* base, const uint8_t* inf, const uint64_t* ab, uint32_t n, void* rec, hipStream_t s);
 // the bucket MSM's launches (zkp_coop.hip, "group addition and bucket MSM"; driven by zkp_msm.hip, sized by zkp_msm_plan.hpp)
 hipError_t msm_points(const uint64_t* w, uint32_t n_fp, void* rec, hipStream_t s);
 hipError_t msm_digits(const uint64_t* sc, const uint8_t* inf, uint32_t terms, uint32_t m, int shared, uint32_t c, uint32_t windows, uint32_t* keys,

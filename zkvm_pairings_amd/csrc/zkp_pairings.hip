@@ -22,6 +22,7 @@
 #include "../../include/zkp_recover.h"
 #include "../../include/zkp_bls.h"
 #include "../../include/zkp_bls_agg.h"
+#include "../../include/zkp_bls_grouped.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -42,6 +43,7 @@
 #include "zkp_recover.hpp"
 #include "zkp_bls.hpp"
 #include "zkp_bls_agg.hpp"
+#include "zkp_bls_grouped.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -492,6 +494,8 @@ struct zkp_ctx {
     size_t bls_cap = 0;
     void* agg_ws = nullptr;     // grow-only workspace of the G1 segment sums and FastAggregateVerify (zkp_bls_agg_plan.hpp layout)
     size_t agg_cap = 0;
+    void* grp_ws = nullptr;     // grow-only workspace of the scaled segment sums and the grouped verifiers (zkp_bls_grouped_plan.hpp layout)
+    size_t grp_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -921,6 +925,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->fk20_ws) (void)hipFree(c->fk20_ws);
     if (c->bls_ws) (void)hipFree(c->bls_ws);
     if (c->agg_ws) (void)hipFree(c->agg_ws);
+    if (c->grp_ws) (void)hipFree(c->grp_ws);
     if (c->g1ntt_split) (void)hipFree(c->g1ntt_split);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
@@ -1679,6 +1684,17 @@ int grow_agg(zkp_ctx* c, size_t bytes, void** ws) {
     *ws = c->agg_ws;
     return ZKP_OK;
 }
+int grow_grp(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->grp_cap) {
+        if (c->grp_ws) { HIPCHK(c, hipFree(c->grp_ws)); c->grp_ws = nullptr; c->grp_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->grp_ws, bytes));
+        zkp_dbg_alloc("ctx.grp", c->grp_ws, bytes);
+        c->grp_cap = bytes;
+    }
+    *ws = c->grp_ws;
+    return ZKP_OK;
+}
+int grow_prod(zkp_ctx* c, size_t records) { return ensure_prod(c, records); }
 int* bls_bad_word(zkp_ctx* c) { return c->validate ? c->d_flag + 2 : nullptr; }
 int* validation_word(zkp_ctx* c) { return c->d_flag + 2; }
 int mul(zkp_ctx* c, int which, const void* base, size_t stride, const void* sc, size_t n, void* out, void* out_inf, hipStream_t s) {
@@ -3301,6 +3317,139 @@ int zkp_bls_fast_aggregate_verify_batch(zkp_ctx* c, const uint64_t* table, size_
     int rc;
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_table * 2)) || (rc = validate_dev(c, (const uint64_t*)d[3], n * 4)) ||
         (rc = zkp::agg_verify_dev(c, d[0], n_table, d[1], n_idx, d[2], dm, dof, dd, dst_len, d[3], d[4], n, d[5], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- scaled G1 segment sums and the verifiers grouped by message (zkp_bls_grouped.hip,
+// include/zkp_bls_grouped.h)
+namespace {
+bool grp_sum_args_bad(const zkp_ctx* c, const void* pts, const void* rand, size_t n, const void* seg_off, size_t n_seg, const void* out, const void* out_inf,
+                      const void* status) {
+    return !c || zkp::grp::args_bad(n, n_seg) || (n && (!pts || !rand)) || ((n_seg || n) && !seg_off) || (n_seg && (!out || !out_inf || !status));
+}
+bool grp_verify_args_bad(const zkp_ctx* c, const void* pk, const void* grp_off, const void* msgs, const void* offsets, size_t m, const void* dst, size_t dst_len,
+                         const void* sig, size_t n, const void* rand, int flags, const void* all_ok) {
+    return h2c_msgs_bad(c, msgs, offsets, m, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || zkp::grp::args_bad(n, m) ||
+           n > zkp::bls::MAX_VERIFY_N || (n && zkp::rlc::args_bad(n, 1, 1, 0)) || (n && (!pk || !sig || !rand || !grp_off));
+}
+bool grp_fav_args_bad(const zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, const void* grp_off,
+                      const void* msgs, const void* offsets, size_t m, const void* dst, size_t dst_len, const void* sig, size_t n, const void* rand, int flags,
+                      const void* all_ok) {
+    return grp_verify_args_bad(c, sig, grp_off, msgs, offsets, m, dst, dst_len, sig, n, rand, flags, all_ok) || zkp::agg::args_bad(n_table, n_idx, n) ||
+           (n_table && !table) || (n_idx && !idx) || ((n || n_idx) && !seg_off);
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_g1_scaled_segment_sum_batch_dev(zkp_ctx* c, const void* pts, const void* inf, const void* rand, size_t n, const void* seg_off, size_t n_seg, void* out,
+                                        void* out_inf, void* status, void* stream) {
+    if (grp_sum_args_bad(c, pts, rand, n, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, pts, n * 2, S(stream))) return rc;
+    return zkp::grp_scaled_segment_sum_dev(c, pts, inf, rand, n, seg_off, n_seg, out, out_inf, status, S(stream));
+}
+int zkp_g1_scaled_segment_sum_batch(zkp_ctx* c, const uint64_t* pts, const uint8_t* inf, const uint64_t* rand, size_t n, const uint64_t* seg_off, size_t n_seg,
+                                    uint64_t* out, uint8_t* out_inf, uint8_t* status) {
+    if (grp_sum_args_bad(c, pts, rand, n, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    if (!n_seg && !n) return ZKP_OK;
+    if (zkp::grp::offsets_malformed(seg_off, n_seg, n)) return ZKP_ERR_ARG;
+    HostIO io(c);
+    const void* dp = io.in(0, pts, n * 96);
+    const void* dr = io.in(1, rand, n * 16);
+    const void* ds = io.in(2, seg_off, (n_seg + 1) * 8);
+    const void* di = io.in(3, inf, n);
+    void* dout = io.out(4, out, n_seg * 96);
+    void* dinf = io.out(5, out_inf, n_seg);
+    void* dst = io.out(6, status, n_seg);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dp, n * 2)) ||
+        (rc = zkp::grp_scaled_segment_sum_dev(c, dp, di, dr, n, ds, n_seg, dout, dinf, dst, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_verify_grouped_batch_dev(zkp_ctx* c, const void* pk, const void* inf_pk, const void* grp_off, const void* msgs, const void* offsets, size_t m,
+                                     const void* dst, size_t dst_len, const void* sig, const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok,
+                                     void* stream) {
+    if (grp_verify_args_bad(c, pk, grp_off, msgs, offsets, m, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, pk, n * 2, S(stream))) || (rc = validate_on_stream(c, sig, n * 4, S(stream)))) return rc;
+    return zkp::grp_verify_dev(c, pk, inf_pk, grp_off, msgs, offsets, m, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+// the six arrays one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_verify_grouped_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* inf_pk, const uint64_t* grp_off, const uint8_t* msgs, const uint64_t* offsets,
+                                 size_t m, const uint8_t* dst, size_t dst_len, const uint64_t* sig, const uint8_t* inf_sig, size_t n, const uint64_t* rand,
+                                 int flags, int* all_ok) {
+    if (grp_verify_args_bad(c, pk, grp_off, msgs, offsets, m, dst, dst_len, sig, n, rand, flags, all_ok) || offsets_malformed(msgs, offsets, m)) return ZKP_ERR_ARG;
+    if (grp_off && zkp::grp::offsets_malformed(grp_off, m, n)) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[6] = {pk, inf_pk, grp_off, sig, inf_sig, rand};
+    const size_t bytes[6] = {n * 96, n, (m + 1) * 8, n * 192, n, n * 16};
+    size_t off[6], total = 0;
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, m, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[6];
+    for (int i = 0; i < 6; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n * 2)) || (rc = validate_dev(c, (const uint64_t*)d[3], n * 4)) ||
+        (rc = zkp::grp_verify_dev(c, d[0], d[1], d[2], dm, dof, m, dd, dst_len, d[3], d[4], n, d[5], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_fast_aggregate_verify_grouped_batch_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off,
+                                                    const void* grp_off, const void* msgs, const void* offsets, size_t m, const void* dst, size_t dst_len,
+                                                    const void* sig, const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok, void* stream) {
+    if (grp_fav_args_bad(c, table, n_table, idx, n_idx, seg_off, grp_off, msgs, offsets, m, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, table, n_table * 2, S(stream))) || (rc = validate_on_stream(c, sig, n * 4, S(stream)))) return rc;
+    return zkp::grp_fast_aggregate_verify_dev(c, table, n_table, idx, n_idx, seg_off, grp_off, msgs, offsets, m, dst, dst_len, sig, inf_sig, n, rand, flags,
+                                              (int*)all_ok, S(stream));
+}
+// the seven arrays one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_fast_aggregate_verify_grouped_batch(zkp_ctx* c, const uint64_t* table, size_t n_table, const uint32_t* idx, size_t n_idx, const uint64_t* seg_off,
+                                                const uint64_t* grp_off, const uint8_t* msgs, const uint64_t* offsets, size_t m, const uint8_t* dst,
+                                                size_t dst_len, const uint64_t* sig, const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags,
+                                                int* all_ok) {
+    if (grp_fav_args_bad(c, table, n_table, idx, n_idx, seg_off, grp_off, msgs, offsets, m, dst, dst_len, sig, n, rand, flags, all_ok) ||
+        offsets_malformed(msgs, offsets, m))
+        return ZKP_ERR_ARG;
+    if ((n || n_idx) && (zkp::agg::offsets_malformed(seg_off, n, n_idx) || zkp::agg::rows_out_of_range(idx, n_idx, n_table))) return ZKP_ERR_ARG;
+    if (grp_off && zkp::grp::offsets_malformed(grp_off, m, n)) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[7] = {table, idx, seg_off, grp_off, sig, inf_sig, rand};
+    const size_t bytes[7] = {n_table * 96, n_idx * 4, (n + 1) * 8, (m + 1) * 8, n * 192, n, n * 16};
+    size_t off[7], total = 0;
+    for (int i = 0; i < 7; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, m, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[7];
+    for (int i = 0; i < 7; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_table * 2)) || (rc = validate_dev(c, (const uint64_t*)d[4], n * 4)) ||
+        (rc = zkp::grp_fast_aggregate_verify_dev(c, d[0], n_table, d[1], n_idx, d[2], d[3], dm, dof, m, dd, dst_len, d[4], d[5], n, d[6], flags, c->d_flag + 1,
+                                                 c->stream)))
         return rc;
     return io.finish();
 }

@@ -1171,6 +1171,125 @@ class PairingEngine:
                                                                 _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags, ctypes.byref(ok)))
         return bool(ok.value)
 
+    # ------------------------------------------------------------------ verification grouped by message (include/zkp_bls_grouped.h)
+    @staticmethod
+    def _offsets_np(off, name):
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("%s: count + 1 values, at least one" % name)
+        return off
+
+    def g1_scaled_segment_sum(self, pts, rand, seg_off, inf=None):
+        """out[g] = sum of [a_i + b_i z^2] pts[i] over i in [seg_off[g], seg_off[g + 1]) with (a_i, b_i) = rand[i]
+        (zkp_g1_scaled_segment_sum_batch): (points (n_seg, 12), inf (n_seg,), status (n_seg,)).  pts (n, 12) G1 points, rand (n, 2) uint64,
+        seg_off (n_seg + 1,) uint64.  Host arrays with malformed offsets raise; resident torch tensors (int64) stay on the GPU, where a
+        malformed call gives identities with status 1."""
+        if _is_torch(pts):
+            import torch
+            self._t_check(pts, 12, "pts")
+            n = pts.numel() // 12
+            self._t_check(rand, 2, "rand", rows=n)
+            self._t_check(seg_off, None, "seg_off", rows=1)
+            self._t_bytes(inf, n, "inf")
+            n_seg = seg_off.numel() - 1
+            out = torch.empty((n_seg, 12), dtype=pts.dtype, device=pts.device)
+            oi, st = torch.empty(n_seg, dtype=torch.uint8, device=pts.device), torch.empty(n_seg, dtype=torch.uint8, device=pts.device)
+            self._chk(self._lib.zkp_g1_scaled_segment_sum_batch_dev(self._h, self._tp(pts), self._tp(inf), self._tp(rand), n, self._tp(seg_off), n_seg,
+                                                                    self._tp(out), self._tp(oi), self._tp(st), self._stream()))
+            return out, oi, st
+        pts, r = _np(pts, 12), _np(rand, 2)
+        n = pts.shape[0]
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d points" % (r.shape[0], n))
+        seg_off = self._offsets_np(seg_off, "seg_off")
+        i = _flags(inf, n, "inf")
+        n_seg = seg_off.size - 1
+        out, oi, st = np.empty((n_seg, 12), dtype=np.uint64), np.empty(n_seg, dtype=np.uint8), np.empty(n_seg, dtype=np.uint8)
+        self._chk(self._lib.zkp_g1_scaled_segment_sum_batch(self._h, _ptr(pts), _ptr(i), _ptr(r), n, _ptr(seg_off), n_seg, _ptr(out), _ptr(oi), _ptr(st)))
+        return out, oi, st
+
+    def bls_verify_grouped(self, pk, grp_off, msgs, sig, dst, offsets=None, inf_pk=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """n BLS signatures ORDERED BY MESSAGE over m distinct messages (zkp_bls_verify_grouped_batch): signatures grp_off[g] .. grp_off[g + 1]
+        sign msgs[g].  The answer of bls_verify on the messages expanded per signature with the same rand, from m hashes and m + 1 Miller
+        loops.  Host arrays return a bool; resident torch tensors fill and return all_ok (int32 (1,)) without synchronising."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(pk):
+            import torch
+            self._t_check(pk, 12, "pk"), self._t_check(sig, 24, "sig")
+            n = pk.numel() // 12
+            msgs, offsets, m, dst = self._msgs_t(msgs, offsets, dst)
+            self._t_check(grp_off, None, "grp_off", rows=m + 1)
+            if sig.numel() // 24 != n:
+                raise ValueError("%d public keys, %d signatures" % (n, sig.numel() // 24))
+            self._t_bytes(inf_pk, n, "inf_pk"), self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(pk.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=pk.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_verify_grouped_batch_dev(self._h, self._tp(pk), self._tp(inf_pk), self._tp(grp_off), self._tp(msgs), self._tp(offsets), m,
+                                                                 self._tp(dst), dst.numel(), self._tp(sig), self._tp(inf_sig), n, self._tp(rand), flags,
+                                                                 self._tp(all_ok), self._stream()))
+            return all_ok
+        buf, off, m, d = self._msgs_np(msgs, offsets, dst)
+        pk, sig = _np(pk, 12), _np(sig, 24)
+        n = pk.shape[0]
+        grp_off = self._offsets_np(grp_off, "grp_off")
+        if sig.shape[0] != n or grp_off.size != m + 1:
+            raise ValueError("%d public keys, %d signatures, %d messages, %d group offsets" % (n, sig.shape[0], m, grp_off.size))
+        ip, isg = _flags(inf_pk, n, "inf_pk"), _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_verify_grouped_batch(self._h, _ptr(pk), _ptr(ip), _ptr(grp_off), _ptr(buf), _ptr(off), m, _ptr(d), d.size, _ptr(sig), _ptr(isg),
+                                                         n, _ptr(r), flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def bls_fast_aggregate_verify_grouped(self, table, idx, seg_off, grp_off, msgs, sig, dst, offsets=None, inf_sig=None, rand=None, points_checked=False,
+                                          all_ok=None):
+        """n aggregate signatures ORDERED BY MESSAGE, each by the committee idx[seg_off[i] .. seg_off[i + 1]) of the key table, over m
+        distinct messages (zkp_bls_fast_aggregate_verify_grouped_batch): the answer of bls_fast_aggregate_verify on the messages expanded
+        per aggregate.  The arguments of bls_fast_aggregate_verify and bls_verify_grouped."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(table):
+            import torch
+            n_table, n_idx, n = self._entries_t(table, idx, seg_off)
+            self._t_check(sig, 24, "sig")
+            msgs, offsets, m, dst = self._msgs_t(msgs, offsets, dst)
+            self._t_check(grp_off, None, "grp_off", rows=m + 1)
+            if sig.numel() // 24 != n:
+                raise ValueError("%d committees, %d signatures" % (n, sig.numel() // 24))
+            self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(table.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=table.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_fast_aggregate_verify_grouped_batch_dev(self._h, self._tp(table), n_table, self._tp(idx), n_idx, self._tp(seg_off),
+                                                                                self._tp(grp_off), self._tp(msgs), self._tp(offsets), m, self._tp(dst),
+                                                                                dst.numel(), self._tp(sig), self._tp(inf_sig), n, self._tp(rand), flags,
+                                                                                self._tp(all_ok), self._stream()))
+            return all_ok
+        table, sig = _np(table, 12), _np(sig, 24)
+        idx, seg_off = self._entries_np(idx, seg_off)
+        buf, off, m, d = self._msgs_np(msgs, offsets, dst)
+        n = seg_off.size - 1
+        grp_off = self._offsets_np(grp_off, "grp_off")
+        if sig.shape[0] != n or grp_off.size != m + 1:
+            raise ValueError("%d committees, %d signatures, %d messages, %d group offsets" % (n, sig.shape[0], m, grp_off.size))
+        isg = _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_fast_aggregate_verify_grouped_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), _ptr(grp_off),
+                                                                        _ptr(buf), _ptr(off), m, _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags,
+                                                                        ctypes.byref(ok)))
+        return bool(ok.value)
+
     # ------------------------------------------------------------------ the Groth16 producer side (include/zkp_prove.h)
     def _csr(self, mat, name, keep, resident):
         """(n_rows, n_cols, row_ptr, col, val) -> zkp_fr_csr; row_ptr (n_rows + 1) and col (nnz) 32-bit, val (nnz, 4) canonical"""

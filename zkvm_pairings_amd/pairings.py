@@ -1017,3 +1017,64 @@ def bls_fast_aggregate_verify_each(table, committees, msgs, sigs, dst, bits=None
     apk, inf, st = e.g1_segment_sum(table, idx, seg_off)
     ok = bls_verify_each(apk, msgs, sigs, dst, points_checked=points_checked, inf_pk=inf, inf_sig=inf_sig, engine=e)
     return ok & (np.asarray(st) == 0) & (np.diff(seg_off.astype(np.int64)) > 0)
+
+
+# ------------------------------------------------------------------------------------------------ verification grouped by message (include/zkp_bls_grouped.h)
+def group_by_message(messages):
+    """A list of n messages (bytes) -> (perm int64 (n,), distinct (list of m bytes), grp_off uint64 (m + 1,)): the order bls_verify_grouped
+    wants.  The distinct messages keep the order of their first appearance and the signatures of one message their order: signatures
+    perm[grp_off[g] : grp_off[g + 1]] sign distinct[g]."""
+    first, members = {}, []
+    for i, msg in enumerate(messages):
+        msg = bytes(msg)
+        g = first.setdefault(msg, len(members))
+        if g == len(members):
+            members.append([])
+        members[g].append(i)
+    distinct = [None] * len(members)
+    for msg, g in first.items():
+        distinct[g] = msg
+    grp_off = np.zeros(len(members) + 1, dtype=np.uint64)
+    if members:
+        grp_off[1:] = np.cumsum([len(x) for x in members], dtype=np.uint64)
+    perm = np.array([i for x in members for i in x], dtype=np.int64)
+    return perm, distinct, grp_off
+
+
+def _take(rows, perm, cols=None, dtype=np.uint64):
+    if rows is None:
+        return None
+    rows = np.ascontiguousarray(rows, dtype=dtype)
+    return np.ascontiguousarray((rows.reshape(-1, cols) if cols else rows.reshape(-1))[perm])
+
+
+def bls_verify_grouped_batch(pks, msgs, sigs, dst, rand=None, points_checked=False, inf_pk=None, inf_sig=None, engine=None):
+    """bls_verify_batch with one hash and one Miller pair per DISTINCT message (PairingEngine.bls_verify_grouped): the arguments and the
+    answer of bls_verify_batch; the signatures are put in the order of group_by_message here, rand (per signature, in the caller's order)
+    with them"""
+    perm, distinct, grp_off = group_by_message(msgs)
+    pks, sigs = _take(pks, perm, 12), _take(sigs, perm, 24)
+    if pks.shape[0] != perm.size or sigs.shape[0] != perm.size:
+        raise ValueError("%d messages, %d public keys, %d signatures" % (perm.size, pks.shape[0], sigs.shape[0]))
+    return (engine or default_engine()).bls_verify_grouped(pks, grp_off, distinct, sigs, dst, inf_pk=_take(inf_pk, perm, dtype=np.uint8),
+                                                           inf_sig=_take(inf_sig, perm, dtype=np.uint8), rand=_take(rand, perm, 2),
+                                                           points_checked=points_checked)
+
+
+def bls_fast_aggregate_verify_grouped_batch(table, committees, msgs, sigs, dst, bits=None, absent_from=None, rand=None, points_checked=False, inf_sig=None,
+                                            engine=None):
+    """bls_fast_aggregate_verify_batch with one hash and one Miller pair per DISTINCT message (PairingEngine.bls_fast_aggregate_verify_grouped):
+    the arguments and the answer of bls_fast_aggregate_verify_batch; committees, signatures and rand are put in the order of
+    group_by_message here"""
+    idx, seg_off = _entries(committees, bits, absent_from)
+    perm, distinct, grp_off = group_by_message(msgs)
+    if seg_off.size - 1 != perm.size:
+        raise ValueError("%d committees, %d messages" % (seg_off.size - 1, perm.size))
+    lo, hi = seg_off[:-1].astype(np.int64)[perm], seg_off[1:].astype(np.int64)[perm]
+    new_off = np.zeros(perm.size + 1, dtype=np.uint64)
+    if perm.size:
+        new_off[1:] = np.cumsum(hi - lo).astype(np.uint64)
+    new_idx = np.concatenate([idx[a:b] for a, b in zip(lo, hi)]).astype(np.uint32) if perm.size else idx[:0]
+    return (engine or default_engine()).bls_fast_aggregate_verify_grouped(table, new_idx, new_off, grp_off, distinct, _take(sigs, perm, 24), dst,
+                                                                          inf_sig=_take(inf_sig, perm, dtype=np.uint8), rand=_take(rand, perm, 2),
+                                                                          points_checked=points_checked)

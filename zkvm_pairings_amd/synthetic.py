@@ -420,3 +420,25 @@ def bls_aggregate_instance(n_table, sizes, seed=SEED, engine=None, dst=b"BLS_SIG
     sigs[inf != 0] = 0
     sigs[inf != 0, 12] = 1
     return sks, table, committees, msgs, sigs
+
+
+def bls_grouped_instance(sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
+    """n = sum(sizes) valid BLS signatures ORDERED BY MESSAGE over m = len(sizes) distinct messages, from the seed: group g holds sizes[g]
+    signatures of message g (a size may be 0: a message nobody signed), sig_i = [sk_i] H(m_g).  The messages are 4 to 67 bytes and
+    pairwise distinct (the group's number leads).  -> (sks (n, 4), pks (n, 12), msgs (list of m bytes), grp_off uint64 (m + 1,), sigs (n, 24))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    m, n = len(sizes), int(sum(sizes))
+    sks = scalars(seed ^ 0x6B15, n)
+    raw = splitmix64(seed ^ 0x65E5, 9 * m).reshape(m, 9) if m else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [int(g).to_bytes(4, "little") + raw[g, 1:].tobytes()[:int(raw[g, 0]) % 64] for g in range(m)]
+    grp_off = np.zeros(m + 1, dtype=np.uint64)
+    if m:
+        grp_off[1:] = np.cumsum(sizes, dtype=np.uint64)
+    if n == 0:
+        return sks, np.zeros((0, 12), dtype=np.uint64), msgs, grp_off, np.zeros((0, 24), dtype=np.uint64)
+    pks, _ = engine.g1_mul(G1_GENERATOR, sks)
+    h, _ = engine.hash_to_g2(msgs, dst)
+    sigs, _ = engine.g2_mul(np.repeat(h, np.asarray(sizes, dtype=np.int64), axis=0), sks)
+    return sks, pks, msgs, grp_off, sigs
