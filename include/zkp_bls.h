@@ -45,8 +45,8 @@
  * projective points, plus for the verifier 195 B per signature (the hashed point, its infinity byte, two status bytes) and the workspaces
  * of zkp_pairing_check_batch_rlc with k = 1, s1 = 1.
  *
- * Out of scope: hashing to G1 (the minimal-signature-size variants), DSTs over 255 bytes, ragged per-signature committees (they are
- * include/zkp_bls_agg.h), proof-of-possession management, more than one GPU.
+ * Out of scope: hashing to G1 (the minimal-signature-size variants: they are include/zkp_bls_minsig.h), DSTs over 255 bytes, ragged
+ * per-signature committees (they are include/zkp_bls_agg.h), proof-of-possession management, more than one GPU.
  */
 #ifndef ZKP_BLS_H
 #define ZKP_BLS_H

@@ -16,6 +16,7 @@ pub mod recover;
 pub mod bls;
 pub mod bls_agg;
 pub mod bls_grouped;
+pub mod bls_minsig;
 
 #[repr(C)]
 pub struct ZkpCtx {

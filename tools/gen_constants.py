@@ -199,6 +199,185 @@ def h2c_consts():
     return out, iso
 
 
+# ---------------------------------------------------------------------------------------------------- hash-to-G1 (RFC 9380, zkp_bls_minsig.hip)
+# E1': y^2 = x^3 + A x + B, 11-isogenous to E: y^2 = x^3 + 4.  The isogeny's 53 coefficients are DERIVED: the kernel is the one rational
+# subgroup of order 11, Velu's formulas give a map onto y^2 = x^3 + 4 * 11^6, and of the six scalings (x, y) -> (x / s^2, y / s^3) with
+# s^6 = 11^6 exactly one (s = 11) reproduces the RFC's vectors (tests/golden/h2c_g1_vectors.json).
+G1H_A = 0x00144698a3b8e9433d693a02c96d4982b0ea985383ee66a8d8e8981aefd881ac98936f8da0e0f97f5cf428082d584c1d
+G1H_B = 0x12e2908d11688030018b12e8753eee3b2016c1f0f24f4070a0b9c14fcef35ef55a23215a316ceaa5d1cc48e98e172be0
+G1H_Z = 11
+G1H_ORDER = (m.BLS_X + 1) ** 2 // 3 * m.R_ORDER         # #E(Fp) = #E1'(Fp): the curves are isogenous
+G1H_H_EFF = m.BLS_X + 1                                # 1 - x
+
+
+def _e1_add(p1, p2):
+    if p1 is None:
+        return p2
+    if p2 is None:
+        return p1
+    (x1, y1), (x2, y2) = p1, p2
+    if x1 == x2:
+        if (y1 + y2) % P == 0:
+            return None
+        lam = (3 * x1 * x1 + G1H_A) * m.fp_inv(2 * y1 % P) % P
+    else:
+        lam = (y2 - y1) * m.fp_inv((x2 - x1) % P) % P
+    x3 = (lam * lam - x1 - x2) % P
+    return (x3, (lam * (x1 - x3) - y1) % P)
+
+
+def _e1_mul(pt, k):
+    r = None
+    for bit in bin(k)[2:]:
+        r = _e1_add(r, r)
+        if bit == "1":
+            r = _e1_add(r, pt)
+    return r
+
+
+def _e1_rhs(x):
+    return (x * x * x + G1H_A * x + G1H_B) % P
+
+
+def g1h_kernel():
+    """T, 2 T, .., 5 T, T a generator of the rational 11-torsion of E1' (cyclic: 121 | #E1' but one subgroup of order 11 is rational)"""
+    assert G1H_ORDER % 121 == 0
+    x = 1
+    while True:
+        x += 1
+        y = m.fp_sqrt(_e1_rhs(x))
+        if y is None:
+            continue
+        assert _e1_mul((x, y), G1H_ORDER) is None                                       # E1' is isogenous to E
+        t = _e1_mul((x, y), G1H_ORDER // 121)
+        if t is None:
+            continue
+        while _e1_mul(t, 11) is not None:
+            t = _e1_mul(t, 11)
+        pts = [t]
+        for _ in range(4):
+            pts.append(_e1_add(pts[-1], t))
+        assert _e1_add(_e1_add(pts[4], t), pts[4]) is None and len({q[0] for q in pts}) == 5
+        return pts
+
+
+def _qmul(a, b):
+    out = [0] * (len(a) + len(b) - 1)
+    for i, x in enumerate(a):
+        for j, y in enumerate(b):
+            out[i + j] = (out[i + j] + x * y) % P
+    return out
+
+
+def _qadd(a, b):
+    n = max(len(a), len(b))
+    return [((a[i] if i < len(a) else 0) + (b[i] if i < len(b) else 0)) % P for i in range(n)]
+
+
+def _qeval(c, x):
+    acc = 0
+    for k in reversed(c):
+        acc = (acc * x + k) % P
+    return acc
+
+
+def g1h_velu():
+    """Velu's isogeny of that kernel as (x_num, x_den, y_num, y_den), coefficients of x^0, x^1, ..: X = x_num / x_den,
+    Y = y y_num / y_den with x_den = D^2, y_den = D^3, D = prod (x - x_Q); and the image curve's b"""
+    pts = g1h_kernel()
+    lin = [[(-q[0]) % P, 1] for q in pts]
+
+    def others(skip, power):
+        r = [1]
+        for j, f in enumerate(lin):
+            if j != skip:
+                for _ in range(power):
+                    r = _qmul(r, f)
+        return r
+    d = others(-1, 1)
+    d2, d3 = _qmul(d, d), _qmul(_qmul(d, d), d)
+    xn, yn = _qmul([0, 1], d2), d3
+    sv = sw = 0
+    for i, (xq, yq) in enumerate(pts):
+        v, u = 2 * (3 * xq * xq + G1H_A) % P, 4 * yq * yq % P
+        sv, sw = (sv + v) % P, (sw + u + xq * v) % P
+        xn = _qadd(xn, _qmul(_qadd([v * c % P for c in lin[i]], [u]), others(i, 2)))   # v / (x - xq) + u / (x - xq)^2
+        yn = _qadd(yn, [(-c) % P for c in _qmul(_qadd([v * c % P for c in lin[i]], [2 * u % P]), others(i, 3))])
+    assert (G1H_A - 5 * sv) % P == 0                                                    # the image curve has a = 0 ...
+    b_img = (G1H_B - 7 * sw) % P
+    assert b_img == 4 * 11 ** 6 == 0x6c20a4                                             # ... and b = 4 * 11^6
+    assert len(xn) == 12 and len(d2) == 11 and len(yn) == 16 and len(d3) == 16
+    return xn, d2, yn, d3
+
+
+def g1h_scalings():
+    g = 2
+    while pow(g, (P - 1) // 2, P) == 1 or pow(g, (P - 1) // 3, P) == 1:
+        g += 1
+    w = pow(g, (P - 1) // 6, P)                                                         # a primitive sixth root of unity
+    return [11 * pow(w, k, P) % P for k in range(6)]
+
+
+def g1h_point(msg, dst, iso):
+    """hash_to_curve of the suite with the rational map `iso`: hashlib, straight formulas, the group law of the model"""
+    import hashlib
+    dp = dst + bytes([len(dst)])
+    b0 = hashlib.sha256(bytes(64) + msg + (128).to_bytes(2, "big") + b"\x00" + dp).digest()
+    bs = [hashlib.sha256(b0 + b"\x01" + dp).digest()]
+    for i in range(2, 5):
+        bs.append(hashlib.sha256(bytes(x ^ y for x, y in zip(b0, bs[-1])) + bytes([i]) + dp).digest())
+    stream = b"".join(bs)
+    acc = None
+    for u in (int.from_bytes(stream[64 * i:64 * i + 64], "big") % P for i in range(2)):
+        zu2 = G1H_Z * u * u % P
+        tv1 = (zu2 * zu2 + zu2) % P
+        x = G1H_B * m.fp_inv(G1H_Z * G1H_A % P) % P if tv1 == 0 else (-G1H_B) * m.fp_inv(G1H_A) % P * (1 + m.fp_inv(tv1)) % P
+        y = m.fp_sqrt(_e1_rhs(x))
+        if y is None:
+            x = zu2 * x % P
+            y = m.fp_sqrt(_e1_rhs(x))
+        if (y & 1) != (u & 1):
+            y = P - y
+        xn, xd, yn, yd = iso
+        dx, dy = _qeval(xd, x), _qeval(yd, x)
+        if dx and dy:
+            acc = m.g1_add(acc, (_qeval(xn, x) * m.fp_inv(dx) % P, y * _qeval(yn, x) % P * m.fp_inv(dy) % P))
+    return m.g1_mul(acc, G1H_H_EFF) if acc is not None else None
+
+
+_G1H = None
+
+
+def g1h_consts():
+    """(name -> Fp constant of the hash-to-G1 kernels, the isogeny as four coefficient lists): of the six scalings exactly one gives the
+    suite's vectors"""
+    global _G1H
+    if _G1H is not None:
+        return _G1H
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "h2c_g1_vectors.json")) as f:
+        kat = json.load(f)
+    xn, xd, yn, yd = g1h_velu()
+    hit = []
+    for s in g1h_scalings():
+        i2 = m.fp_inv(s * s % P)
+        i3 = i2 * m.fp_inv(s) % P
+        iso = ([c * i2 % P for c in xn], xd, [c * i3 % P for c in yn], yd)
+        if all(g1h_point(v["msg"].encode(), kat["dst"].encode(), iso) == tuple(int(c, 16) for c in v["p"]) for v in kat["vectors"]):
+            hit.append((s, iso))
+    assert len(hit) == 1 and hit[0][0] == 11, "exactly one scaling reproduces the vectors: s = 11"
+    iso = hit[0][1]
+    out = {"G1SSWU_A": G1H_A, "G1SSWU_B": G1H_B, "G1SSWU_Z": G1H_Z}
+    c2 = m.fp_sqrt(P - G1H_Z)
+    assert c2 is not None                                                               # sqrt_ratio's c2 = sqrt(-Z)
+    out["G1SSWU_C2"] = c2
+    for nm, coeffs in zip(("XNUM", "XDEN", "YNUM", "YDEN"), iso):
+        for i, cf in enumerate(coeffs):
+            out["G1ISO_%s%d" % (nm, i)] = cf
+    _G1H = (out, iso)
+    return _G1H
+
+
 def balanced28(v):
     """14 signed limbs in [-2^27, 2^27) with sum l_i 2^(28 i) == v (v >= 0, v < 2^391)."""
     out = []
@@ -247,6 +426,12 @@ def emit28(c):
              "#define ZKP28_CONST_LIST(X) \\"]
     for i, (k, v) in enumerate(names):
         lines.append("  X(%s, %s)%s" % (k, ", ".join(str(x) for x in balanced28(v)), " \\" if i + 1 < len(names) else ""))
+    # hash-to-G1 (zkp_bls_minsig.hip): a list of its own, so that every line above stays as it was; the isogeny's 55 rows are in the order
+    # x_num (12), x_den (11), y_num (16), y_den (16), each from x^0 up
+    g1h = list(g1h_consts()[0].items())
+    lines += ["/* hash-to-G1: simplified SWU on E1' and the 11-isogeny to E, same form as above */", "#define ZKP28_G1H_CONST_LIST(X) \\"]
+    for i, (k, v) in enumerate(g1h):
+        lines.append("  X(%s, %s)%s" % (k, ", ".join(str(x) for x in balanced28(m28(v))), " \\" if i + 1 < len(g1h) else ""))
     with open(os.path.join(ROOT, "zkvm_pairings_amd", "csrc", "zkp_constants28.h"), "w") as f:
         f.write("\n".join(lines) + "\n")
 
@@ -302,6 +487,10 @@ def main():
         names.append(("M_" + k + "_1", mont(v[1])))
     for i, (k, v) in enumerate(names):
         lines.append("  X(%s, %s)%s" % (k, ", ".join("0x%08xu" % x for x in limbs(v, 32, 12)), " \\" if i + 1 < len(names) else ""))
+    g1h = list(g1h_consts()[0].items())                       # hash-to-G1, a list of its own below the first
+    lines.append("#define ZKP_G1H_CONST_LIST(X) \\")
+    for i, (k, v) in enumerate(g1h):
+        lines.append("  X(M_%s, %s)%s" % (k, ", ".join("0x%08xu" % x for x in limbs(mont(v), 32, 12)), " \\" if i + 1 < len(g1h) else ""))
     with open(os.path.join(ROOT, "zkvm_pairings_amd", "csrc", "zkp_constants.h"), "w") as f:
         f.write("\n".join(lines) + "\n")
     emit28(c)

@@ -1,6 +1,6 @@
 """MI355X-native batched BLS12-381 pairing engine behind the zkvm-pairings API shape.
 
-Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h, include/zkp_bls_agg.h and include/zkp_bls_grouped.h); it raises if
+Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h, include/zkp_bls_agg.h, include/zkp_bls_grouped.h and include/zkp_bls_minsig.h); it raises if
 the library has not been built.  There is no CPU fallback."""
 from . import _lib
 from ._lib import ZkpError
@@ -15,6 +15,8 @@ from .pairings import (R1CS, CellSetup, Fk20Setup, Fr, G1Affine, G2Affine, Groth
                        hash_to_g2, bls_sign_batch, bls_verify_batch, bls_verify_each, bls_verify_batch_compressed, bls_verify_each_compressed,
                        committee_entries, bls_aggregate_keys, bls_fast_aggregate_verify_batch, bls_fast_aggregate_verify_each,
                        group_by_message, bls_verify_grouped_batch, bls_fast_aggregate_verify_grouped_batch,
+                       hash_to_g1, bls_minsig_keygen_batch, bls_minsig_sign_batch, bls_minsig_verify_batch, bls_minsig_verify_samekey_batch, bls_minsig_verify_each,
+                       bls_minsig_verify_batch_compressed, bls_minsig_verify_each_compressed,
                        multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
@@ -25,4 +27,6 @@ __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "p
            "hash_to_g2", "bls_sign_batch", "bls_verify_batch", "bls_verify_each", "bls_verify_batch_compressed", "bls_verify_each_compressed",
            "committee_entries", "bls_aggregate_keys", "bls_fast_aggregate_verify_batch", "bls_fast_aggregate_verify_each",
            "group_by_message", "bls_verify_grouped_batch", "bls_fast_aggregate_verify_grouped_batch",
+           "hash_to_g1", "bls_minsig_keygen_batch", "bls_minsig_sign_batch", "bls_minsig_verify_batch", "bls_minsig_verify_samekey_batch", "bls_minsig_verify_each",
+           "bls_minsig_verify_batch_compressed", "bls_minsig_verify_each_compressed",
            "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

@@ -270,6 +270,22 @@ GRP_SIGNATURES = {
                                                                 c_int, c_vp, c_vp]),
 }
 
+# include/zkp_bls_minsig.h: hash-to-G1 and the minimal-signature-size BLS verifiers (signatures in G1, public keys in G2)
+BLS_MINSIG_SIGNATURES = {
+    "zkp_hash_to_field_g1_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    "zkp_hash_to_field_g1_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_map_from_fields_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_map_from_fields_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g1_clear_cofactor_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_g1_clear_cofactor_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_hash_to_g1_batch": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    "zkp_hash_to_g1_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_bls_minsig_verify_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_minsig_verify_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
+    "zkp_bls_minsig_verify_samekey_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_minsig_verify_samekey_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -298,7 +314,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
                                   list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items()) + list(AGG_SIGNATURES.items()) +
-                                  list(GRP_SIGNATURES.items())):
+                                  list(GRP_SIGNATURES.items()) + list(BLS_MINSIG_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -80,6 +80,11 @@ __device__ __forceinline__ bool f_is_zero(const Fp28& a) {
 }
 // r = take ? a : r, as v_cndmask_b32 on the ballot of `take` (uniform where it is used).  Written in asm so that the compiler cannot turn a
 // chain of these selects over the window table back into a dynamically indexed (scratch) array.
+#ifdef ZKP_FP28_HOST   // the host builds of the tests: the same select in plain C++
+__device__ __forceinline__ void f_select(Fp28& r, const Fp28& a, bool take) {
+    for (int i = 0; i < NL; i++) r.l[i] = take ? a.l[i] : r.l[i];
+}
+#else
 __device__ __forceinline__ void f_select(Fp28& r, const Fp28& a, bool take) {
     const uint64_t m = __builtin_amdgcn_ballot_w64(take);   // an SGPR pair: the lanes that take a
 #pragma unroll
@@ -89,6 +94,7 @@ __device__ __forceinline__ void f_select(Fp28& r, const Fp28& a, bool take) {
         r.l[i] = v;
     }
 }
+#endif
 __device__ __forceinline__ bool e_bit(int i) { return (KW_EXP[i >> 6] >> (i & 63)) & 1; }
 
 // r = a^((p-3)/4): left-to-right sliding window over the odd powers a^1 .. a^(2^WIN - 1).  The exponent and so the whole schedule

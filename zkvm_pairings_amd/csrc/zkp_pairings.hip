@@ -23,6 +23,7 @@
 #include "../../include/zkp_bls.h"
 #include "../../include/zkp_bls_agg.h"
 #include "../../include/zkp_bls_grouped.h"
+#include "../../include/zkp_bls_minsig.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -44,6 +45,7 @@
 #include "zkp_bls.hpp"
 #include "zkp_bls_agg.hpp"
 #include "zkp_bls_grouped.hpp"
+#include "zkp_bls_minsig.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -496,6 +498,8 @@ struct zkp_ctx {
     size_t agg_cap = 0;
     void* grp_ws = nullptr;     // grow-only workspace of the scaled segment sums and the grouped verifiers (zkp_bls_grouped_plan.hpp layout)
     size_t grp_cap = 0;
+    void* minsig_ws = nullptr;  // grow-only workspace of hash-to-G1 and the min-sig BLS verifiers (zkp_bls_minsig_plan.hpp layout)
+    size_t minsig_cap = 0;
     uint64_t* prod = nullptr;   // Fp12 records of the product tree (zkp_fp12_product / zkp_miller_product)
     size_t prod_cap = 0;
     // host-pointer pairing entry points on large batches: slices of host_slice pairs, two workspace slots, copies of
@@ -926,6 +930,7 @@ void zkp_free(zkp_ctx* c) {
     if (c->bls_ws) (void)hipFree(c->bls_ws);
     if (c->agg_ws) (void)hipFree(c->agg_ws);
     if (c->grp_ws) (void)hipFree(c->grp_ws);
+    if (c->minsig_ws) (void)hipFree(c->minsig_ws);
     if (c->g1ntt_split) (void)hipFree(c->g1ntt_split);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 6; j++)
@@ -1692,6 +1697,16 @@ int grow_grp(zkp_ctx* c, size_t bytes, void** ws) {
         c->grp_cap = bytes;
     }
     *ws = c->grp_ws;
+    return ZKP_OK;
+}
+int grow_minsig(zkp_ctx* c, size_t bytes, void** ws) {
+    if (bytes > c->minsig_cap) {
+        if (c->minsig_ws) { HIPCHK(c, hipFree(c->minsig_ws)); c->minsig_ws = nullptr; c->minsig_cap = 0; }
+        HIPCHK(c, hipMalloc(&c->minsig_ws, bytes));
+        zkp_dbg_alloc("ctx.minsig", c->minsig_ws, bytes);
+        c->minsig_cap = bytes;
+    }
+    *ws = c->minsig_ws;
     return ZKP_OK;
 }
 int grow_prod(zkp_ctx* c, size_t records) { return ensure_prod(c, records); }
@@ -3450,6 +3465,164 @@ int zkp_bls_fast_aggregate_verify_grouped_batch(zkp_ctx* c, const uint64_t* tabl
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_table * 2)) || (rc = validate_dev(c, (const uint64_t*)d[4], n * 4)) ||
         (rc = zkp::grp_fast_aggregate_verify_dev(c, d[0], n_table, d[1], n_idx, d[2], d[3], dm, dof, m, dd, dst_len, d[4], d[5], n, d[6], flags, c->d_flag + 1,
                                                  c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- hash-to-G1 and the min-sig BLS batch verifiers (zkp_bls_minsig.hip,
+// include/zkp_bls_minsig.h)
+extern "C" {
+
+int zkp_hash_to_field_g1_batch_dev(zkp_ctx* c, const void* msgs, const void* offsets, size_t n, const void* dst, size_t dst_len, void* out_u, void* stream) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && !out_u)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return zkp::g1h_field_dev(c, msgs, offsets, n, dst, dst_len, out_u, S(stream));
+}
+int zkp_hash_to_field_g1_batch(zkp_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, uint64_t* out_u) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && !out_u) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    void* dout = io.out(4, out_u, n * 96);
+    int rc;
+    if ((rc = io.status()) || (rc = zkp::g1h_field_dev(c, dm, dof, n, dd, dst_len, dout, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_g1_map_from_fields_batch_dev(zkp_ctx* c, const void* u, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!u || !out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, u, n * 2, S(stream))) return rc;
+    return zkp::g1h_map_dev(c, u, n, out, out_inf, S(stream));
+}
+int zkp_g1_map_from_fields_batch(zkp_ctx* c, const uint64_t* u, size_t n, uint64_t* out, uint8_t* out_inf) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!u || !out || !out_inf))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* du = io.in(0, u, n * 96);
+    void* dout = io.out(4, out, n * 96);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)du, n * 2)) || (rc = zkp::g1h_map_dev(c, du, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_g1_clear_cofactor_batch_dev(zkp_ctx* c, const void* pts, const void* inf, size_t n, void* out, void* out_inf, void* stream) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!pts || !out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, pts, n * 2, S(stream))) return rc;
+    return zkp::g1h_clear_dev(c, pts, inf, n, out, out_inf, S(stream));
+}
+int zkp_g1_clear_cofactor_batch(zkp_ctx* c, const uint64_t* pts, const uint8_t* inf, size_t n, uint64_t* out, uint8_t* out_inf) {
+    if (!c || n > zkp::bls::MAX_N || (n && (!pts || !out || !out_inf))) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const void* dp = io.in(0, pts, n * 96);
+    const void* di = io.in(2, inf, n);
+    void* dout = io.out(4, out, n * 96);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dp, n * 2)) || (rc = zkp::g1h_clear_dev(c, dp, di, n, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+int zkp_hash_to_g1_batch_dev(zkp_ctx* c, const void* msgs, const void* offsets, size_t n, const void* dst, size_t dst_len, void* out, void* out_inf,
+                             void* stream) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && (!out || !out_inf))) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    return zkp::g1h_hash_dev(c, msgs, offsets, n, dst, dst_len, out, out_inf, S(stream));
+}
+int zkp_hash_to_g1_batch(zkp_ctx* c, const uint8_t* msgs, const uint64_t* offsets, size_t n, const uint8_t* dst, size_t dst_len, uint64_t* out,
+                         uint8_t* out_inf) {
+    if (h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || (n && (!out || !out_inf)) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) return ZKP_OK;
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    void* dout = io.out(4, out, n * 96);
+    void* dinf = io.out(6, out_inf, n);
+    int rc;
+    if ((rc = io.status()) || (rc = zkp::g1h_hash_dev(c, dm, dof, n, dd, dst_len, dout, dinf, c->stream))) return rc;
+    return io.finish();
+}
+
+// k free pairs and s2 columns as the verifier hands them to the driver: (1, 1) for the general one, (0, 2) for the same-key one
+static bool minsig_args_bad(const zkp_ctx* c, const void* pk, const void* msgs, const void* offsets, const void* dst, size_t dst_len, const void* sig, size_t n,
+                            const void* rand, int flags, const void* all_ok, size_t k, size_t s2, bool pk_always) {
+    return h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || n > zkp::bls::MAX_VERIFY_N ||
+           zkp::rlc::args_bad(n, k, 0, s2) || ((n || pk_always) && !pk) || (n && (!sig || !rand));
+}
+int zkp_bls_minsig_verify_batch_dev(zkp_ctx* c, const void* pk, const void* inf_pk, const void* msgs, const void* offsets, const void* dst, size_t dst_len,
+                                    const void* sig, const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok, void* stream) {
+    if (minsig_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok, 1, 1, false)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, pk, n * 4, S(stream))) || (rc = validate_on_stream(c, sig, n * 2, S(stream)))) return rc;
+    return zkp::minsig_verify_dev(c, pk, inf_pk, msgs, offsets, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+// the arrays of points one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_minsig_verify_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* inf_pk, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst,
+                                size_t dst_len, const uint64_t* sig, const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags, int* all_ok) {
+    if (minsig_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok, 1, 1, false) || offsets_malformed(msgs, offsets, n)) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[5] = {pk, inf_pk, sig, inf_sig, rand};
+    const size_t bytes[5] = {n * 192, n, n * 96, n, n * 16};
+    size_t off[5], total = 0;
+    for (int i = 0; i < 5; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[5];
+    for (int i = 0; i < 5; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n * 4)) || (rc = validate_dev(c, (const uint64_t*)d[2], n * 2)) ||
+        (rc = zkp::minsig_verify_dev(c, d[0], d[1], dm, dof, dd, dst_len, d[2], d[3], n, d[4], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_minsig_verify_samekey_batch_dev(zkp_ctx* c, const void* pk, const void* msgs, const void* offsets, const void* dst, size_t dst_len, const void* sig,
+                                            const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok, void* stream) {
+    if (minsig_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok, 0, n ? 2 : 0, true)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, pk, 4, S(stream))) || (rc = validate_on_stream(c, sig, n * 2, S(stream)))) return rc;
+    return zkp::minsig_verify_samekey_dev(c, pk, msgs, offsets, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+int zkp_bls_minsig_verify_samekey_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len,
+                                        const uint64_t* sig, const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags, int* all_ok) {
+    if (minsig_args_bad(c, pk, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok, 0, n ? 2 : 0, true) || offsets_malformed(msgs, offsets, n))
+        return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[4] = {pk, sig, inf_sig, rand};
+    const size_t bytes[4] = {192, n * 96, n, n * 16};
+    size_t off[4], total = 0;
+    for (int i = 0; i < 4; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[4];
+    for (int i = 0; i < 4; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], 4)) || (rc = validate_dev(c, (const uint64_t*)d[1], n * 2)) ||
+        (rc = zkp::minsig_verify_samekey_dev(c, d[0], dm, dof, dd, dst_len, d[1], d[2], n, d[3], flags, c->d_flag + 1, c->stream)))
         return rc;
     return io.finish();
 }

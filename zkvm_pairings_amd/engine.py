@@ -1096,6 +1096,138 @@ class PairingEngine:
                                                  ctypes.byref(ok)))
         return bool(ok.value)
 
+    # ------------------------------------------------------------------ hash-to-G1 and min-sig BLS signatures (include/zkp_bls_minsig.h)
+    def hash_to_field_g1(self, msgs, dst, offsets=None):
+        """messages -> (u0, u1) of RFC 9380 hash_to_field for G1, (n, 12) words (zkp_hash_to_field_g1_batch); the arguments of
+        hash_to_field_g2"""
+        if _is_torch(offsets):
+            import torch
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            out = torch.empty((n, 12), dtype=torch.int64, device=offsets.device)
+            self._chk(self._lib.zkp_hash_to_field_g1_batch_dev(self._h, self._tp(msgs), self._tp(offsets), n, self._tp(dst), dst.numel(), self._tp(out),
+                                                               self._stream()))
+            return out
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        out = np.empty((n, 12), dtype=np.uint64)
+        self._chk(self._lib.zkp_hash_to_field_g1_batch(self._h, _ptr(buf), _ptr(off), n, _ptr(d), d.size, _ptr(out)))
+        return out
+
+    def g1_map_from_fields(self, u):
+        """u (n, 12): two Fp elements per point -> clear_cofactor(iso(sswu(u0)) + iso(sswu(u1))): (points (n, 12), inf (n,))"""
+        if _is_torch(u):
+            import torch
+            self._t_check(u, 12, "u")
+            n = u.numel() // 12
+            out, oi = torch.empty((n, 12), dtype=u.dtype, device=u.device), torch.empty(n, dtype=torch.uint8, device=u.device)
+            self._chk(self._lib.zkp_g1_map_from_fields_batch_dev(self._h, self._tp(u), n, self._tp(out), self._tp(oi), self._stream()))
+            return out, oi
+        u = _np(u, 12)
+        out, oi = np.empty((u.shape[0], 12), dtype=np.uint64), np.empty(u.shape[0], dtype=np.uint8)
+        self._chk(self._lib.zkp_g1_map_from_fields_batch(self._h, _ptr(u), u.shape[0], _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def g1_clear_cofactor(self, pts, inf=None):
+        """[1 - x] P for any points of E: y^2 = x^3 + 4 (zkp_g1_clear_cofactor_batch): (points (n, 12), inf (n,))"""
+        if _is_torch(pts):
+            import torch
+            self._t_check(pts, 12, "pts")
+            n = pts.numel() // 12
+            self._t_bytes(inf, n, "inf")
+            out, oi = torch.empty((n, 12), dtype=pts.dtype, device=pts.device), torch.empty(n, dtype=torch.uint8, device=pts.device)
+            self._chk(self._lib.zkp_g1_clear_cofactor_batch_dev(self._h, self._tp(pts), self._tp(inf), n, self._tp(out), self._tp(oi), self._stream()))
+            return out, oi
+        pts = _np(pts, 12)
+        n = pts.shape[0]
+        i = _flags(inf, n, "inf")
+        out, oi = np.empty((n, 12), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_g1_clear_cofactor_batch(self._h, _ptr(pts), _ptr(i), n, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def hash_to_g1(self, msgs, dst, offsets=None):
+        """messages -> points of G1 (RFC 9380 BLS12381G1_XMD:SHA-256_SSWU_RO_; zkp_hash_to_g1_batch): (points (n, 12), inf (n,)); the
+        arguments of hash_to_field_g2"""
+        if _is_torch(offsets):
+            import torch
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            out, oi = torch.empty((n, 12), dtype=torch.int64, device=offsets.device), torch.empty(n, dtype=torch.uint8, device=offsets.device)
+            self._chk(self._lib.zkp_hash_to_g1_batch_dev(self._h, self._tp(msgs), self._tp(offsets), n, self._tp(dst), dst.numel(), self._tp(out), self._tp(oi),
+                                                         self._stream()))
+            return out, oi
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        out, oi = np.empty((n, 12), dtype=np.uint64), np.empty(n, dtype=np.uint8)
+        self._chk(self._lib.zkp_hash_to_g1_batch(self._h, _ptr(buf), _ptr(off), n, _ptr(d), d.size, _ptr(out), _ptr(oi)))
+        return out, oi
+
+    def bls_minsig_verify(self, pk, msgs, sig, dst, offsets=None, inf_pk=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """n BLS signatures of the minimal-signature-size layout (public keys in G2 (n, 24), signatures in G1 (n, 12)) verified as ONE
+        pairing product (zkp_bls_minsig_verify_batch): True iff prod_i e([r_i] H(m_i), pk_i) e(sum_i [r_i] sig_i, -g2) == 1, every pk
+        and sig is valid (unless points_checked), no pk is the identity and no (a_i, b_i) of rand is zero.  The arguments and the
+        return value of bls_verify."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(pk):
+            import torch
+            self._t_check(pk, 24, "pk"), self._t_check(sig, 12, "sig")
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            if pk.numel() // 24 != n or sig.numel() // 12 != n:
+                raise ValueError("%d messages, %d public keys, %d signatures" % (n, pk.numel() // 24, sig.numel() // 12))
+            self._t_bytes(inf_pk, n, "inf_pk"), self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(pk.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=pk.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_minsig_verify_batch_dev(self._h, self._tp(pk), self._tp(inf_pk), self._tp(msgs), self._tp(offsets), self._tp(dst),
+                                                                dst.numel(), self._tp(sig), self._tp(inf_sig), n, self._tp(rand), flags, self._tp(all_ok),
+                                                                self._stream()))
+            return all_ok
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        pk, sig = _np(pk, 24), _np(sig, 12)
+        if pk.shape[0] != n or sig.shape[0] != n:
+            raise ValueError("%d messages, %d public keys, %d signatures" % (n, pk.shape[0], sig.shape[0]))
+        ip, isg = _flags(inf_pk, n, "inf_pk"), _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_minsig_verify_batch(self._h, _ptr(pk), _ptr(ip), _ptr(buf), _ptr(off), _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r),
+                                                        flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def bls_minsig_verify_samekey(self, pk, msgs, sig, dst, offsets=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """bls_minsig_verify when ONE key pk (24 words) signed every message (zkp_bls_minsig_verify_samekey_batch): two G1 sums, two
+        Miller loops.  The same answer as bls_minsig_verify with the key repeated and the same rand."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(pk):
+            import torch
+            self._t_check(pk, 24, "pk", rows=1), self._t_check(sig, 12, "sig")
+            msgs, offsets, n, dst = self._msgs_t(msgs, offsets, dst)
+            if sig.numel() // 12 != n:
+                raise ValueError("%d messages, %d signatures" % (n, sig.numel() // 12))
+            self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(pk.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=pk.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_minsig_verify_samekey_batch_dev(self._h, self._tp(pk), self._tp(msgs), self._tp(offsets), self._tp(dst), dst.numel(),
+                                                                        self._tp(sig), self._tp(inf_sig), n, self._tp(rand), flags, self._tp(all_ok),
+                                                                        self._stream()))
+            return all_ok
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        pk, sig = _np(pk, 24), _np(sig, 12)
+        if pk.shape[0] != 1 or sig.shape[0] != n:
+            raise ValueError("%d messages, %d public keys (one wanted), %d signatures" % (n, pk.shape[0], sig.shape[0]))
+        isg = _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_minsig_verify_samekey_batch(self._h, _ptr(pk), _ptr(buf), _ptr(off), _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r),
+                                                                flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
     # ------------------------------------------------------------------ committee aggregation (include/zkp_bls_agg.h)
     @staticmethod
     def _entries_np(idx, seg_off):

@@ -951,6 +951,100 @@ def bls_verify_each_compressed(pk_bytes, msgs, sig_bytes, dst, engine=None):
     return dec & bls_verify_each(pk, msgs, sg, dst, inf_pk=ipk, inf_sig=isg, engine=e)
 
 
+# ------------------------------------------------------------------------------------------------ min-sig BLS signatures (include/zkp_bls_minsig.h)
+QUICKNET_DST = b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_"
+
+
+def hash_to_g1(msgs, dst, engine=None):
+    """a list of messages (bytes) -> (points (n, 12), inf (n,)): RFC 9380 BLS12381G1_XMD:SHA-256_SSWU_RO_ under the tag dst"""
+    return (engine or default_engine()).hash_to_g1(msgs, dst)
+
+
+def bls_minsig_keygen_batch(sks, engine=None):
+    """pk_i = [sk_i] g2: secret keys (n, 4) words below r -> (public keys (n, 24), inf (n,))"""
+    e = engine or default_engine()
+    sks = np.ascontiguousarray(sks, dtype=np.uint64).reshape(-1, 4)
+    return e.g2_mul(G2Affine.generator().to_array(), sks)
+
+
+def bls_minsig_sign_batch(sks, msgs, dst, engine=None):
+    """sig_i = [sk_i] H(m_i) in G1: secret keys (n, 4) words below r, messages a list of bytes -> (signatures (n, 12), inf (n,))"""
+    e = engine or default_engine()
+    h, hinf = e.hash_to_g1(msgs, dst)
+    sks = np.ascontiguousarray(sks, dtype=np.uint64).reshape(-1, 4)
+    if sks.shape[0] != h.shape[0]:
+        raise ValueError("%d secret keys for %d messages" % (sks.shape[0], h.shape[0]))
+    if h.shape[0] == 0:
+        return h, hinf
+    sig, inf = e.g1_mul(h, sks)
+    inf = inf | hinf
+    sig[inf != 0] = 0
+    sig[inf != 0, 6] = 1
+    return sig, inf
+
+
+def bls_minsig_verify_batch(pks, msgs, sigs, dst, rand=None, points_checked=False, inf_pk=None, inf_sig=None, engine=None):
+    """True iff every signature verifies (one pairing product under a random linear combination, PairingEngine.bls_minsig_verify):
+    public keys (n, 24) in G2, messages a list of bytes, signatures (n, 12) in G1"""
+    return (engine or default_engine()).bls_minsig_verify(pks, msgs, sigs, dst, inf_pk=inf_pk, inf_sig=inf_sig, rand=rand, points_checked=points_checked)
+
+
+def bls_minsig_verify_samekey_batch(pk, msgs, sigs, dst, rand=None, points_checked=False, inf_sig=None, engine=None):
+    """bls_minsig_verify_batch when ONE public key pk (24 words) signed every message - a beacon chain: two G1 sums and two Miller loops
+    for the whole batch (PairingEngine.bls_minsig_verify_samekey)"""
+    return (engine or default_engine()).bls_minsig_verify_samekey(pk, msgs, sigs, dst, inf_sig=inf_sig, rand=rand, points_checked=points_checked)
+
+
+def bls_minsig_verify_each(pks, msgs, sigs, dst, points_checked=False, inf_pk=None, inf_sig=None, engine=None):
+    """bool array (n,): signature i verifies.  The per-signature path of bls_verify_each: pairing_check with k = 2 on (H(m_i), pk_i),
+    (sig_i, -g2), ANDed with is_valid of pk_i and sig_i (unless points_checked) and with pk_i not the identity."""
+    e = engine or default_engine()
+    pks = np.ascontiguousarray(pks, dtype=np.uint64).reshape(-1, 24)
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint64).reshape(-1, 12)
+    n = pks.shape[0]
+    if sigs.shape[0] != n or len(msgs) != n:
+        raise ValueError("%d messages, %d public keys, %d signatures" % (len(msgs), n, sigs.shape[0]))
+    ok = np.ones(n, dtype=bool)
+    if n == 0:
+        return ok
+    ip = np.zeros(n, dtype=np.uint8) if inf_pk is None else np.ascontiguousarray(inf_pk, dtype=np.uint8).reshape(n)
+    isg = np.zeros(n, dtype=np.uint8) if inf_sig is None else np.ascontiguousarray(inf_sig, dtype=np.uint8).reshape(n)
+    ok &= ip == 0
+    if not points_checked:
+        ok &= (e.g2_is_valid(pks, ip) == 0) & (e.g1_is_valid(sigs, isg) == 0)
+    h, hinf = e.hash_to_g1(msgs, dst)
+    g1 = np.empty((n, 2, 12), dtype=np.uint64)
+    g2 = np.empty((n, 2, 24), dtype=np.uint64)
+    g1[:, 0], g1[:, 1] = h, sigs
+    g2[:, 0], g2[:, 1] = pks, (-G2Affine.generator()).to_array()
+    i1, i2 = np.zeros((n, 2), dtype=np.uint8), np.zeros((n, 2), dtype=np.uint8)
+    i1[:, 0], i1[:, 1], i2[:, 0] = hinf, isg, ip
+    per, _ = e.pairing_check(g1.reshape(-1, 12), g2.reshape(-1, 24), 2, i1.reshape(-1), i2.reshape(-1))
+    return ok & (np.asarray(per).reshape(-1) != 0)
+
+
+def _bls_minsig_decompress(pk_bytes, sig_bytes, e):
+    pk, ipk, spk = e.decompress_points(pk_bytes, 2)
+    sg, isg, ssg = e.decompress_points(sig_bytes, 1)
+    return pk, ipk, sg, isg, (np.asarray(spk) == 0) & (np.asarray(ssg) == 0)
+
+
+def bls_minsig_verify_batch_compressed(pk_bytes, msgs, sig_bytes, dst, rand=None, engine=None):
+    """bls_minsig_verify_batch on 96-byte compressed public keys and 48-byte compressed signatures, decompressed on the GPU; a string
+    that does not decompress fails the batch"""
+    e = engine or default_engine()
+    pk, ipk, sg, isg, dec = _bls_minsig_decompress(pk_bytes, sig_bytes, e)
+    if not dec.all():
+        return False
+    return e.bls_minsig_verify(pk, msgs, sg, dst, inf_pk=ipk, inf_sig=isg, rand=rand)
+
+
+def bls_minsig_verify_each_compressed(pk_bytes, msgs, sig_bytes, dst, engine=None):
+    e = engine or default_engine()
+    pk, ipk, sg, isg, dec = _bls_minsig_decompress(pk_bytes, sig_bytes, e)
+    return dec & bls_minsig_verify_each(pk, msgs, sg, dst, inf_pk=ipk, inf_sig=isg, engine=e)
+
+
 # ------------------------------------------------------------------------------------------------ committee aggregation (include/zkp_bls_agg.h)
 SUBTRACT = 0x80000000   # bit 31 of an entry: subtract the table row
 

@@ -395,6 +395,26 @@ def bls_instance(n, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256
     return sks, pks, msgs, sigs
 
 
+def bls_minsig_instance(n, same_key=False, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_"):
+    """n valid BLS signatures of the minimal-signature-size layout from the seed: secret keys (ONE key repeated when same_key), messages
+    of 0 .. 63 bytes, public keys [sk] g2 and signatures [sk] H(m) in G1, the hash and both multiplications on the engine.
+    -> (sks (n, 4), pks (n, 24), msgs (list of bytes), sigs (n, 12))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    sks = scalars(seed ^ 0xB16, n)
+    if same_key and n:
+        sks[:] = sks[0]
+    raw = splitmix64(seed ^ 0x5E6, 9 * n).reshape(n, 9) if n else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [raw[i, 1:].tobytes()[:int(raw[i, 0]) % 64] for i in range(n)]
+    if n == 0:
+        return sks, np.zeros((0, 24), dtype=np.uint64), msgs, np.zeros((0, 12), dtype=np.uint64)
+    pks, _ = engine.g2_mul(G2_GENERATOR, sks)
+    h, _ = engine.hash_to_g1(msgs, dst)
+    sigs, _ = engine.g1_mul(h, sks)
+    return sks, pks, msgs, sigs
+
+
 def bls_aggregate_instance(n_table, sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
     """A table of n_table key pairs and one valid aggregate signature per committee size in `sizes`, from the seed: committee i draws
     sizes[i] rows (with repetition) and signs message i with the SUM of their secret keys, sig_i = [sum sk] H(m_i) - which is what the
