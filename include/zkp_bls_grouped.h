@@ -21,7 +21,8 @@
  *                                              the affine wire point, canonical, so bit-exact whatever the order of addition; the
  *                                              identity is (0, 1) with out_inf = 1.  An empty segment, an input at infinity (inf may be
  *                                              null) and a zero (a_i, b_i) give the identity and are no error; P and -P under one (a, b)
- *                                              cancel; status is 0 unless the call is malformed.
+ *                                              cancel; status is 0 unless the call is malformed.  For a point of the curve outside
+ *                                              G1 the summand is [a_i] P_i + [b_i] (beta x_i, -y_i), as in zkp_g1_mul_endo_batch.
  * zkp_bls_verify_grouped_batch                 *all_ok = what zkp_bls_verify_batch returns on the same signatures with message g repeated
  *                                              for each member of group g and the same rand: the two products are equal in Gt, so this
  *                                              holds for every input, forged ones included.  The same flag rules: is_valid on pk and sig

@@ -26,7 +26,11 @@ Hash-to-G2 and the BLS verifier (csrc/zkp_bls.hip; the last section) follow the 
 signatures, with the model of tests/h2c_model.py behind the expected bytes.  Two departures, both stated where they occur: the flags of
 hash_to_g2 are zero everywhere (no message hashes to the identity), so condition 3 holds for its points only; and the verifier returns
 one verdict, so conditions 2 and 3 are checked on the array its slices write, the hashed points, and the GPU test moves a forgery across
-the boundary instead."""
+the boundary instead.
+
+Hash-to-G1 and the min-sig verifiers (csrc/zkp_bls_minsig.hip) have the same five kinds of call with tests/h2g1_model.py behind them, and
+the grouped and the committee verifier (csrc/zkp_bls_grouped.hip, csrc/zkp_bls_agg.hip), which drive sliced callees on m messages or n
+aggregate keys, a call each above 2^17: the last two sections."""
 import random
 
 import numpy as np
@@ -386,3 +390,234 @@ def message_list(call, msgs=None):
     buf = (call.msgs if msgs is None else msgs).tobytes()
     off = call.offsets.tolist()
     return [buf[a:b] for a, b in zip(off[:-1], off[1:])]
+
+
+# ------------------------------------------------------------------------------------------------------------------- hash-to-G1 and the min-sig verifiers
+# csrc/zkp_bls_minsig.hip walks its messages, pairs of field elements and points in slices of minsig::SLICE = bls::SLICE, like the section
+# above, with tests/h2g1_model.py behind the expected bytes.  The shapes, the message lengths and the tails are those of the hash-to-G2
+# calls; the pools are others (other seeds, the other tag).  The cofactor call takes its points from h2g1_adversarial.point_cases(): points
+# of small order and two flagged identities make its output flags differ on both sides of every boundary.  The verifiers are judged on
+# the hashed G1 points, the array their slices write (the same-key verifier writes them into every second row of its columns).
+CLEAR_NAMES = ("order3_plus", "order3_minus", "identity", "order11", "g1_random", "g1_generator", "g1_negated", "order3_plus_g1",
+               "order11_plus_g1", "order33_plus_g1", "flagged_generator", "outside0", "outside1")
+CLEAR_FLAGGED_BODY, CLEAR_FLAGGED_TAIL = 2, 10                        # (0, 1) with its flag; the generator's words with the flag, which decides
+
+
+def minsig_field_pool():
+    def build():
+        import minsig_replay_cases as mrc
+        rng = random.Random(SEED * 17)
+        msgs = [bytes(rng.randrange(256) for _ in range(k)) for k in HASH_LENGTHS]
+        _distinct(msgs)
+        return dict(msgs=msgs, u=mrc.field_rows(msgs, mrc.DST))
+    return rc._cached(("slice-minsig-field-pool",), build)
+
+
+def minsig_field_call():
+    """hash_to_field_g1 on SLICE + 61 messages; Call.msgs / Call.offsets are the arguments"""
+    p = minsig_field_pool()
+    idx = draw_spread(SEED + 701, HASH_N, HASH_N - BLS_SLICE, HASH_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, HASH_BASE)
+    call = Call(HASH_N, BLS_SLICE, idx, dict(msg=(rows, 1)), dict(u=(p["u"][idx], 1)), p)
+    call.msgs, call.offsets, call.constant = buf, off, set()
+    return call
+
+
+def minsig_map_pool():
+    def build():
+        import h2g1_model as g
+        import minsig_replay_cases as mrc
+        rng = random.Random(SEED * 19)
+        us = [(rng.randrange(1, g.P), rng.randrange(1, g.P)) for _ in range(BLS_B)]
+        for j in (MAP_INF, MAP_INF_BODY):
+            us[j] = (us[j][0], g.P - us[j][0])
+        _distinct(us)
+        pts = [g.map_from_fields(a, b) for a, b in us]
+        points, inf = mrc.point_rows(pts)
+        return dict(us=us, pts=pts, u=mrc.u64([g.fp_words(a) + g.fp_words(b) for a, b in us]).reshape(-1, 12), points=points, inf=inf)
+    return rc._cached(("slice-minsig-map-pool",), build)
+
+
+def minsig_map_call():
+    p = minsig_map_pool()
+    idx = draw(SEED + 711, MAP_N, MAP_TAIL, BLS_B)
+    call = Call(MAP_N, BLS_SLICE, idx, dict(u=(p["u"][idx], 1)), dict(points=(p["points"][idx], 1), inf=(p["inf"][idx], 1)), p)
+    call.constant = set()
+    return call
+
+
+def minsig_clear_pool():
+    def build():
+        import h2g1_adversarial as ha
+        import h2g1_model as g
+        import minsig_replay_cases as mrc
+        by = dict(ha.point_cases())
+        by["flagged_generator"] = None
+        pts = [by[k] for k in CLEAR_NAMES]
+        rows, flags = mrc.point_rows(pts)
+        rows[CLEAR_FLAGGED_TAIL] = mrc.u64(g.g1_words(g.m.G1_GEN)[0])
+        assert flags.tolist() == [int(j in (CLEAR_FLAGGED_BODY, CLEAR_FLAGGED_TAIL)) for j in range(BLS_B)]
+        _distinct([r.tolist() + [f] for r, f in zip(rows, flags)])
+        outs = [g.clear_cofactor(q) for q in pts]
+        points, inf = mrc.point_rows(outs)
+        return dict(names=CLEAR_NAMES, pts=pts, outs=outs, pts_rows=rows, pts_inf=flags, points=points, inf=inf)
+    return rc._cached(("slice-minsig-clear-pool",), build)
+
+
+def minsig_clear_call():
+    p = minsig_clear_pool()
+    idx = draw(SEED + 723, MAP_N, MAP_TAIL, BLS_B)
+    call = Call(MAP_N, BLS_SLICE, idx, dict(pts=(p["pts_rows"][idx], 1), inf=(p["pts_inf"][idx], 1)), dict(points=(p["points"][idx], 1), inf=(p["inf"][idx], 1)), p)
+    call.constant = set()
+    return call
+
+
+def minsig_verify_pool(same_key):
+    """BLS_B messages signed by g.sign: by BLS_B keys, or all by one"""
+    def build():
+        import h2c_model as h
+        import h2g1_model as g
+        import minsig_replay_cases as mrc
+        rng = random.Random(SEED * 29 + same_key)
+        one = rng.randrange(1, g.R_ORDER)
+        pool = []
+        for _ in range(BLS_B):
+            sk = one if same_key else rng.randrange(1, g.R_ORDER)
+            msg = bytes(rng.randrange(256) for _ in range(rng.randrange(1, 48)))
+            pool.append((sk, g.sk_to_pk(sk), msg, g.sign(sk, msg, mrc.DST)))
+        msgs = [x[2] for x in pool]
+        _distinct(msgs)
+        hp, hinf = mrc.point_rows([mrc.hashed(x, mrc.DST) for x in msgs])
+        assert not hinf.any()
+        return dict(pool=pool, msgs=msgs, pk=mrc.u64([h.g2_words(x[1])[0] for x in pool]).reshape(-1, 24),
+                    sig=mrc.u64([g.g1_words(x[3])[0] for x in pool]).reshape(-1, 12), hp=hp)
+    return rc._cached(("slice-minsig-verify-pool", same_key), build)
+
+
+def minsig_verify_call(same_key):
+    """bls_minsig_verify or bls_minsig_verify_samekey on SLICE + 6 valid signatures, judged on the hashed points as verify_call is.  For the
+    same-key call Call.pk1 is the one key; its input pk repeats it and is constant"""
+    p = minsig_verify_pool(same_key)
+    idx = draw(SEED + 731 + same_key, VERIFY_N, VERIFY_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, VERIFY_BASE)
+    rand = np.random.RandomState(SEED + 741 + same_key).randint(1, 1 << 62, size=(VERIFY_N, 2)).astype(np.uint64)
+    inputs = dict(sig=(p["sig"][idx], 1), msg=(rows, 1), rand=(rand, 1))
+    if not same_key:
+        inputs["pk"] = (p["pk"][idx], 1)
+    call = Call(VERIFY_N, BLS_SLICE, idx, inputs, dict(hp=(p["hp"][idx], 1)), p)
+    call.msgs, call.offsets, call.constant = buf, off, set()
+    call.pk1 = np.ascontiguousarray(p["pk"][:1])
+    call.forged = (BLS_SLICE - 1, BLS_SLICE, VERIFY_N - 1)
+    call.shifted = BLS_SLICE + 2                                     # the signature a test moves out of G1: its status byte lies behind the boundary
+    call.flagged_pk = BLS_SLICE + 1
+    return call
+
+
+def shifted_signature(call, j):
+    """the signatures with number j moved by (0, 2), a point of order 3: on the curve, outside G1, and the pairing equation still holds"""
+    import h2g1_model as g
+    import minsig_replay_cases as mrc
+    sig = call.arg("sig").copy()
+    moved = g.e_add(call.pool["pool"][call.idx[j]][3], (0, 2))
+    sig[j] = mrc.u64(g.g1_words(moved)[0])
+    return sig, moved
+
+
+# ------------------------------------------------------------------------------------------------------------------- the grouped and the committee verifiers
+# csrc/zkp_bls_grouped.hip and csrc/zkp_bls_agg.hip do not slice themselves; they drive sliced callees on workspace arrays: the hash on m
+# messages, bls_verify on the n aggregate keys, the Miller product over m pairs.  Their calls are judged on what those callees write.
+GROUPED_M = BLS_SLICE + 6
+GROUPED_SIZES = {5: 0, 6: 2, BLS_SLICE - 2: 0, BLS_SLICE: 3}          # every other group holds one signature: n = m + 1
+COM_N = BLS_SLICE + 6
+COM_TABLE = 36
+COM_SIZES = (1, 2, 3, 4, 5, 7, 33, 2, 1, 3, 5, 4, 7)                  # 33: a run border (32 records) inside a committee, in the body
+COM_WIDTH = max(COM_SIZES)
+
+
+def grouped_call():
+    """bls_verify_grouped on m = SLICE + 6 messages: group g holds the key and the signature of pool item idx[g] of verify_pool(), once,
+    but for the groups of GROUPED_SIZES, which hold it 0, 2, 0 and 3 times.  Call.n is m, the count its sliced callee walks; Call.pk,
+    Call.sig, Call.rand and Call.grp_off are the arguments per signature, Call.member the group of every signature"""
+    p = verify_pool()
+    m = GROUPED_M
+    idx = draw(SEED + 801, m, VERIFY_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, VERIFY_BASE)
+    sizes = np.ones(m, dtype=np.int64)
+    for g, k in GROUPED_SIZES.items():
+        sizes[g] = k
+    grp_off = np.zeros(m + 1, dtype=np.uint64)
+    grp_off[1:] = np.cumsum(sizes).astype(np.uint64)
+    member = np.repeat(np.arange(m, dtype=np.int64), sizes)
+    rand = np.random.RandomState(SEED + 802).randint(1, 1 << 62, size=(member.size, 2)).astype(np.uint64)
+    call = Call(m, BLS_SLICE, idx, dict(msg=(rows, 1), pk=(p["pk"][idx], 1), sig=(p["sig"][idx], 1)), dict(hq=(p["hq"][idx], 1)), p)
+    call.msgs, call.offsets, call.constant = buf, off, set()
+    call.sizes, call.grp_off, call.member, call.rand = sizes, grp_off, member, rand
+    call.pk, call.sig = np.ascontiguousarray(p["pk"][idx[member]]), np.ascontiguousarray(p["sig"][idx[member]])
+    call.forged = (BLS_SLICE - 1, BLS_SLICE + 1, m - 1)
+    call.moved = BLS_SLICE + 1                                       # grp_off[moved] + 1: the signature of this group is filed under the group before it
+    return call
+
+
+def expanded_messages(call, msgs=None):
+    """(buffer, offsets) of the grouped call's messages, one per signature: what bls_verify takes"""
+    import bls_replay_cases as brc
+    lst = message_list(call, msgs)
+    return brc.pack([lst[g] for g in call.member.tolist()], VERIFY_BASE)
+
+
+def committees_pool():
+    def build():
+        import agg_model as am
+        sks, pks = am.key_table(COM_TABLE)
+        vp = verify_pool()
+        rng = random.Random(SEED * 31)
+        entries, sums, sigs = [], [], []
+        for j, k in enumerate(COM_SIZES):
+            rows = rng.sample(range(COM_TABLE), k)
+            neg = [k > 1 and i > 0 and rng.randrange(4) == 0 for i in range(k)]
+            sk = sum(-sks[r] if s else sks[r] for r, s in zip(rows, neg)) % am.h.R_ORDER
+            assert sk
+            entries.append([r | am.SIGN if s else r for r, s in zip(rows, neg)])
+            sums.append(sk)
+            sigs.append(am.sign(vp["msgs"][j], sk))
+        _distinct(entries)
+        flat, seg_off = am.committee_entries(entries)
+        apk, apk_inf, status = am.sum_rows(pks, flat, seg_off)
+        assert not apk_inf.any() and not status.any()
+        padded = np.zeros((BLS_B, COM_WIDTH + 1), dtype=np.uint32)
+        for j, e in enumerate(entries):
+            padded[j, :len(e)], padded[j, COM_WIDTH] = e, len(e)
+        return dict(entries=entries, sks=sums, table=am.table_rows(pks), padded=padded, apk=apk, msgs=vp["msgs"], hq=vp["hq"],
+                    sig=am.u64([am.h.g2_words(s)[0] for s in sigs]).reshape(-1, 24))
+    return rc._cached(("slice-committees-pool",), build)
+
+
+def committees_call():
+    """bls_fast_aggregate_verify on SLICE + 6 committees over a table of 36 keys: committee j of the call is pool committee idx[j] and signs
+    pool message idx[j].  Call.entries / Call.seg_off are the committee arguments; the input `com` is their fixed-width form (the entries
+    zero-padded, the size in the last column), on which the slice conditions are checked"""
+    p = committees_pool()
+    idx = draw(SEED + 901, COM_N, VERIFY_TAIL, BLS_B)
+    buf, off, rows = pack_from_pool(p["msgs"], idx, VERIFY_BASE)
+    com = p["padded"][idx]
+    sizes = com[:, COM_WIDTH].astype(np.uint64)
+    seg_off = np.zeros(COM_N + 1, dtype=np.uint64)
+    seg_off[1:] = np.cumsum(sizes, dtype=np.uint64)
+    keep = np.arange(COM_WIDTH, dtype=np.uint64)[None, :] < sizes[:, None]
+    rand = np.random.RandomState(SEED + 902).randint(1, 1 << 62, size=(COM_N, 2)).astype(np.uint64)
+    call = Call(COM_N, BLS_SLICE, idx, dict(com=(com, 1), msg=(rows, 1), sig=(p["sig"][idx], 1), rand=(rand, 1)),
+                dict(apk=(p["apk"][idx], 1), hq=(p["hq"][idx], 1)), p)
+    call.msgs, call.offsets, call.constant = buf, off, set()
+    call.entries, call.seg_off = np.ascontiguousarray(com[:, :COM_WIDTH][keep]), seg_off
+    call.forged = (BLS_SLICE - 1, BLS_SLICE, COM_N - 1)
+    return call
+
+
+def swapped_member(call, j):
+    """the entries with the first member of committee j replaced by the lowest table row that the committee does not hold"""
+    import agg_model as am
+    held = {e & am.ROW for e in call.pool["entries"][call.idx[j]]}
+    other = min(r for r in range(COM_TABLE) if r not in held)
+    entries = call.entries.copy()
+    entries[int(call.seg_off[j])] = other
+    return entries, other

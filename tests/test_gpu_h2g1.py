@@ -131,6 +131,79 @@ def test_clear_cofactor_on_small_orders_the_identity_and_points_outside_g1(eng):
     assert none[keep].tobytes() == pts[keep].tobytes()
 
 
+def border_lanes(n, last):
+    """where k_g1h_affine's shared inversion (one per wavefront of 64, prefix and suffix products through LDS) meets identities: lanes 0, 63
+    and 64, where they exist; point n - 1, which every dead lane of a short wavefront reads again, when `last`; and at n = 130 the whole
+    first wavefront, whose shared product is then 1, beside a live second one"""
+    lanes = {j for j in (0, 63, 64) if j < n} | (set(range(64)) if n == 130 else set())
+    lanes.discard(n - 1)
+    if last:
+        lanes.add(n - 1)
+    return sorted(lanes)
+
+
+BORDER_SIZES = [1, 64, 65, 127, 130]
+
+
+@pytest.mark.parametrize("n", BORDER_SIZES)
+def test_clear_cofactor_identities_at_the_borders_of_the_shared_inversion(eng, n):
+    """a zero Z let into the product of a wavefront would zero its 63 neighbours: identities of all three kinds in turn - a flagged one,
+    (0, +-2) of order 3, the point of order 11 - at the borders, every other row a point with a finite image"""
+    by = dict(ha.point_cases())
+    kinds = [by[k] for k in ("identity", "order3_plus", "order11", "order3_minus")]
+    finite = [(k, q) for k, q in ha.point_cases() if _clear(q) is not None]
+    assert len(finite) == 12 and all(_clear(q) is None for q in kinds)
+    for last in ((True, False) if n in (65, 127) else (True,)):
+        lanes = border_lanes(n, last)
+        assert (n - 1 in lanes) == last and (n < 130 or lanes[:64] == list(range(64)))
+        pts = [finite[(5 * j + n) % len(finite)][1] for j in range(n)]
+        for k, j in enumerate(lanes):
+            pts[j] = kinds[(k + n + last) % len(kinds)]
+        pin, iin = wire(pts)
+        got, inf = both(eng, "g1_clear_cofactor", (pin,), inf=iin)
+        want, winf = wire([_clear(q) for q in pts])
+        assert np.nonzero(winf)[0].tolist() == lanes
+        for j in range(n):
+            assert got[j].tobytes() == want[j].tobytes() and inf[j] == winf[j], (n, last, j)
+        live = inf == 0
+        assert not ((got[:, :6] == 0).all(axis=1) & (got[:, 6:] == 0).all(axis=1))[live].any()
+        assert not np.asarray(eng.g1_is_valid(got, inf))[live].any()
+
+
+_CLEARED = {}
+_MAPPED = {}
+
+
+def _clear(q):
+    if q not in _CLEARED:
+        _CLEARED[q] = g.clear_cofactor(q)
+    return _CLEARED[q]
+
+
+@pytest.mark.parametrize("n", [65, 130])
+def test_map_from_fields_cancelling_pairs_at_the_borders_of_the_shared_inversion(eng, n):
+    """the same placement through the map: (u, -u) gives Q + (-Q), the identity out of k_g1h_clear<false>'s sum, at lanes 0, 63, 64 and
+    n - 1, at 130 in every lane of the first wavefront"""
+    rng = random.Random(0xB0)
+    us = [(rng.randrange(1, P), rng.randrange(1, P)) for _ in range(4)]
+    lanes = border_lanes(n, True)
+    pairs = [us[(3 * j + n) % len(us)] for j in range(n)]
+    for j in lanes:
+        pairs[j] = (pairs[j][0], P - pairs[j][0])
+    u = np.array([g.fp_words(a) + g.fp_words(b) for a, b in pairs], dtype=np.uint64)
+    got, inf = both(eng, "g1_map_from_fields", (u,))
+    for a, b in pairs:
+        if (a, b) not in _MAPPED:
+            _MAPPED[(a, b)] = g.map_from_fields(a, b)
+    want, winf = wire([_MAPPED[x] for x in pairs])
+    assert np.nonzero(winf)[0].tolist() == lanes
+    for j in range(n):
+        assert got[j].tobytes() == want[j].tobytes() and inf[j] == winf[j], (n, j)
+    live = inf == 0
+    assert not ((got[:, :6] == 0).all(axis=1) & (got[:, 6:] == 0).all(axis=1))[live].any()
+    assert not np.asarray(eng.g1_is_valid(got, inf))[live].any()
+
+
 def test_one_call_over_the_slice_boundary(eng):
     """2^17 + 61 messages from a pool of 64, a first offset that is not zero: every row equals the model's point of its message"""
     import torch

@@ -138,6 +138,115 @@ def test_identities_at_the_borders_of_the_shared_inversion(eng, table):
     assert [j for j in range(65) if oi[j]] == [0, 63, 64] and not st.any()
 
 
+# ------------------------------------------------------------------------------------------------------------------- k_grp_scale on what k_g1_mul_endo28 is tested on
+M64 = (1 << 64) - 1
+EDGE_PAIRS = [(1, 0), (0, 1), (M64, 0), (0, M64), (M64, M64), (1, 1), (M64, 1), (1, M64), (1 << 63, 1 << 63), (1 << 63, 0), (0, 0)]
+
+
+def _same_rows(got, want, what):
+    for g, w, name in zip(got, want, ("out", "out_inf", "status")):
+        g = g.cpu().numpy() if hasattr(g, "cpu") else np.asarray(g)
+        assert g.tobytes() == w.tobytes(), "%s: %s differs, first at row %r" % (what, name, np.nonzero((g.view(np.uint8).reshape(len(w), -1) != w.view(np.uint8).reshape(len(w), -1)).any(axis=1))[0][:1].tolist())
+
+
+@pytest.mark.parametrize("flagged", [(), (0, 63)], ids=["no-flags", "flags-at-0-and-63"])
+def test_one_entry_segments_on_the_edge_scalars_equal_the_model_and_g1_mul_endo(eng, table, flagged):
+    """70 segments of one entry, a full wavefront of k_grp_scale and a short one: the scalars (a, b) with a or b 0, 1, 2^63 or 2^64 - 1, then
+    seeded pairs.  out is the model's [a + b z^2] P and, row for row, what zkp_g1_mul_endo_batch gives; an input flagged at lane 0 or 63 is
+    the identity"""
+    n = 70
+    rng = random.Random(70)
+    picks = [rng.randrange(N_KEYS) for _ in range(n)]
+    logs, pts, inf = _inputs(table, picks)
+    rand = gm.rand_rows(n, 9)
+    rand[:len(EDGE_PAIRS)] = np.array(EDGE_PAIRS, dtype=np.uint64)
+    if 63 in flagged:
+        rand[63] = (M64, M64)
+    for j in flagged:
+        logs[j], inf[j] = None, 1                                    # the words stay those of the table row: the flag decides
+    _, oi, st = want = check(eng, logs, pts, inf if flagged else None, rand, list(range(n + 1)))
+    assert np.nonzero(oi)[0].tolist() == sorted(set(flagged) | {EDGE_PAIRS.index((0, 0))}) and not st.any()
+    endo, ei = eng.g1_mul_endo(pts, rand, inf if flagged else None)
+    assert endo.tobytes() == want[0].tobytes() and ei.tobytes() == want[1].tobytes(), "g1_mul_endo"
+
+
+def _outside_points():
+    """points of E(Fp) outside G1: (0, +-2) of order 3, where phi'(P) = (beta x, -y) = -P and the table entry P + phi'(P) is the identity;
+    a point of order 11; the fixture's points of small order and random points of the curve"""
+    import h2g1_adversarial as ha
+    import h2g1_model as g
+    import outside_groups as og
+    pts = [(0, 2), (0, g.P - 2), dict(ha.point_cases())["order11"]] + [q for q in og.g1_points().values() if g.e_on_curve(q)]
+    out = []
+    for q in pts:
+        if q not in out:
+            out.append(q)
+    assert len(out) >= 6 and all(g.e_on_curve(q) and not g.in_g1(q) for q in out)
+    return out
+
+
+def _endo_value(q, a, b):
+    """[a] P + [b] (beta x, -y) on all of E(Fp): what k_grp_scale's joint double-and-add computes whether or not P lies in G1"""
+    import bls12_381_model as m
+    import h2g1_model as g
+    return g.e_add(g.e_mul(q, a), g.e_mul((q[0] * m.BETA % g.P, (-q[1]) % g.P), b))
+
+
+def test_points_outside_g1_give_a_p_plus_b_phi_p_alone_and_three_to_a_segment(eng):
+    import h2g1_model as g
+    rng = random.Random(0xE0D3)
+    rows, pairs = [], []
+    for q in _outside_points():
+        for a, b in [(1, 0), (0, 1), (1, 1), (M64, M64), (3, 5), (rng.getrandbits(64), rng.getrandbits(64))]:
+            rows.append(q), pairs.append((a, b))
+    n = len(rows)
+    assert n % 3 == 0 and (rows[2], pairs[2]) == ((0, 2), (1, 1))
+    pts = am.g1_rows(rows)[0]
+    rand = np.array(pairs, dtype=np.uint64)
+    vals = [_endo_value(q, a, b) for q, (a, b) in zip(rows, pairs)]
+    assert vals[2] is None and vals[0] == (0, 2) and vals[1] == (0, g.P - 2)                    # T = P + phi'(P) is the identity; phi'(P) = -P
+    singles = list(range(n + 1))
+    want = am.g1_rows(vals) + (np.zeros(n, dtype=np.uint8),)
+    _same_rows(run_dev(eng, pts, None, rand, singles), want, "_dev flavour, one entry per segment")
+    _same_rows(eng.g1_scaled_segment_sum(pts, rand, gm.off_array(singles)), want, "host flavour, one entry per segment")
+    endo, ei = eng.g1_mul_endo(pts, rand)
+    assert endo.tobytes() == want[0].tobytes() and ei.tobytes() == want[1].tobytes(), "g1_mul_endo"
+    triples = list(range(0, n + 1, 3))
+    sums = [g.e_add(g.e_add(vals[i], vals[i + 1]), vals[i + 2]) for i in range(0, n, 3)]
+    want = am.g1_rows(sums) + (np.zeros(n // 3, dtype=np.uint8),)
+    assert sums[0] is None                                                                       # P + phi'(P) + the identity
+    assert vals[3] is None and vals[4] == (0, 2)                                                 # [M64] (P - P); 3 P - 5 P = -2 P = P for a point of order 3
+    _same_rows(run_dev(eng, pts, None, rand, triples), want, "_dev flavour, three entries per segment")
+
+
+def test_equal_and_opposite_sums_that_meet_in_different_jacobian_representations(eng, table):
+    """P1 = [s] g1 under (1, 0) and P2 = g1 under (a, b) with s = a + b z^2 are one point with two Z: [P1, P2] is the doubling branch of
+    jac_add met by cross-multiplication, [-P1, P2] the cancellation, [P1, P2, Q] a chain after the doubling.  Once inside a run of 32
+    records (level 0) and once across a run border, where the two meet as partial sums of the next level"""
+    rng = random.Random(0x2A)
+    n = 98
+    picks = [rng.randrange(N_KEYS) for _ in range(n)]
+    logs, pts, _ = _inputs(table, picks)
+    rand = gm.rand_rows(n, 12)
+    lens = [2, 2, 3, 24, 2, 30, 2, 30, 3]                            # the segments between the sites are whole ones of table rows
+    off = _off(lens)
+    sites = {0: False, 2: True, 4: False, 31: False, 63: True, 95: False}                      # where P1 stands; True: -P1
+    assert off[-1] == n and set(sites) <= set(off) and all((at + 1) % 32 == 0 for at in (31, 63, 95))    # there P1 ends a run, P2 opens the next
+    for at, neg in sites.items():
+        a, b = (int(v) for v in gm.rand_rows(1, 100 + at)[0])
+        s = gm.scalar(a, b)
+        logs[at], logs[at + 1] = (gm.R - s if neg else s), 1
+        rand[at], rand[at + 1] = (1, 0), (a, b)
+        pts[at:at + 2] = gm.point_rows(logs[at:at + 2])[0]
+    want = check(eng, logs, pts, None, rand, off)
+    oi = want[1]
+    assert [off[g] for g in np.nonzero(oi)[0]] == [2, 63] and not want[2].any()
+    for start in (0, 31):                                                                        # [2 s] g1, stated from the scalar
+        seg = off.index(start)
+        a, b = gm.rand_pairs(rand)[start + 1]
+        assert want[0][seg].tobytes() == am.g1_rows([am.public_key(2 * gm.scalar(a, b))])[0][0].tobytes()
+
+
 MALFORMED = {"decreasing": [0, 5, 4, 45], "first-not-zero": [1, 5, 9, 45], "last-beyond": [0, 5, 9, 46], "last-below": [0, 5, 9, 44]}
 
 

@@ -1,5 +1,6 @@
 """The slice loops of the G1 NTT, FK20 (csrc/zkp_fk20.hip), the KZG opening (csrc/zkp_poly.hip) and of hash-to-G2 and the BLS verifier
-(csrc/zkp_bls.hip) on one MI355X (run with -m gpu): every
+(csrc/zkp_bls.hip), of hash-to-G1 and the min-sig verifiers (csrc/zkp_bls_minsig.hip), and the grouped and the committee verifier above
+2^17 messages or committees, on one MI355X (run with -m gpu): every
 call here is the smallest that crosses a slice boundary of its entry point and ends in a short last slice, its inputs and expected bytes
 are assembled from a small pool by a pseudo-random index sequence (tests/slice_pools.py), and tests/test_slices_cpu.py has shown without
 a GPU that a slice which took offset 0, the previous slice's offset, or another slice's rows in ANY operand cannot give these bytes.
@@ -175,3 +176,182 @@ def test_bls_verify_one_forgery_on_either_side_of_the_boundary(eng, where):
     assert _verify(eng, call, bad, True) is False
     each = z.bls_verify_each(call.arg("pk"), sp.message_list(call, bad), call.arg("sig"), h.ETH_DST, engine=eng)
     assert np.nonzero(~each)[0].tolist() == [j]
+
+
+# ------------------------------------------------------------------------------------------------------------------- hash-to-G1 and the min-sig verifiers
+def _minsig_dst():
+    import h2g1_model as g
+    return g.QUICKNET_DST
+
+
+def test_hash_to_field_g1_two_slices_of_mixed_length_messages(eng):
+    """2^17 + 61 messages behind a non-zero offsets[0]: g1h_field_dev's output pointer and k_g1h_field's message index in the second slice"""
+    call = sp.minsig_field_call()
+    got = eng.hash_to_field_g1(call.msgs, _minsig_dst(), offsets=call.offsets)
+    same(call, dict(u=got), "hash_to_field_g1 (host)")
+    got = eng.hash_to_field_g1(to_dev(call.msgs), _minsig_dst(), offsets=to_dev(call.offsets))
+    same(call, dict(u=got), "hash_to_field_g1 (dev)")
+
+
+def test_g1_map_three_slices_with_an_identity_in_the_tail(eng):
+    """2 * 2^17 + 5 pairs of field elements: g1h_map_dev's input and output pointers in the second and third slice; (a, -a) in the tail"""
+    call = sp.minsig_map_call()
+    assert call.want("inf")[call.n - call.tail:].any()
+    pts, inf = eng.g1_map_from_fields(call.arg("u"))
+    same(call, dict(points=pts, inf=inf), "g1_map_from_fields (host)")
+    pts, inf = eng.g1_map_from_fields(to_dev(call.arg("u")))
+    same(call, dict(points=pts, inf=inf), "g1_map_from_fields (dev)")
+
+
+@pytest.mark.parametrize("flags", [True, False], ids=["inf", "inf-none"])
+def test_g1_clear_cofactor_three_slices_of_points_of_every_kind(eng, flags):
+    """2 * 2^17 + 5 points of E, identities of every kind among them: g1h_clear_dev's point, flag and output pointers in every slice.
+    Without the flag bytes the rows whose input is a flagged identity are compared with nothing: their words are then a point off the curve"""
+    call = sp.minsig_clear_call()
+    pin, iin = call.arg("pts"), call.arg("inf")
+    if flags:
+        pts, inf = eng.g1_clear_cofactor(pin, iin)
+        same(call, dict(points=pts, inf=inf), "g1_clear_cofactor (host)")
+        pts, inf = eng.g1_clear_cofactor(to_dev(pin), to_dev(iin))
+        same(call, dict(points=pts, inf=inf), "g1_clear_cofactor (dev)")
+        return
+    keep = iin == 0
+    for what, got in (("host", eng.g1_clear_cofactor(pin)), ("dev", eng.g1_clear_cofactor(to_dev(pin)))):
+        for name, g in zip(("points", "inf"), got):
+            want = call.want(name)
+            g = to_host(g).view(want.dtype).reshape(want.shape).copy()
+            g[~keep] = want[~keep]
+            if g.tobytes() != want.tobytes():
+                pytest.fail("g1_clear_cofactor inf = None (%s): output %s differs, first at %r" % (what, name, sp.first_difference(g, want, 1, call)))
+
+
+_RESIDENT = {}
+
+
+def _resident(key, build):
+    """the device tensors of a call, made once for the tests that share it"""
+    if key not in _RESIDENT:
+        _RESIDENT[key] = build()
+    return _RESIDENT[key]
+
+
+def _minsig_verify(eng, same_key, msgs=None, sig=None, inf_pk=None):
+    call = sp.minsig_verify_call(same_key)
+    t = _resident(("minsig", same_key), lambda: dict(pk=to_dev(call.pk1 if same_key else call.arg("pk")), msgs=to_dev(call.msgs), sig=to_dev(call.arg("sig")),
+                                                     off=to_dev(call.offsets), rand=to_dev(call.arg("rand"))))
+    msgs = t["msgs"] if msgs is None else to_dev(msgs)
+    sig = t["sig"] if sig is None else to_dev(sig)
+    if same_key:
+        ok = eng.bls_minsig_verify_samekey(t["pk"], msgs, sig, _minsig_dst(), offsets=t["off"], rand=t["rand"])
+    else:
+        ok = eng.bls_minsig_verify(t["pk"], msgs, sig, _minsig_dst(), offsets=t["off"], rand=t["rand"], inf_pk=None if inf_pk is None else to_dev(inf_pk))
+    return bool(to_host(ok)[0])
+
+
+@pytest.mark.parametrize("same_key", [False, True], ids=["general", "samekey"])
+def test_minsig_verify_two_slices_holds(eng, same_key):
+    """2^17 + 6 model-signed messages: hash_into's output pointer, hp + 12 at ostride (ostride 2 for the same-key rows), must be the slice's own"""
+    assert _minsig_verify(eng, same_key) is True
+
+
+@pytest.mark.parametrize("where", [0, 1, 2])
+@pytest.mark.parametrize("same_key", [False, True], ids=["general", "samekey"])
+def test_minsig_verify_one_forgery_on_either_side_of_the_boundary(eng, same_key, where):
+    call = sp.minsig_verify_call(same_key)
+    assert _minsig_verify(eng, same_key, msgs=sp.forged_messages(call, call.forged[where])) is False
+
+
+@pytest.mark.parametrize("same_key", [False, True], ids=["general", "samekey"])
+def test_minsig_verify_a_signature_outside_g1_behind_the_boundary(eng, same_key):
+    """signature 2^17 + 2 moved by a point of order 3: the product still holds, only the status byte st[n + 2^17 + 2] (same key: st[2^17 + 2])
+    refuses the batch"""
+    call = sp.minsig_verify_call(same_key)
+    assert _minsig_verify(eng, same_key, sig=sp.shifted_signature(call, call.shifted)[0]) is False
+
+
+def test_minsig_verify_an_identity_key_behind_the_boundary(eng):
+    call = sp.minsig_verify_call(False)
+    inf_pk = np.zeros(call.n, dtype=np.uint8)
+    assert _minsig_verify(eng, False, inf_pk=inf_pk) is True                                   # flags that are all zero change nothing
+    inf_pk[call.flagged_pk] = 1
+    assert _minsig_verify(eng, False, inf_pk=inf_pk) is False
+
+
+# ------------------------------------------------------------------------------------------------------------------- committees and groups above 2^17
+def _i32(a):
+    return to_dev(np.ascontiguousarray(a).view(np.int32))
+
+
+def _committees():
+    call = sp.committees_call()
+    t = _resident("committees", lambda: dict(table=to_dev(call.pool["table"]), entries=_i32(call.entries), seg_off=to_dev(call.seg_off), msgs=to_dev(call.msgs),
+                                             off=to_dev(call.offsets), sig=to_dev(call.arg("sig")), rand=to_dev(call.arg("rand"))))
+    return call, t
+
+
+def test_g1_segment_sum_on_two_to_the_17_and_six_committees(eng):
+    """2^17 + 6 segments of 1 .. 33 signed table rows, about 10^6 entries: k_agg_keys' search and k_agg_affine beyond a few hundred segments"""
+    call, t = _committees()
+    out, oi, st = eng.g1_segment_sum(t["table"], t["entries"], t["seg_off"])
+    want = call.want("apk")
+    g = to_host(out).view(np.uint64).reshape(want.shape)
+    if g.tobytes() != want.tobytes():
+        pytest.fail("g1_segment_sum: out differs, first at %r" % sp.first_difference(g, want, 1, call))
+    assert not to_host(oi).any() and not to_host(st).any() and to_host(oi).shape == to_host(st).shape == (call.n,)
+
+
+def _aggregate_verify(eng, entries=None):
+    import h2c_model as h
+    call, t = _committees()
+    ok = eng.bls_fast_aggregate_verify(t["table"], t["entries"] if entries is None else _i32(entries), t["seg_off"], t["msgs"], t["sig"], h.ETH_DST, offsets=t["off"],
+                                       rand=t["rand"])
+    return bool(to_host(ok)[0])
+
+
+def test_fast_aggregate_verify_two_slices_of_committees_holds(eng):
+    """bls_verify_dev on 2^17 + 6 aggregate keys held in the workspace: every slice of it must take its own keys, flags and hashed points"""
+    assert _aggregate_verify(eng) is True
+
+
+@pytest.mark.parametrize("where", [0, 1, 2])
+def test_fast_aggregate_verify_one_wrong_member_on_either_side_of_the_boundary(eng, where):
+    call = sp.committees_call()
+    assert _aggregate_verify(eng, sp.swapped_member(call, call.forged[where])[0]) is False
+
+
+def _grouped(eng, msgs=None, grp_off=None, expanded=False):
+    """bls_verify_grouped, or bls_verify on the messages expanded per signature, with the same rand"""
+    import h2c_model as h
+    call = sp.grouped_call()
+    t = _resident("grouped", lambda: dict(pk=to_dev(call.pk), sig=to_dev(call.sig), rand=to_dev(call.rand), grp_off=to_dev(call.grp_off), msgs=to_dev(call.msgs),
+                                          off=to_dev(call.offsets)))
+    if expanded:
+        buf, off = sp.expanded_messages(call, msgs)
+        ok = eng.bls_verify(t["pk"], to_dev(buf), t["sig"], h.ETH_DST, offsets=to_dev(off), rand=t["rand"])
+    else:
+        ok = eng.bls_verify_grouped(t["pk"], t["grp_off"] if grp_off is None else to_dev(grp_off), t["msgs"] if msgs is None else to_dev(msgs), t["sig"], h.ETH_DST,
+                                    offsets=t["off"], rand=t["rand"])
+    return bool(to_host(ok)[0])
+
+
+def test_verify_grouped_two_slices_of_messages_holds_as_the_ungrouped_call_does(eng):
+    """2^17 + 6 messages, one signature more: h2c_hash_dev over m messages in two slices, k_grp_keys and k_grp_affine over 2^17 + 6 groups,
+    a Miller product of m pairs; groups of 0, 2 and 3 signatures at 5, 6, 2^17 - 2 and 2^17"""
+    assert _grouped(eng) is True
+    assert _grouped(eng, expanded=True) is True
+
+
+@pytest.mark.parametrize("where", [0, 1, 2])
+def test_verify_grouped_one_changed_message_on_either_side_of_the_boundary(eng, where):
+    call = sp.grouped_call()
+    bad = sp.forged_messages(call, call.forged[where])
+    assert _grouped(eng, msgs=bad) is False
+    if where == 1:
+        assert _grouped(eng, msgs=bad, expanded=True) is False
+
+
+def test_verify_grouped_a_signature_filed_under_its_neighbour_behind_the_boundary(eng):
+    call = sp.grouped_call()
+    off = call.grp_off.copy()
+    off[call.moved] += 1
+    assert _grouped(eng, grp_off=off) is False

@@ -3,7 +3,8 @@ own offsets (the docstring of tests/slice_pools.py states them).  The slice leng
 compute for the exact shapes; every shape crosses its boundaries and ends in a short slice; no slice of any input or expected output
 equals another slice's rows; the expected arrays read with a wrong offset differ from the true ones in every output array; the pools
 are consistent on integers by a second route.  The same for the sliced calls of csrc/zkp_bls.hip: hash_to_field_g2, hash_to_g2, the map
-and the verifier (BLS_NAMES).  No GPU and no library call."""
+and the verifier (BLS_NAMES), for those of csrc/zkp_bls_minsig.hip (MINSIG_NAMES) and for the grouped and the committee verifier above
+2^17 messages or committees (DRIVER_NAMES).  No GPU and no library call."""
 import os
 import subprocess
 
@@ -25,6 +26,7 @@ PROGRAM = """
 #include "zkp_fk20_plan.hpp"
 #include "zkp_poly_plan.hpp"
 #include "zkp_bls_plan.hpp"
+#include "zkp_bls_minsig_plan.hpp"
 int main() {
     using namespace zkp;
     std::printf("g1ntt %%zu\\n", fk20::slice_vectors((size_t)%d, %du));
@@ -39,6 +41,16 @@ int main() {
     std::printf("bls_verify %%zu\\n", bls::layout((size_t)%d, true).slice);
     std::printf("bls_small %%zu\\n", bls::layout((size_t)5, true).slice);
     std::printf("bls_stride %%zu\\n", (bls::layout((size_t)%d, false).hq - bls::layout((size_t)%d, false).pts) / (bls::POINT_I32 * 4));
+    std::printf("minsig_const %%zu\\n", minsig::SLICE);
+    std::printf("minsig_field %%zu\\n", minsig::layout((size_t)%d, minsig::HASH).slice);
+    std::printf("minsig_map %%zu\\n", minsig::layout((size_t)%d, minsig::HASH).slice);
+    std::printf("minsig_clear %%zu\\n", minsig::layout((size_t)%d, minsig::HASH).slice);
+    std::printf("minsig_verify %%zu\\n", minsig::layout((size_t)%d, minsig::VERIFY).slice);
+    std::printf("minsig_samekey %%zu\\n", minsig::layout((size_t)%d, minsig::SAMEKEY).slice);
+    std::printf("minsig_small %%zu %%zu %%zu\\n", minsig::layout((size_t)5, minsig::HASH).slice, minsig::layout((size_t)5, minsig::VERIFY).slice,
+                minsig::layout((size_t)5, minsig::SAMEKEY).slice);
+    std::printf("bls_grouped %%zu\\n", bls::layout((size_t)%d, false).slice);
+    std::printf("bls_committees %%zu\\n", bls::layout((size_t)%d, true).slice);
     return 0;
 }
 """
@@ -49,12 +61,13 @@ def header_slices(tmp_path_factory):
     d = tmp_path_factory.mktemp("slices")
     src, exe = str(d / "slices.cpp"), str(d / "slices")
     with open(src, "w") as f:
-        f.write(PROGRAM % (sp.NTT_N_VEC, sp.NTT_LOG2, sp.FK20_N, sp.FK20_LOG2, sp.OPEN_N, sp.OPEN_LOG2, sp.HASH_N, sp.MAP_N, sp.VERIFY_N, sp.HASH_N, sp.HASH_N))
+        f.write(PROGRAM % (sp.NTT_N_VEC, sp.NTT_LOG2, sp.FK20_N, sp.FK20_LOG2, sp.OPEN_N, sp.OPEN_LOG2, sp.HASH_N, sp.MAP_N, sp.VERIFY_N, sp.HASH_N, sp.HASH_N,
+                           sp.HASH_N, sp.MAP_N, sp.MAP_N, sp.VERIFY_N, sp.VERIFY_N, sp.GROUPED_M, sp.COM_N))
     cc = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", exe, src], capture_output=True, text=True, timeout=300)
     assert cc.returncode == 0, cc.stdout[-3000:] + cc.stderr[-3000:]
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr[-3000:]
-    return {k: int(v) for k, v in (line.split() for line in out.stdout.split("\n") if line)}
+    return {k: (int(v[0]) if len(v) == 1 else tuple(int(x) for x in v)) for k, *v in (line.split() for line in out.stdout.split("\n") if line)}
 
 
 @pytest.fixture(scope="module")
@@ -329,3 +342,208 @@ def test_opening_pool_y_is_horner_and_in_the_domain_the_evaluation_of_the_slot(c
             ev = _ints(sp.rows(c.arg("evals"), st.n, j, 1))
             assert ev == p["evals_int"][c.idx[j]] and ev[5] == prc.horner(f, st.slot_domain[5])
         assert c.want("inf")[c.n - 3:].tolist() == [0, 1, 0] and sp.OPEN_POLY_KINDS[sp.OPEN_TAIL[1]] == "constant"
+
+
+# ------------------------------------------------------------------------------------------------------------------- min-sig, grouped and committees
+# The same conditions for the sliced calls of csrc/zkp_bls_minsig.hip (MINSIG_NAMES) and for the two verifiers that drive sliced callees on
+# m messages or n committees (DRIVER_NAMES): slice lengths from the planning headers, shapes and tails, no shift invariance, the two wrong
+# readings, the packing, and the pools by a second route.
+MINSIG_NAMES = ["minsig_field", "minsig_map", "minsig_clear", "minsig_verify", "minsig_samekey"]
+DRIVER_NAMES = ["grouped", "committees"]
+OUTPUTS = {"minsig_field": {"u"}, "minsig_map": {"points", "inf"}, "minsig_clear": {"points", "inf"}, "minsig_verify": {"hp"}, "minsig_samekey": {"hp"},
+           "grouped": {"hq"}, "committees": {"apk", "hq"}}
+
+
+@pytest.fixture(scope="module")
+def more_calls():
+    return {"minsig_field": sp.minsig_field_call(), "minsig_map": sp.minsig_map_call(), "minsig_clear": sp.minsig_clear_call(),
+            "minsig_verify": sp.minsig_verify_call(False), "minsig_samekey": sp.minsig_verify_call(True), "grouped": sp.grouped_call(),
+            "committees": sp.committees_call()}
+
+
+def test_minsig_slice_lengths_shapes_and_tails(header_slices, more_calls):
+    h = header_slices
+    for k in ("minsig_const", "minsig_field", "minsig_map", "minsig_clear", "minsig_verify", "minsig_samekey", "bls_grouped", "bls_committees"):
+        assert h[k] == sp.BLS_SLICE == 1 << 17, k
+    assert h["minsig_small"] == (5, 5, 5)                                                         # a call of 5 has the slice, and the strides, of its own size
+    want = {"minsig_field": (2, 61), "minsig_map": (3, 5), "minsig_clear": (3, 5), "minsig_verify": (2, 6), "minsig_samekey": (2, 6), "grouped": (2, 6),
+            "committees": (2, 6)}
+    tails = {"minsig_field": sp.HASH_TAIL, "minsig_map": sp.MAP_TAIL, "minsig_clear": sp.MAP_TAIL}
+    for name in MINSIG_NAMES + DRIVER_NAMES:
+        c = more_calls[name]
+        n_slices, tail = want[name]
+        ids = tails.get(name, sp.VERIFY_TAIL)
+        assert c.slice == sp.BLS_SLICE and c.starts == [s * c.slice for s in range(n_slices)] and c.tail == tail == c.n - c.starts[-1], name
+        assert set(c.outputs) == OUTPUTS[name] and c.constant == set(), name
+        for arr, per in list(c.inputs.values()) + list(c.outputs.values()):
+            assert per == 1 and arr.shape[0] == c.n and arr.flags.c_contiguous, name
+        last, body = c.idx[c.n - c.tail:], c.idx[:c.n - c.tail]
+        assert set(last.tolist()) == set(ids) and set(body.tolist()) == set(range(sp.BLS_B)) - set(ids), name
+        assert name == "minsig_field" or last.tolist() == list(ids), name                         # distinct items
+        assert sp.BLS_B == 13 and c.slice % sp.BLS_B
+        for shift in list(range(1, 64)) + [c.slice]:
+            if shift < len(body):
+                assert (body[shift:] != body[:-shift]).mean() > 0.5, (name, shift)
+    assert 2 * more_calls["minsig_field"].tail == 64 + 58                                         # k_g1h_map: one full wavefront and a partial one
+    assert more_calls["minsig_field"].tail == 61 and more_calls["minsig_map"].tail == 5           # k_g1h_clear / k_g1h_affine: partial wavefronts
+
+
+@pytest.mark.parametrize("name", MINSIG_NAMES + DRIVER_NAMES)
+def test_minsig_no_slice_repeats_the_rows_of_another(more_calls, name):
+    c = more_calls[name]
+    arrays = list(c.inputs.items()) + list(c.outputs.items())
+    assert len(arrays) >= 2
+    for at in c.starts[1:]:
+        w = sp.window(c, at)
+        assert w == min(64, c.slice, c.n - at)
+        for other in c.starts:
+            if other == at:
+                continue
+            for what, (arr, per) in arrays:
+                assert sp.rows(arr, per, at, w).tobytes() != sp.rows(arr, per, other, w).tobytes(), (name, what, at, other)
+
+
+@pytest.mark.parametrize("how", ["zero", "previous"])
+@pytest.mark.parametrize("name", MINSIG_NAMES + DRIVER_NAMES)
+def test_minsig_a_wrong_offset_in_any_slice_changes_every_output_array(more_calls, name, how):
+    c = more_calls[name]
+    assert set(c.outputs) == OUTPUTS[name] and c.constant == set()                                # no constant output: every array tells offsets apart
+    for what, (arr, per) in c.outputs.items():
+        wrong = sp.reading(c, what, how)
+        assert wrong.shape == arr.shape and wrong.tobytes() != arr.tobytes(), (name, what, how)
+        assert sp.rows(wrong, per, 0, c.slice).tobytes() == sp.rows(arr, per, 0, c.slice).tobytes()
+        for at in c.starts[1:]:
+            cnt = min(c.slice, c.n - at)
+            assert sp.rows(wrong, per, at, cnt).tobytes() != sp.rows(arr, per, at, cnt).tobytes(), (name, what, how, at)
+            assert sp.first_difference(wrong, arr, per, c)["slice"] == 1
+    if len(c.starts) > 2:
+        for what in c.outputs:
+            assert sp.reading(c, what, "zero").tobytes() != sp.reading(c, what, "previous").tobytes(), (name, what)
+
+
+def test_minsig_messages_are_packed_as_the_pool_has_them(more_calls):
+    for name in ("minsig_field", "minsig_verify", "minsig_samekey", "grouped", "committees"):
+        c = more_calls[name]
+        off, msgs = c.offsets, c.pool["msgs"]
+        base = sp.HASH_BASE if name == "minsig_field" else sp.VERIFY_BASE
+        assert off.dtype == np.uint64 and off.shape == (c.n + 1,) and int(off[0]) == base > 0 and int(off[-1]) == c.msgs.size
+        assert (c.msgs[:base] == 0xA5).all() and (np.diff(off.astype(np.int64)) == np.array([len(x) for x in msgs])[c.idx]).all()
+        for j in (0, 1, 2, c.slice - 1, c.slice, c.slice + 1, c.n - 2, c.n - 1):
+            assert c.msgs[int(off[j]):int(off[j + 1])].tobytes() == msgs[c.idx[j]], (name, j)
+        lens = np.diff(off.astype(np.int64))
+        for at in c.starts:
+            assert len(set(lens[at:at + sp.window(c, at)].tolist())) >= 4, (name, at)
+    c = more_calls["minsig_field"]
+    assert tuple(len(x) for x in c.pool["msgs"]) == sp.HASH_LENGTHS and (np.diff(c.offsets.astype(np.int64))[:c.slice] == 0).any()
+
+
+def test_minsig_identity_outputs_on_both_sides_of_every_boundary(more_calls):
+    for name in ("minsig_map", "minsig_clear"):
+        c = more_calls[name]
+        inf = c.want("inf")
+        assert inf[c.n - c.tail:].sum() == 1 and inf[c.n - c.tail:].tolist() == [int(j == sp.MAP_INF) for j in sp.MAP_TAIL], name
+        for at in c.starts[:-1]:
+            assert inf[at:at + 64].any() and not inf[at:at + 64].all() and inf[at + c.slice - 64:at + c.slice].any(), (name, at)
+        assert (c.want("points")[inf == 1] == np.eye(1, 12, 6, dtype=np.uint64)[0]).all()
+    c = more_calls["minsig_clear"]
+    assert sp.CLEAR_FLAGGED_TAIL == sp.MAP_INF and {"identity", "order3_plus", "order11"} <= set(c.pool["names"])
+    fin = c.arg("inf")                                                                            # the input flags: one flagged item in the body, one in the tail
+    assert fin[c.n - c.tail:].sum() == 1 and all(fin[at:at + c.slice].any() for at in c.starts[:-1])
+    names = np.array(c.pool["names"])
+    for at in c.starts[:-1]:                                                                      # every kind of identity in every full slice, unflagged ones among them
+        assert {"identity", "order3_plus", "order3_minus", "order11"} <= set(names[c.idx[at:at + c.slice]])
+    assert ((c.want("inf") == 1) & (fin == 0)).any() and c.want("inf").sum() > 2 * fin.sum()
+
+
+def test_minsig_pools_are_consistent_by_a_second_route(more_calls):
+    import h2c_model as h
+    import h2g1_model as g
+    import minsig_replay_cases as mrc
+    p = sp.minsig_field_pool()
+    for j, msg in enumerate(p["msgs"]):
+        assert _ints(p["u"][j].reshape(2, 6)) == list(g.hash_to_field_g1(msg, mrc.DST))
+    p = sp.minsig_map_pool()
+    assert [q is None for q in p["pts"]] == [j in (sp.MAP_INF, sp.MAP_INF_BODY) for j in range(sp.BLS_B)]
+    for (u0, u1), q, row, flag in zip(p["us"], p["pts"], p["points"], p["inf"]):
+        assert q == g.clear_cofactor(g.e_add(g.iso11(g.sswu(u0)[0]), g.iso11(g.sswu(u1)[0]))) and g.words_g1(row, flag) == q
+        assert g.in_g1(q)
+    p = sp.minsig_clear_pool()
+    assert p["pts_inf"].tolist() == [int(q is None) for q in p["pts"]] and p["pts"][0] == (0, 2)
+    for q, out, row, flag in zip(p["pts"], p["outs"], p["points"], p["inf"]):
+        assert g.e_on_curve(q) and g.words_g1(row, flag) == out and g.in_g1(out)
+        assert out == g.e_add(q, g.e_mul(q, g.X_ABS))                                             # [1 - x] P = P + [|x|] P: x is negative
+    assert [o is None for o in p["outs"]] == [k in ("order3_plus", "order3_minus", "identity", "order11", "flagged_generator") for k in p["names"]]
+    for same_key in (False, True):
+        name = "minsig_samekey" if same_key else "minsig_verify"
+        c = more_calls[name]
+        p = c.pool
+        assert len(p["pool"]) == sp.BLS_B and len({x[0] for x in p["pool"]}) == (1 if same_key else sp.BLS_B)
+        for j, (sk, pk, msg, sig) in enumerate(p["pool"]):
+            hp = mrc.hashed(msg, mrc.DST)
+            u0, u1 = g.hash_to_field_g1(msg, mrc.DST)
+            assert hp == g.clear_cofactor(g.e_add(g.iso11(g.sswu(u0)[0]), g.iso11(g.sswu(u1)[0])))
+            assert g.words_g1(p["hp"][j], 0) == hp and g.words_g1(p["sig"][j], 0) == sig and h.words_g2(p["pk"][j], 0) == pk == g.sk_to_pk(sk)
+            assert g.in_g1(sig) and sig == g.e_mul(hp, sk) and g.verify(pk, msg, sig, mrc.DST)
+        assert c.forged == (c.slice - 1, c.slice, c.n - 1) and (c.arg("rand") != 0).all()
+        for j in c.forged:
+            sk, pk, msg, sig = p["pool"][c.idx[j]]
+            bad = sp.forged_messages(c, j)
+            lst = sp.message_list(c, bad)
+            assert len(msg) > 0 and (bad != c.msgs).sum() == 1 and lst[j] != msg and len(lst[j]) == len(msg) and lst[j - 1] == p["msgs"][c.idx[j - 1]]
+            assert g.hash_to_g1(lst[j], mrc.DST) != mrc.hashed(msg, mrc.DST)                      # another point: [sk] of it is another signature
+        sig, moved = sp.shifted_signature(c, c.shifted)
+        assert c.shifted == c.slice + 2 and g.e_on_curve(moved) and not g.in_g1(moved) and (sig != c.arg("sig")).any(axis=1).sum() == 1
+        assert g.e_mul(moved, 3) == g.e_mul(p["pool"][c.idx[c.shifted]][3], 3)
+    assert more_calls["minsig_samekey"].pk1.shape == (1, 24) and more_calls["minsig_verify"].flagged_pk == sp.BLS_SLICE + 1
+
+
+def test_grouped_and_committee_calls_are_what_their_pools_sign(more_calls):
+    import agg_model as am
+    import bls_replay_cases as brc
+    import bls12_381_model as m
+    import h2c_model as h
+    from h2g1_model import words_g1
+    c = more_calls["grouped"]
+    p = c.pool
+    m_msgs, n = c.n, c.member.size
+    assert n == m_msgs + 1 == int(c.grp_off[-1]) and c.grp_off.dtype == np.uint64 and int(c.grp_off[0]) == 0
+    assert {g: int(c.sizes[g]) for g in sp.GROUPED_SIZES} == {5: 0, 6: 2, c.slice - 2: 0, c.slice: 3} and (np.delete(c.sizes, list(sp.GROUPED_SIZES)) == 1).all()
+    assert (np.diff(c.grp_off.astype(np.int64)) == c.sizes).all() and c.pk.shape == (n, 12) and c.sig.shape == (n, 24) and c.rand.shape == (n, 2)
+    for i in (0, 5, 6, 7, n // 2, n - 1):                                                         # signature i is its group's pool item
+        g = int(c.member[i])
+        assert int(c.grp_off[g]) <= i < int(c.grp_off[g + 1]) and c.pk[i].tobytes() == p["pk"][c.idx[g]].tobytes() and c.sig[i].tobytes() == p["sig"][c.idx[g]].tobytes()
+    assert (c.rand != 0).all() and len({tuple(r) for r in c.rand[int(c.grp_off[c.slice]):int(c.grp_off[c.slice + 1])].tolist()}) == 3
+    for j in c.forged:                                                                            # a changed message matters only where somebody signed it
+        sk, pk, msg, sig = p["pool"][c.idx[j]]
+        lst = sp.message_list(c, sp.forged_messages(c, j))
+        assert c.sizes[j] >= 1 and len(msg) > 0 and lst[j] != msg and not h.verify(pk, lst[j], sig, brc.DST)
+    assert c.forged == (c.slice - 1, c.slice + 1, m_msgs - 1) and c.moved == c.slice + 1
+    assert c.idx[c.moved] != c.idx[c.moved - 1] and c.sizes[c.moved] == 1                         # the moved signature lands under another message
+    sk, pk, msg, sig = p["pool"][c.idx[c.moved]]
+    assert not h.verify(pk, p["msgs"][c.idx[c.moved - 1]], sig, brc.DST)
+    buf, off = sp.expanded_messages(c)
+    assert off.shape == (n + 1,) and int(off[0]) == sp.VERIFY_BASE
+    for i in (0, 6, 7, n - 1):
+        assert buf[int(off[i]):int(off[i + 1])].tobytes() == p["msgs"][c.idx[c.member[i]]]
+    c = more_calls["committees"]
+    p = c.pool
+    sks, pks = am.key_table(sp.COM_TABLE)
+    assert tuple(len(e) for e in p["entries"]) == sp.COM_SIZES and sorted(set(sp.COM_SIZES)) == [1, 2, 3, 4, 5, 7, 33]
+    assert any(e & am.SIGN for x in p["entries"] for e in x) and all(not x[0] & am.SIGN for x in p["entries"])
+    sizes = np.diff(c.seg_off.astype(np.int64))
+    assert (sizes == np.array(sp.COM_SIZES)[c.idx]).all() and c.entries.size == int(c.seg_off[-1]) < 8 * c.n and c.entries.dtype == np.uint32
+    assert (sizes[:c.slice] == 33).sum() > 1000 and sp.COM_SIZES[6] == 33 and 6 not in sp.VERIFY_TAIL
+    for j in (0, 1, c.slice - 1, c.slice, c.n - 1):
+        assert c.entries[int(c.seg_off[j]):int(c.seg_off[j + 1])].tolist() == p["entries"][c.idx[j]]
+    for j, (e, sk, msg) in enumerate(zip(p["entries"], p["sks"], p["msgs"])):
+        acc = None
+        for x in e:
+            acc = m.g1_add(acc, m.g1_neg(pks[x & am.ROW]) if x & am.SIGN else pks[x & am.ROW])
+        assert acc == am.public_key(sk) and words_g1(p["apk"][j], 0) == acc                       # the signed sum of the keys is the key of the signed sum
+        assert h.verify(acc, msg, h.words_g2(p["sig"][j], 0), brc.DST) and h.words_g2(p["hq"][j], 0) == brc.hashed(msg, brc.DST)
+    for j in c.forged:                                                                            # another member: another aggregate key under the same signature
+        entries, other = sp.swapped_member(c, j)
+        e = p["entries"][c.idx[j]]
+        assert other not in {x & am.ROW for x in e} and (entries != c.entries).sum() == 1
+        assert (p["sks"][c.idx[j]] - sks[e[0]] + sks[other]) % h.R_ORDER != p["sks"][c.idx[j]]
+    assert c.forged == (c.slice - 1, c.slice, c.n - 1)
