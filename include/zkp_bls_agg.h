@@ -52,8 +52,8 @@
  * verifier 96 + 2 B per committee and the workspaces of zkp_bls_verify_batch.
  *
  * Out of scope: folding aggregates that sign the SAME message into one Miller pair (sum [r_i] apk_i by message before the pairing - the
- * follow-up, on this segment sum), AggregateVerify with ragged numbers of distinct messages per signature, G2 segment sums, aggregation
- * bitfields expanded on the device, hashing to G1, more than one GPU.
+ * follow-up, on this segment sum), aggregation bitfields expanded on the device, hashing to G1, more than one GPU.
+ * G2 segment sums and AggregateVerify with ragged numbers of messages per signature went to zkp_bls_agg_g2.h.
  */
 #ifndef ZKP_BLS_AGG_H
 #define ZKP_BLS_AGG_H

@@ -59,8 +59,9 @@
  * verifiers 34 B per signature, 291 B per message, three Fp12 records, the hash's workspace at m messages and the G2 MSM's at n terms;
  * for the aggregate form 98 B per committee and the workspace of zkp_g1_segment_sum_batch.
  *
- * Out of scope: sorting the signatures by message on the device (the caller sorts; the keys must arrive sorted), AggregateVerify with
- * ragged numbers of distinct messages per signature, G2 segment sums, hashing to G1 (the 11-isogeny of RFC 9380), more than one GPU.
+ * Out of scope: sorting the signatures by message on the device (the caller sorts; the keys must arrive sorted), hashing to G1
+ * (the 11-isogeny of RFC 9380), more than one GPU.  AggregateVerify with ragged numbers of messages per signature and G2 segment sums
+ * went to zkp_bls_agg_g2.h.
  */
 #ifndef ZKP_BLS_GROUPED_H
 #define ZKP_BLS_GROUPED_H

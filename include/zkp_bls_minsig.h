@@ -50,8 +50,8 @@
  * byte, two status bytes; 196 B for the same-key verifier, whose rows hold the signature too) and the workspaces of
  * zkp_pairing_check_batch_rlc with k = 1, s2 = 1 (k = 0, s2 = 2).
  *
- * Out of scope: the _NU_ (encode-to-curve) suites, DSTs over 255 bytes, committee aggregation for G2 keys (a G2 segment sum), grouping
- * by message for this layout, more than one GPU.
+ * Out of scope: the _NU_ (encode-to-curve) suites, DSTs over 255 bytes, grouping by message for this layout, more than one GPU.
+ * Committee aggregation for G2 keys (a G2 segment sum) went to zkp_bls_agg_g2.h.
  */
 #ifndef ZKP_BLS_MINSIG_H
 #define ZKP_BLS_MINSIG_H

@@ -17,6 +17,7 @@ pub mod bls;
 pub mod bls_agg;
 pub mod bls_grouped;
 pub mod bls_minsig;
+pub mod bls_agg_g2;
 
 #[repr(C)]
 pub struct ZkpCtx {

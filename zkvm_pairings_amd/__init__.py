@@ -1,6 +1,6 @@
 """MI355X-native batched BLS12-381 pairing engine behind the zkvm-pairings API shape.
 
-Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h, include/zkp_bls_agg.h, include/zkp_bls_grouped.h and include/zkp_bls_minsig.h); it raises if
+Loading this package loads libzkp_pairings.so (the C ABI in include/zkp_pairings.h, include/zkp_poly.h, include/zkp_prove.h, include/zkp_fk20.h, include/zkp_cells.h, include/zkp_recover.h, include/zkp_bls.h, include/zkp_bls_agg.h, include/zkp_bls_grouped.h, include/zkp_bls_minsig.h and include/zkp_bls_agg_g2.h); it raises if
 the library has not been built.  There is no CPU fallback."""
 from . import _lib
 from ._lib import ZkpError
@@ -17,6 +17,8 @@ from .pairings import (R1CS, CellSetup, Fk20Setup, Fr, G1Affine, G2Affine, Groth
                        group_by_message, bls_verify_grouped_batch, bls_fast_aggregate_verify_grouped_batch,
                        hash_to_g1, bls_minsig_keygen_batch, bls_minsig_sign_batch, bls_minsig_verify_batch, bls_minsig_verify_samekey_batch, bls_minsig_verify_each,
                        bls_minsig_verify_batch_compressed, bls_minsig_verify_each_compressed,
+                       bls_aggregate_signatures, bls_minsig_aggregate_keys, bls_minsig_fast_aggregate_verify_batch, bls_minsig_fast_aggregate_verify_each,
+                       bls_aggregate_verify_batch, bls_aggregate_verify_each,
                        multi_miller_loop, pairing)
 from . import synthetic  # noqa: E402
 
@@ -29,4 +31,6 @@ __all__ = ["PairingEngine", "G1Affine", "G2Affine", "Gt", "MillerLoopResult", "p
            "group_by_message", "bls_verify_grouped_batch", "bls_fast_aggregate_verify_grouped_batch",
            "hash_to_g1", "bls_minsig_keygen_batch", "bls_minsig_sign_batch", "bls_minsig_verify_batch", "bls_minsig_verify_samekey_batch", "bls_minsig_verify_each",
            "bls_minsig_verify_batch_compressed", "bls_minsig_verify_each_compressed",
+           "bls_aggregate_signatures", "bls_minsig_aggregate_keys", "bls_minsig_fast_aggregate_verify_batch", "bls_minsig_fast_aggregate_verify_each",
+           "bls_aggregate_verify_batch", "bls_aggregate_verify_each",
            "synthetic", "ZkpError", "KERNEL_AUTO", "KERNEL_THREAD", "KERNEL_COOP"]

@@ -286,6 +286,17 @@ BLS_MINSIG_SIGNATURES = {
     "zkp_bls_minsig_verify_samekey_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
 }
 
+# include/zkp_bls_agg_g2.h: G2 segment sums, FastAggregateVerify for committees of G2 keys, AggregateVerify
+AGG_G2_SIGNATURES = {
+    "zkp_g2_segment_sum_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "zkp_g2_segment_sum_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "zkp_bls_minsig_fast_aggregate_verify_batch": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_minsig_fast_aggregate_verify_batch_dev": (c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int,
+                                                               c_vp, c_vp]),
+    "zkp_bls_aggregate_verify_batch": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "zkp_bls_aggregate_verify_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_int, c_vp, c_vp]),
+}
+
 _lib = None
 
 
@@ -314,7 +325,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(POLY_SIGNATURES.items()) + list(PROVE_SIGNATURES.items()) + list(FK20_SIGNATURES.items()) +
                                   list(CELLS_SIGNATURES.items()) + list(RECOVER_SIGNATURES.items()) + list(BLS_SIGNATURES.items()) + list(AGG_SIGNATURES.items()) +
-                                  list(GRP_SIGNATURES.items()) + list(BLS_MINSIG_SIGNATURES.items())):
+                                  list(GRP_SIGNATURES.items()) + list(BLS_MINSIG_SIGNATURES.items()) + list(AGG_G2_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the ABI lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -264,6 +264,31 @@ int agg_verify_dev(zkp_ctx* c, const void* table, size_t n_table, const void* id
     return ctxop::fail(c, "k_agg_fold", hipGetLastError());
 }
 
+// the fill and the index kernels for zkp_bls_agg_g2.hip, which indexes G2 tables and message lists by the same rules
+namespace aggk {
+int zero(zkp_ctx* c, void* p, size_t bytes, hipStream_t s) {
+    const size_t n16 = bytes / 16, want = (n16 + 255) / 256;
+    hipLaunchKernelGGL(k_agg_zero, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, (uint4*)p, n16);
+    return ctxop::fail(c, "k_agg_zero", hipGetLastError());
+}
+int check(zkp_ctx* c, const void* seg_off, size_t n_seg, size_t n_idx, uint8_t* status, int* word, hipStream_t s) {
+    hipLaunchKernelGGL(k_agg_check, dim3(blocks_of(n_seg + 1, TPB_I)), dim3(TPB_I), 0, s, (const uint64_t*)seg_off, (uint32_t)n_seg, (uint64_t)n_idx, status, word,
+                       ctxop::bls_bad_word(c));
+    return ctxop::fail(c, "k_agg_check", hipGetLastError());
+}
+int keys(zkp_ctx* c, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, size_t n_table, const int* word, uint32_t* keys, uint32_t* vals,
+         uint8_t* status, hipStream_t s) {
+    if (!n_idx) return 0;
+    hipLaunchKernelGGL(k_agg_keys, dim3(blocks_of(n_idx, TPB_I)), dim3(TPB_I), 0, s, (const uint32_t*)idx, (uint32_t)n_idx, (const uint64_t*)seg_off,
+                       (uint32_t)n_seg, (uint32_t)n_table, word, keys, vals, status);
+    return ctxop::fail(c, "k_agg_keys", hipGetLastError());
+}
+int fold(zkp_ctx* c, const uint8_t* status, const void* seg_off, size_t n, const int* word, int* all_ok, hipStream_t s) {
+    hipLaunchKernelGGL(k_agg_fold, dim3(blocks_of(n ? n : 1, TPB_I)), dim3(TPB_I), 0, s, status, (const uint64_t*)seg_off, (uint32_t)n, word, all_ok);
+    return ctxop::fail(c, "k_agg_fold", hipGetLastError());
+}
+}  // namespace aggk
+
 #else
 }  // namespace
 #endif

@@ -17,4 +17,14 @@ int agg_segment_sum_dev(zkp_ctx* c, const void* table, size_t n_table, const voi
 int agg_verify_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, const void* msgs, const void* offsets,
                    const void* dst, size_t dst_len, const void* sig, const void* inf_sig, size_t n, const void* rand, int flags, int* all_ok, hipStream_t s);
 
+// the launches of this unit's fill and index kernels, for zkp_bls_agg_g2.hip: k_agg_zero over `bytes` (a multiple of 16) from p; k_agg_check
+// (word zeroed before; zeroes status[0 .. n_seg)); k_agg_keys (no launch when n_idx = 0); k_agg_fold
+namespace aggk {
+int zero(zkp_ctx* c, void* p, size_t bytes, hipStream_t s);
+int check(zkp_ctx* c, const void* seg_off, size_t n_seg, size_t n_idx, uint8_t* status, int* word, hipStream_t s);
+int keys(zkp_ctx* c, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, size_t n_table, const int* word, uint32_t* keys, uint32_t* vals,
+         uint8_t* status, hipStream_t s);
+int fold(zkp_ctx* c, const uint8_t* status, const void* seg_off, size_t n, const int* word, int* all_ok, hipStream_t s);
+}  // namespace aggk
+
 }  // namespace zkp

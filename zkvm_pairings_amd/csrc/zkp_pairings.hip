@@ -24,6 +24,7 @@
 #include "../../include/zkp_bls_agg.h"
 #include "../../include/zkp_bls_grouped.h"
 #include "../../include/zkp_bls_minsig.h"
+#include "../../include/zkp_bls_agg_g2.h"
 #include "zkp_field.hpp"
 #include "zkp_coop.hpp"
 #include "zkp_compress.hpp"
@@ -46,6 +47,7 @@
 #include "zkp_bls_agg.hpp"
 #include "zkp_bls_grouped.hpp"
 #include "zkp_bls_minsig.hpp"
+#include "zkp_bls_agg_g2.hpp"
 #include "zkp_fk20_plan.hpp"
 #include "zkp_plan.hpp"
 
@@ -3623,6 +3625,138 @@ int zkp_bls_minsig_verify_samekey_batch(zkp_ctx* c, const uint64_t* pk, const ui
     int rc;
     if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], 4)) || (rc = validate_dev(c, (const uint64_t*)d[1], n * 2)) ||
         (rc = zkp::minsig_verify_samekey_dev(c, d[0], dm, dof, dd, dst_len, d[1], d[2], n, d[3], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- G2 segment sums, the min-sig FastAggregateVerify and AggregateVerify
+// (zkp_bls_agg_g2.hip, include/zkp_bls_agg_g2.h)
+namespace {
+bool agg2_sum_args_bad(const zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, const void* out,
+                       const void* out_inf, const void* status) {
+    return !c || zkp::agg2::args_bad(n_table, n_idx, n_seg) || (n_table && !table) || (n_idx && !idx) || ((n_seg || n_idx) && !seg_off) ||
+           (n_seg && (!out || !out_inf || !status));
+}
+bool agg2_minsig_args_bad(const zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, const void* msgs,
+                          const void* offsets, const void* dst, size_t dst_len, const void* sig, size_t n, const void* rand, int flags, const void* all_ok) {
+    return h2c_msgs_bad(c, msgs, offsets, n, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || n > zkp::bls::MAX_VERIFY_N ||
+           zkp::rlc::args_bad(n, 1, 0, 1) || (n && (!sig || !rand)) || zkp::agg2::args_bad(n_table, n_idx, n) || (n_table && !table) || (n_idx && !idx) ||
+           ((n || n_idx) && !seg_off);
+}
+bool aggv_args_bad(const zkp_ctx* c, const void* pk, const void* msgs, const void* offsets, size_t n_msg, const void* seg_off, const void* dst, size_t dst_len,
+                   const void* sig, size_t n, const void* rand, int flags, const void* all_ok) {
+    // zkp_bls_verify_batch's refusals on n_msg, but sig and rand hold n rows: with messages and no signature (malformed) they may be null
+    return h2c_msgs_bad(c, msgs, offsets, n_msg, dst, dst_len) || !all_ok || (flags & ~ZKP_BLS_POINTS_CHECKED) || zkp::rlc::args_bad(n_msg, 1, 1, 0) ||
+           zkp::agg2::verify_args_bad(n_msg, n) || (n_msg && !pk) || (n && (!sig || !rand)) || ((n || n_msg) && !seg_off);
+}
+}  // namespace
+
+extern "C" {
+
+int zkp_g2_segment_sum_batch_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off, size_t n_seg, void* out,
+                                 void* out_inf, void* status, void* stream) {
+    if (agg2_sum_args_bad(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    if (int rc = validate_on_stream(c, table, n_table * 4, S(stream))) return rc;
+    return zkp::agg2_segment_sum_dev(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status, S(stream));
+}
+int zkp_g2_segment_sum_batch(zkp_ctx* c, const uint64_t* table, size_t n_table, const uint32_t* idx, size_t n_idx, const uint64_t* seg_off, size_t n_seg,
+                             uint64_t* out, uint8_t* out_inf, uint8_t* status) {
+    if (agg2_sum_args_bad(c, table, n_table, idx, n_idx, seg_off, n_seg, out, out_inf, status)) return ZKP_ERR_ARG;
+    if (!n_seg && !n_idx) return ZKP_OK;
+    if (zkp::agg::offsets_malformed(seg_off, n_seg, n_idx) || zkp::agg::rows_out_of_range(idx, n_idx, n_table)) return ZKP_ERR_ARG;
+    HostIO io(c);
+    const void* dt = io.in(0, table, n_table * 192);
+    const void* di = io.in(1, idx, n_idx * 4);
+    const void* ds = io.in(2, seg_off, (n_seg + 1) * 8);
+    void* dout = io.out(4, out, n_seg * 192);
+    void* dinf = io.out(5, out_inf, n_seg);
+    void* dst = io.out(6, status, n_seg);
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)dt, n_table * 4)) ||
+        (rc = zkp::agg2_segment_sum_dev(c, dt, n_table, di, n_idx, ds, n_seg, dout, dinf, dst, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_minsig_fast_aggregate_verify_batch_dev(zkp_ctx* c, const void* table, size_t n_table, const void* idx, size_t n_idx, const void* seg_off,
+                                                   const void* msgs, const void* offsets, const void* dst, size_t dst_len, const void* sig,
+                                                   const void* inf_sig, size_t n, const void* rand, int flags, void* all_ok, void* stream) {
+    if (agg2_minsig_args_bad(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, table, n_table * 4, S(stream))) || (rc = validate_on_stream(c, sig, n * 2, S(stream)))) return rc;
+    return zkp::agg2_minsig_verify_dev(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok,
+                                       S(stream));
+}
+// the six arrays one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_minsig_fast_aggregate_verify_batch(zkp_ctx* c, const uint64_t* table, size_t n_table, const uint32_t* idx, size_t n_idx, const uint64_t* seg_off,
+                                               const uint8_t* msgs, const uint64_t* offsets, const uint8_t* dst, size_t dst_len, const uint64_t* sig,
+                                               const uint8_t* inf_sig, size_t n, const uint64_t* rand, int flags, int* all_ok) {
+    if (agg2_minsig_args_bad(c, table, n_table, idx, n_idx, seg_off, msgs, offsets, dst, dst_len, sig, n, rand, flags, all_ok) ||
+        offsets_malformed(msgs, offsets, n))
+        return ZKP_ERR_ARG;
+    if ((n || n_idx) && (zkp::agg::offsets_malformed(seg_off, n, n_idx) || zkp::agg::rows_out_of_range(idx, n_idx, n_table))) return ZKP_ERR_ARG;
+    if (!n) { *all_ok = 1; return ZKP_OK; }
+    const void* field[6] = {table, idx, seg_off, sig, inf_sig, rand};
+    const size_t bytes[6] = {n_table * 192, n_idx * 4, (n + 1) * 8, n * 96, n, n * 16};
+    size_t off[6], total = 0;
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[6];
+    for (int i = 0; i < 6; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_table * 4)) || (rc = validate_dev(c, (const uint64_t*)d[3], n * 2)) ||
+        (rc = zkp::agg2_minsig_verify_dev(c, d[0], n_table, d[1], n_idx, d[2], dm, dof, dd, dst_len, d[3], d[4], n, d[5], flags, c->d_flag + 1, c->stream)))
+        return rc;
+    return io.finish();
+}
+
+int zkp_bls_aggregate_verify_batch_dev(zkp_ctx* c, const void* pk, const void* inf_pk, const void* msgs, const void* offsets, size_t n_msg, const void* seg_off,
+                                       const void* dst, size_t dst_len, const void* sig, const void* inf_sig, size_t n, const void* rand, int flags,
+                                       void* all_ok, void* stream) {
+    if (aggv_args_bad(c, pk, msgs, offsets, n_msg, seg_off, dst, dst_len, sig, n, rand, flags, all_ok)) return ZKP_ERR_ARG;
+    DEV_ENTER(c, stream);
+    int rc;
+    if ((rc = validate_on_stream(c, pk, n_msg * 2, S(stream))) || (rc = validate_on_stream(c, sig, n * 4, S(stream)))) return rc;
+    return zkp::aggv_verify_dev(c, pk, inf_pk, msgs, offsets, n_msg, seg_off, dst, dst_len, sig, inf_sig, n, rand, flags, (int*)all_ok, S(stream));
+}
+// the six arrays one after the other in slot 3 (256-byte aligned), the messages in slots 0..2, then the same driver
+int zkp_bls_aggregate_verify_batch(zkp_ctx* c, const uint64_t* pk, const uint8_t* inf_pk, const uint8_t* msgs, const uint64_t* offsets, size_t n_msg,
+                                   const uint64_t* seg_off, const uint8_t* dst, size_t dst_len, const uint64_t* sig, const uint8_t* inf_sig, size_t n,
+                                   const uint64_t* rand, int flags, int* all_ok) {
+    if (aggv_args_bad(c, pk, msgs, offsets, n_msg, seg_off, dst, dst_len, sig, n, rand, flags, all_ok) || offsets_malformed(msgs, offsets, n_msg))
+        return ZKP_ERR_ARG;
+    if ((n || n_msg) && zkp::agg::offsets_malformed(seg_off, n, n_msg)) return ZKP_ERR_ARG;
+    if (!n_msg) { *all_ok = n ? 0 : 1; return ZKP_OK; }                   // no message: no signature holds, every segment is empty
+    const void* field[6] = {pk, inf_pk, seg_off, sig, inf_sig, rand};
+    const size_t bytes[6] = {n_msg * 96, n_msg, (n + 1) * 8, n * 192, n, n * 16};
+    size_t off[6], total = 0;
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    HostIO io(c);
+    const uint8_t* dm;
+    const void *dof, *dd;
+    stage_msgs(io, 0, 1, 2, msgs, offsets, n_msg, dst, dst_len, &dm, &dof, &dd);
+    char* dev = (char*)io.slot(3, total);
+    const void* d[6];
+    for (int i = 0; i < 6; i++) d[i] = io.put(dev + off[i], field[i], bytes[i]);
+    io.get(all_ok, c->d_flag + 1, sizeof(int));
+    int rc;
+    if ((rc = io.status()) || (rc = validate_dev(c, (const uint64_t*)d[0], n_msg * 2)) || (rc = validate_dev(c, (const uint64_t*)d[3], n * 4)) ||
+        (rc = zkp::aggv_verify_dev(c, d[0], d[1], dm, dof, n_msg, d[2], dd, dst_len, d[3], d[4], n, d[5], flags, c->d_flag + 1, c->stream)))
         return rc;
     return io.finish();
 }

@@ -1237,12 +1237,12 @@ class PairingEngine:
             raise ValueError("seg_off: n_seg + 1 values, at least one")
         return idx, seg_off
 
-    def _entries_t(self, table, idx, seg_off):
+    def _entries_t(self, table, idx, seg_off, cols=12):
         import torch
-        self._t_check(table, 12, "table")
+        self._t_check(table, cols, "table")
         self._t_check(idx, None, "idx", dtypes=(torch.int32, torch.uint32))
         self._t_check(seg_off, None, "seg_off", rows=1)
-        return table.numel() // 12, idx.numel(), seg_off.numel() - 1
+        return table.numel() // cols, idx.numel(), seg_off.numel() - 1
 
     def g1_segment_sum(self, table, idx, seg_off):
         """out[j] = sum of (+/-) table[idx[e] & 0x7fffffff] over e in [seg_off[j], seg_off[j + 1]) (bit 31 of idx[e]: subtract;
@@ -1301,6 +1301,106 @@ class PairingEngine:
         ok = ctypes.c_int(0)
         self._chk(self._lib.zkp_bls_fast_aggregate_verify_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), _ptr(buf), _ptr(off),
                                                                 _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    # ------------------------------------------------------------------ G2 aggregation and AggregateVerify (include/zkp_bls_agg_g2.h)
+    def g2_segment_sum(self, table, idx, seg_off):
+        """g1_segment_sum over a table (n_table, 24) of finite G2 points (zkp_g2_segment_sum_batch): (points (n_seg, 24), inf (n_seg,),
+        status (n_seg,)) - the aggregate of signatures in the min-pk layout, of public keys in the min-sig layout.  The entries, the
+        refusals and the two flavours are those of g1_segment_sum."""
+        if _is_torch(table):
+            import torch
+            n_table, n_idx, n_seg = self._entries_t(table, idx, seg_off, 24)
+            out = torch.empty((n_seg, 24), dtype=table.dtype, device=table.device)
+            oi, st = torch.empty(n_seg, dtype=torch.uint8, device=table.device), torch.empty(n_seg, dtype=torch.uint8, device=table.device)
+            self._chk(self._lib.zkp_g2_segment_sum_batch_dev(self._h, self._tp(table), n_table, self._tp(idx), n_idx, self._tp(seg_off), n_seg, self._tp(out),
+                                                             self._tp(oi), self._tp(st), self._stream()))
+            return out, oi, st
+        table = _np(table, 24)
+        idx, seg_off = self._entries_np(idx, seg_off)
+        n_seg = seg_off.size - 1
+        out, oi, st = np.empty((n_seg, 24), dtype=np.uint64), np.empty(n_seg, dtype=np.uint8), np.empty(n_seg, dtype=np.uint8)
+        self._chk(self._lib.zkp_g2_segment_sum_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), n_seg, _ptr(out), _ptr(oi),
+                                                     _ptr(st)))
+        return out, oi, st
+
+    def bls_minsig_fast_aggregate_verify(self, table, idx, seg_off, msgs, sig, dst, offsets=None, inf_sig=None, rand=None, points_checked=False,
+                                         all_ok=None):
+        """bls_fast_aggregate_verify in the minimal-signature-size layout (zkp_bls_minsig_fast_aggregate_verify_batch): the key table is
+        (n_table, 24) in G2, the aggregate signatures (n, 12) in G1; True iff bls_minsig_verify holds on the committees' key sums, no
+        committee is empty and no row lies beyond the table.  The arguments and the return value of bls_fast_aggregate_verify."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(table):
+            import torch
+            n_table, n_idx, n = self._entries_t(table, idx, seg_off, 24)
+            self._t_check(sig, 12, "sig")
+            msgs, offsets, n_msg, dst = self._msgs_t(msgs, offsets, dst)
+            if n_msg != n or sig.numel() // 12 != n:
+                raise ValueError("%d committees, %d messages, %d signatures" % (n, n_msg, sig.numel() // 12))
+            self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(table.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=table.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_minsig_fast_aggregate_verify_batch_dev(self._h, self._tp(table), n_table, self._tp(idx), n_idx, self._tp(seg_off),
+                                                                               self._tp(msgs), self._tp(offsets), self._tp(dst), dst.numel(), self._tp(sig),
+                                                                               self._tp(inf_sig), n, self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            return all_ok
+        table, sig = _np(table, 24), _np(sig, 12)
+        idx, seg_off = self._entries_np(idx, seg_off)
+        buf, off, n, d = self._msgs_np(msgs, offsets, dst)
+        if seg_off.size - 1 != n or sig.shape[0] != n:
+            raise ValueError("%d committees, %d messages, %d signatures" % (seg_off.size - 1, n, sig.shape[0]))
+        isg = _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_minsig_fast_aggregate_verify_batch(self._h, _ptr(table), table.shape[0], _ptr(idx), idx.size, _ptr(seg_off), _ptr(buf),
+                                                                       _ptr(off), _ptr(d), d.size, _ptr(sig), _ptr(isg), n, _ptr(r), flags, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def bls_aggregate_verify(self, pk, msgs, seg_off, sig, dst, offsets=None, inf_pk=None, inf_sig=None, rand=None, points_checked=False, all_ok=None):
+        """n aggregate signatures (n, 24), signature j over the pairs (pk_i, m_i) for i in [seg_off[j], seg_off[j + 1]) of n_msg public keys
+        (n_msg, 12) and messages (zkp_bls_aggregate_verify_batch): True iff bls_verify holds with signature j filed under the first message
+        of its segment, the identity under the others and rand row j on all of them, the offsets are well formed and no segment is empty.
+        inf_pk (n_msg,), inf_sig (n,), rand (n, 2).  Messages of one segment are not tested for distinctness.  Host arrays return a bool
+        (malformed seg_off raises); resident torch tensors (seg_off int64) fill and return all_ok (int32 (1,)) without synchronising."""
+        flags = _lib.BLS_POINTS_CHECKED if points_checked else 0
+        if _is_torch(pk):
+            import torch
+            self._t_check(pk, 12, "pk"), self._t_check(sig, 24, "sig")
+            self._t_check(seg_off, None, "seg_off", rows=1)
+            msgs, offsets, n_msg, dst = self._msgs_t(msgs, offsets, dst)
+            n = seg_off.numel() - 1
+            if pk.numel() // 12 != n_msg or sig.numel() // 24 != n:
+                raise ValueError("%d messages, %d public keys; %d segments, %d signatures" % (n_msg, pk.numel() // 12, n, sig.numel() // 24))
+            self._t_bytes(inf_pk, n_msg, "inf_pk"), self._t_bytes(inf_sig, n, "inf_sig")
+            if rand is None:
+                rand = torch.from_numpy(self.rlc_random(n).view(np.int64)).to(pk.device)
+            self._t_check(rand, 2, "rand", rows=n)
+            if all_ok is None:
+                all_ok = torch.empty(1, dtype=torch.int32, device=pk.device)
+            self._t_check(all_ok, None, "all_ok", rows=1, dtypes=(torch.int32,))
+            self._chk(self._lib.zkp_bls_aggregate_verify_batch_dev(self._h, self._tp(pk), self._tp(inf_pk), self._tp(msgs), self._tp(offsets), n_msg,
+                                                                   self._tp(seg_off), self._tp(dst), dst.numel(), self._tp(sig), self._tp(inf_sig), n,
+                                                                   self._tp(rand), flags, self._tp(all_ok), self._stream()))
+            return all_ok
+        buf, off, n_msg, d = self._msgs_np(msgs, offsets, dst)
+        pk, sig = _np(pk, 12), _np(sig, 24)
+        seg_off = self._offsets_np(seg_off, "seg_off")
+        n = seg_off.size - 1
+        if pk.shape[0] != n_msg or sig.shape[0] != n:
+            raise ValueError("%d messages, %d public keys; %d segments, %d signatures" % (n_msg, pk.shape[0], n, sig.shape[0]))
+        ip, isg = _flags(inf_pk, n_msg, "inf_pk"), _flags(inf_sig, n, "inf_sig")
+        r = self.rlc_random(n) if rand is None else _np(rand, 2)
+        if r.shape[0] != n:
+            raise ValueError("rand holds %d pairs for %d signatures" % (r.shape[0], n))
+        ok = ctypes.c_int(0)
+        self._chk(self._lib.zkp_bls_aggregate_verify_batch(self._h, _ptr(pk), _ptr(ip), _ptr(buf), _ptr(off), n_msg, _ptr(seg_off), _ptr(d), d.size, _ptr(sig),
+                                                           _ptr(isg), n, _ptr(r), flags, ctypes.byref(ok)))
         return bool(ok.value)
 
     # ------------------------------------------------------------------ verification grouped by message (include/zkp_bls_grouped.h)

@@ -1113,6 +1113,81 @@ def bls_fast_aggregate_verify_each(table, committees, msgs, sigs, dst, bits=None
     return ok & (np.asarray(st) == 0) & (np.diff(seg_off.astype(np.int64)) > 0)
 
 
+# ------------------------------------------------------------------------------------------------ G2 aggregation and AggregateVerify (include/zkp_bls_agg_g2.h)
+def bls_aggregate_signatures(sigs, groups, bits=None, absent_from=None, engine=None):
+    """Aggregate: the sums of min-pk signatures, (points (n, 24), inf (n,)) (PairingEngine.g2_segment_sum).  sigs (n_sig, 24) finite points
+    of G2, groups lists of rows of sigs (through committee_entries, with its bits and absent_from) or a ready (idx, seg_off) pair"""
+    idx, seg_off = _entries(groups, bits, absent_from)
+    out, inf, _ = (engine or default_engine()).g2_segment_sum(sigs, idx, seg_off)
+    return out, inf
+
+
+def bls_minsig_aggregate_keys(table, committees, bits=None, absent_from=None, engine=None):
+    """bls_aggregate_keys for the minimal-signature-size layout: the committees' aggregate public keys in G2, (points (n, 24), inf (n,))"""
+    idx, seg_off = _entries(committees, bits, absent_from)
+    out, inf, _ = (engine or default_engine()).g2_segment_sum(table, idx, seg_off)
+    return out, inf
+
+
+def bls_minsig_fast_aggregate_verify_batch(table, committees, msgs, sigs, dst, bits=None, absent_from=None, rand=None, points_checked=False, inf_sig=None,
+                                           engine=None):
+    """bls_fast_aggregate_verify_batch for the minimal-signature-size layout (PairingEngine.bls_minsig_fast_aggregate_verify): table
+    (n_table, 24) validated public keys in G2, signatures (n, 12) in G1"""
+    idx, seg_off = _entries(committees, bits, absent_from)
+    return (engine or default_engine()).bls_minsig_fast_aggregate_verify(table, idx, seg_off, msgs, sigs, dst, inf_sig=inf_sig, rand=rand,
+                                                                         points_checked=points_checked)
+
+
+def bls_minsig_fast_aggregate_verify_each(table, committees, msgs, sigs, dst, bits=None, absent_from=None, points_checked=False, inf_sig=None, engine=None):
+    """bool array (n,): aggregate i verifies - the G2 segment sums, then bls_minsig_verify_each on them, ANDed with the statuses and with
+    the committee not being empty"""
+    e = engine or default_engine()
+    idx, seg_off = _entries(committees, bits, absent_from)
+    apk, inf, st = e.g2_segment_sum(table, idx, seg_off)
+    ok = bls_minsig_verify_each(apk, msgs, sigs, dst, points_checked=points_checked, inf_pk=inf, inf_sig=inf_sig, engine=e)
+    return ok & (np.asarray(st) == 0) & (np.diff(seg_off.astype(np.int64)) > 0)
+
+
+def bls_aggregate_verify_batch(pks, msgs, seg_off, sigs, dst, rand=None, points_checked=False, inf_pk=None, inf_sig=None, engine=None):
+    """AggregateVerify, batched: True iff every signature j (sigs (n, 24)) verifies over the pairs (pks[i], msgs[i]) for i in
+    [seg_off[j], seg_off[j + 1]) (PairingEngine.bls_aggregate_verify): public keys (n_msg, 12), messages a list of n_msg bytes, seg_off
+    (n + 1,).  A segment without a pair fails the batch.  The messages of one signature are not tested for distinctness (the
+    proof-of-possession scheme); the basic scheme's rule is the caller's."""
+    return (engine or default_engine()).bls_aggregate_verify(pks, msgs, seg_off, sigs, dst, inf_pk=inf_pk, inf_sig=inf_sig, rand=rand,
+                                                             points_checked=points_checked)
+
+
+def bls_aggregate_verify_each(pks, msgs, seg_off, sigs, dst, points_checked=False, inf_pk=None, inf_sig=None, engine=None):
+    """bool array (n,): signature j verifies over its pairs.  One bls_verify call per segment on an expansion built here: the signature
+    under the segment's first message, the flagged identity under the others, rand rows (1, 0).  An empty segment is False."""
+    e = engine or default_engine()
+    pks = np.ascontiguousarray(pks, dtype=np.uint64).reshape(-1, 12)
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint64).reshape(-1, 24)
+    off = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+    n, n_msg = sigs.shape[0], pks.shape[0]
+    if off.size != n + 1 or len(msgs) != n_msg:
+        raise ValueError("%d messages, %d public keys; %d offsets for %d signatures" % (len(msgs), n_msg, off.size, n))
+    if int(off[0]) != 0 or int(off[-1]) != n_msg or (n and bool((off[1:] < off[:-1]).any())):
+        raise ValueError("seg_off does not run from 0 to the number of messages without decreasing")
+    ip = np.zeros(n_msg, dtype=np.uint8) if inf_pk is None else np.ascontiguousarray(inf_pk, dtype=np.uint8).reshape(n_msg)
+    isg = np.zeros(n, dtype=np.uint8) if inf_sig is None else np.ascontiguousarray(inf_sig, dtype=np.uint8).reshape(n)
+    ok = np.zeros(n, dtype=bool)
+    for j in range(n):
+        lo, hi = int(off[j]), int(off[j + 1])
+        k = hi - lo
+        if k == 0:
+            continue
+        xs = np.zeros((k, 24), dtype=np.uint64)
+        xs[:, 12] = 1
+        xs[0] = sigs[j]
+        xi = np.ones(k, dtype=np.uint8)
+        xi[0] = isg[j]
+        r = np.zeros((k, 2), dtype=np.uint64)
+        r[:, 0] = 1
+        ok[j] = e.bls_verify(pks[lo:hi], list(msgs[lo:hi]), xs, dst, inf_pk=ip[lo:hi], inf_sig=xi, rand=r, points_checked=points_checked)
+    return ok
+
+
 # ------------------------------------------------------------------------------------------------ verification grouped by message (include/zkp_bls_grouped.h)
 def group_by_message(messages):
     """A list of n messages (bytes) -> (perm int64 (n,), distinct (list of m bytes), grp_off uint64 (m + 1,)): the order bls_verify_grouped

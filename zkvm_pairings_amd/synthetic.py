@@ -442,6 +442,58 @@ def bls_aggregate_instance(n_table, sizes, seed=SEED, engine=None, dst=b"BLS_SIG
     return sks, table, committees, msgs, sigs
 
 
+def bls_minsig_aggregate_instance(n_table, sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_POP_"):
+    """bls_aggregate_instance in the minimal-signature-size layout: a table of n_table keys [sk] g2 and one valid aggregate signature in
+    G1 per committee size, sig_i = [sum sk] H(m_i).  -> (sks (n_table, 4), table (n_table, 24), committees (list of lists), msgs,
+    sigs (n, 12))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    n = len(sizes)
+    sks = scalars(seed ^ 0xA67, n_table)
+    table, _ = engine.g2_mul(G2_GENERATOR, sks) if n_table else (np.zeros((0, 24), dtype=np.uint64), None)
+    draw = splitmix64(seed ^ 0xC0118, int(sum(sizes)))
+    committees, at = [], 0
+    for k in sizes:
+        committees.append([int(v % np.uint64(n_table)) for v in draw[at:at + k]])
+        at += k
+    raw = splitmix64(seed ^ 0x5E5B, 9 * n).reshape(n, 9) if n else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [raw[i, 1:].tobytes()[:int(raw[i, 0]) % 64] for i in range(n)]
+    if n == 0:
+        return sks, table, committees, msgs, np.zeros((0, 12), dtype=np.uint64)
+    sums = np.stack([int_to_scalar(sum(scalar_to_int(sks[r]) for r in c) % R_ORDER) for c in committees])
+    h, _ = engine.hash_to_g1(msgs, dst)
+    sigs, inf = engine.g1_mul(h, sums)
+    sigs[inf != 0] = 0
+    sigs[inf != 0, 6] = 1
+    return sks, table, committees, msgs, sigs
+
+
+def bls_aggregate_verify_instance(sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
+    """n = len(sizes) valid aggregate signatures for AggregateVerify from the seed: signature j is the sum of sizes[j] individual
+    signatures [sk_i] H(m_i) by distinct keys on distinct messages (the message's number leads), summed by g2_segment_sum.
+    -> (sks (n_msg, 4), pks (n_msg, 12), msgs (list of n_msg bytes), seg_off uint64 (n + 1,), sigs (n, 24))"""
+    if engine is None:
+        from .pairings import default_engine
+        engine = default_engine()
+    n, n_msg = len(sizes), int(sum(sizes))
+    sks = scalars(seed ^ 0xA6B, n_msg)
+    raw = splitmix64(seed ^ 0x5E5C, 9 * n_msg).reshape(n_msg, 9) if n_msg else np.zeros((0, 9), dtype=np.uint64)
+    msgs = [int(i).to_bytes(4, "little") + raw[i, 1:].tobytes()[:int(raw[i, 0]) % 64] for i in range(n_msg)]
+    seg_off = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        seg_off[1:] = np.cumsum(sizes, dtype=np.uint64)
+    if n_msg == 0:
+        sigs = np.zeros((n, 24), dtype=np.uint64)
+        sigs[:, 12] = 1
+        return sks, np.zeros((0, 12), dtype=np.uint64), msgs, seg_off, sigs
+    pks, _ = engine.g1_mul(G1_GENERATOR, sks)
+    h, _ = engine.hash_to_g2(msgs, dst)
+    each, _ = engine.g2_mul(h, sks)
+    sigs, _, _ = engine.g2_segment_sum(each, np.arange(n_msg, dtype=np.uint32), seg_off)
+    return sks, pks, msgs, seg_off, sigs
+
+
 def bls_grouped_instance(sizes, seed=SEED, engine=None, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
     """n = sum(sizes) valid BLS signatures ORDERED BY MESSAGE over m = len(sizes) distinct messages, from the seed: group g holds sizes[g]
     signatures of message g (a size may be 0: a message nobody signed), sig_i = [sk_i] H(m_g).  The messages are 4 to 67 bytes and
